@@ -8,8 +8,11 @@
 A step = forward (2 x conv + 4 x BiGRU-512 + dense + LayerNorm) + CTC loss + backward + gradient all-reduce (N > 1) +
 GradientClipping(1) + WeightDecay(1e-5) + Adam -- BASELINE.json configs[1] (configs[2] per GPU when N > 1), synthetic
 batch resident in HBM, random-init weights.  One JSON line on rank 0 (see the task contract): value = utterances of
-all ranks / max-over-ranks time; `roofline` = the dominant kernel by time, measured with HIP events in this process;
-`cpu_baseline` = the CPU oracle (oracle/model.py, torch-CPU fp32) timed on this host on a bounded sample (rank 0, N=1).
+all ranks / max-over-ranks time.  With --full (N=1) the line also carries `roofline` = the dominant kernel by time, measured
+with HIP events in this process, and `cpu_baseline` = the CPU oracle (oracle/model.py, torch-CPU fp32) timed on this host on
+a bounded sample; a plain run times its steps and prints the line, nothing else.  --dump-outputs DIR writes the last timed
+step's loss, parameters and gradients as DIR/<name>.npy; that step starts from the seeded weights, so its inputs are the same
+in every run.
 """
 import argparse
 import json
@@ -51,12 +54,18 @@ def parse():
                     "this many conv layers in this process -- with the library ASR_ACT selects -- and print its extra_configs entry as JSON")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-census", action="store_true")
-    ap.add_argument("--census", action="store_true", help="N > 1: run the single-stream kernel census on rank 0 after the timed region as the "
-                                                         "N = 1 line does (default at N > 1: skipped, the line is the scaling point only)")
+    ap.add_argument("--census", action="store_true", help="run the single-stream kernel census on rank 0 after the timed region (default: "
+                                                         "only --full at N = 1 runs it; at N > 1 the line is the scaling point only)")
     ap.add_argument("--no-extra", action="store_true", help="skip extra_configs (Gram-CTC at configs[3] size, the two configs[4] CNN steps, "
                                                            "the ragged-length step)")
     ap.add_argument("--ragged", action="store_true", help="time the step on the ragged batch of SURVEY 8d (x_length ~ U{600..T}, "
                                                           "length-exact recurrences) instead of full-length utterances")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also measure what the headline figure does not need: the "
+                                                        "kernel census and rooflines, extra_configs, the CPU baseline and its parity gate "
+                                                        "(default: off, the run times its steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step handed "
+                                                                        "its caller (loss, parameters, gradients) as DIR/<name>.npy; "
+                                                                        "that step starts from the seeded weights and optimiser state")
     return ap.parse_args()
 
 
@@ -879,6 +888,58 @@ def spawn_ranks(args):
         raise SystemExit(rc if rc != 0 else 1)
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 16
+
+
+def dump_outputs(dirname, loss, model):
+    """--dump-outputs DIR: what the last timed step handed its caller -- the loss (float64), and every parameter after the update with
+    the gradient that update used (float32) -- as DIR/loss.npy, DIR/param.<name>.npy, DIR/grad.<name>.npy.  An array of more than
+    DUMP_SAMPLE elements (fewer if there are many arrays: 64 MB in all) is written as a sample at fixed flat indices (sorted, drawn
+    from a generator seeded with 0), the same for a parameter and its gradient and in every run with the same arguments.  The batch
+    is seeded and the last timed step starts from the seeded weights and optimiser state (seeded_restart), so two runs with the same
+    arguments write the same arrays up to the rounding of the backward pass's float atomics."""
+    import numpy as np
+    tensors = [("loss", loss.detach().reshape(1))]
+    for name, p in model.named_parameters():
+        tensors.append(("param." + name, p.detach()))
+        if p.grad is not None:
+            tensors.append(("grad." + name, p.grad.detach()))
+    cap = max(1024, min(DUMP_SAMPLE, DUMP_MAX_BYTES // (8 * len(tensors))))
+    arrays = {}
+    for name, t in tensors:
+        flat = t.reshape(-1)
+        if flat.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(flat.numel(), cap, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        arrays[name] = flat.double().cpu().numpy() if name == "loss" else flat.float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, total
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    log("outputs: %d arrays, %.1f MB -> %s" % (len(arrays), total / 1e6, dirname))
+
+
+def seeded_restart(opt, model):
+    """--dump-outputs: the last timed step starts again from the seeded weights and optimiser state, so that its inputs are the same
+    in every run.  The float atomics of the backward pass (split-K weight gradients, bias and norm sums) add in no fixed order; one
+    step from the same inputs agrees to rounding (~1e-7), but every further step feeds that rounding back into the weights, and a
+    few steps of Adam at this learning rate amplify it until two runs' weights and gradients differ in every digit.  A snapshot
+    of the master weights and the optimiser state is taken now, before any step; the returned callable copies it back (device
+    copies on the launch stream, ~0.3 GB) and redoes the bf16 weight copies as the optimiser's own update does."""
+    from asr.link import bump_weight_epoch, refresh_compute_copies
+    bufs = [opt.flat_parameters()] + [b for b in opt._state_buffers() if b is not None]
+    snap = [b.clone() for b in bufs]
+
+    def restart():
+        for dst, src in zip(bufs, snap):
+            dst.copy_(src)
+        bump_weight_epoch()
+        refresh_compute_copies(model)
+    return restart
+
+
 REGION = {"device_allocations": None}       # hipMalloc calls of the caching allocator inside the last timed region (healthy: 0)
 
 
@@ -893,8 +954,9 @@ def quiesce_host_gc():
     gc.freeze()
 
 
-def timed_region(step, steps, warmup, comm, sync, dev=None):
-    """the contract's timed region: W untimed steps, barrier + synchronize, K steps, synchronize + barrier, MAX over ranks"""
+def timed_region(step, steps, warmup, comm, sync, dev=None, before_last=None):
+    """the contract's timed region: W untimed steps, barrier + synchronize, K steps, synchronize + barrier, MAX over ranks
+    (`before_last`: queued in front of the last timed step)"""
     import torch.distributed as dist
     for _ in range(warmup):
         step()
@@ -906,7 +968,9 @@ def timed_region(step, steps, warmup, comm, sync, dev=None):
     a0 = torch.cuda.memory_stats().get("num_device_alloc", 0) if torch.cuda.is_available() else 0
     t0 = time.perf_counter()
     last = None
-    for _ in range(steps):
+    for i in range(steps):
+        if before_last is not None and i == steps - 1:
+            before_last()
         last = step()
     sync()
     if comm is not None:
@@ -970,6 +1034,10 @@ def rehearse(args, world, rank):
         return float(g[0])
     dt, per_rank, last = timed_region(step, args.steps, args.warmup, comm, lambda: None)
     ranks = rank_evidence(comm, world, rank, None)
+    if rank == 0 and args.dump_outputs:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "check.npy"), np.asarray([last], dtype=np.float64))
     if rank == 0:
         emit({"metric": "utterances/sec (T=1000, 40x3 feat, |V|~3000) CTC train step", "value": world * args.batch * args.steps / dt,
               "unit": "utterances/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
@@ -985,6 +1053,10 @@ def main():
     args = parse()
     if args.vocab is None:
         args.vocab = 3000 if args.config == "ds2" else 119
+    if not args.full:
+        # a plain run: set up, warm up, time the steps, print the line -- nothing after the region but the outputs asked for
+        args.no_extra = args.no_cpu_baseline = True
+        args.no_census = args.no_census or not args.census      # (unless the census is asked for by name)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1037,9 +1109,9 @@ def main():
     x, labels, x_len, l_len = synthetic_batch(B, T, V, seed=rank, ragged=args.ragged)
     x, labels, x_len, l_len = x.to(dev), labels.to(dev), x_len.to(dev), l_len.to(dev)
     model_kw = {"x_length": x_len} if (args.ragged and args.config == "ds2") else {}
-    if args.config == "cnn":
+    if args.config == "cnn" or args.dump_outputs:
         with torch.no_grad():
-            model(x)                             # the recipes size their layer norms lazily: materialise before opt.setup
+            model(x, **model_kw)                 # the recipes size their layer norms lazily: materialise before opt.setup
 
     opt = Adam(alpha=1e-3, beta1=0.9)
     opt.setup(model)
@@ -1047,6 +1119,7 @@ def main():
     opt.add_hook(WeightDecay(1e-5))
     if comm is not None:
         opt.set_communicator(comm)
+    restart = seeded_restart(opt, model) if args.dump_outputs else None
 
     exposed = []
 
@@ -1058,7 +1131,7 @@ def main():
         return loss
 
     log("rank %d/%d: model built, warm-up %d + timing %d steps" % (rank, world, args.warmup, args.steps))
-    dt, per_rank, loss = timed_region(step, args.steps, args.warmup, comm, torch.cuda.synchronize, dev)
+    dt, per_rank, loss = timed_region(step, args.steps, args.warmup, comm, torch.cuda.synchronize, dev, before_last=restart)
     loss_value = loss.item()
     region_allocs = REGION["device_allocations"]
     exposed_ms = None
@@ -1072,6 +1145,8 @@ def main():
 
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss, model)
     ms_per_step = dt / args.steps * 1e3
     value = world * B * args.steps / dt
     out = {"metric": "utterances/sec (T=1000, 40x3 feat, |V|~3000) CTC train step", "value": value, "unit": "utterances/s",
@@ -1103,7 +1178,7 @@ def main():
         out["allreduce_exposed_ms_per_step"] = exposed_ms
 
     # which hand-off the persistent GRU kernels of the last launch agreed on (decided inside the launch: DESIGN.md section 5)
-    if _ops.LAST_SYNC[0] is not None:
+    if args.full and _ops.LAST_SYNC[0] is not None:
         words = _ops.LAST_SYNC[0][960:1008].cpu().tolist()
         nrec = sum(1 for v in words[32:48] if v > 0)
         out["config"]["gru_handoff"] = {"recurrences": nrec, "xcd_of_recurrence": [v - 1 for v in words[0:16] if v > 0],

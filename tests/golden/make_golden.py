@@ -191,7 +191,8 @@ def g_ctc(gc):
         for k, v in r.items():
             out["%s.%s" % (name, k)] = v
     out["names"] = np.array(sorted(cases.keys()))
-    np.savez_compressed(os.path.join(OUT, "gram_ctc.npz"), **out)
+    import gram_ctc_fixture
+    gram_ctc_fixture.save(OUT, out)           # gram_ctc.npz + the |V| = 3000 arrays one utterance per file
 
     # G4 connection matrices (log 0 / zero_padding) for one mixed case
     uni = np.array([[3, 3, 5, 2], [4, 1, 1, 0]], dtype=np.int32)

@@ -1,5 +1,6 @@
 """The CPU oracle against the reference's golden vectors (and torch CPU) -- no GPU needed."""
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -8,8 +9,15 @@ import torch
 from oracle import ctc as octc
 
 
+def _load_gram_ctc(golden_dir):
+    if golden_dir not in sys.path:
+        sys.path.insert(0, golden_dir)
+    import gram_ctc_fixture
+    return gram_ctc_fixture.load(golden_dir)
+
+
 def _cases(golden_dir):
-    g = np.load(os.path.join(golden_dir, "gram_ctc.npz"))
+    g = _load_gram_ctc(golden_dir)
     return g, [str(n) for n in g["names"]]
 
 
