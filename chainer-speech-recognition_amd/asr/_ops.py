@@ -757,6 +757,24 @@ def edit_distance(ref, ref_len, hyp, hyp_len):
     return dist
 
 
+def ctc_beam_search(logits, lengths, blank, beam_width, top_k, min_logp=None):
+    """(T, B, V) f32 logits -> (ids (B, beam_width, T) int32 padded with blank, lengths (B, beam_width) int32,
+    scores (B, beam_width) f32): the N-best of the CTC prefix beam search, best first; unused slots have length 0 and
+    score -inf.  `lengths` (B) int32 or None (all T frames); min_logp None: no candidate threshold."""
+    T, B, V = logits.shape
+    dev = logits.device
+    nbytes = _lib.lib().asr_ctc_beam_workspace_bytes(T, B, V, int(beam_width), int(top_k))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    ids = torch.empty((B, beam_width, T), dtype=I32, device=dev)
+    out_len = torch.empty((B, beam_width), dtype=I32, device=dev)
+    scores = torch.empty((B, beam_width), dtype=torch.float32, device=dev)
+    rc = _lib.lib().asr_ctc_beam_search(stream(), ptr(logits), None if lengths is None else ptr(lengths), T, B, V, int(blank),
+                                        int(beam_width), int(top_k), float("-inf") if min_logp is None else float(min_logp),
+                                        ptr(ws), nbytes, ptr(ids), ptr(out_len), ptr(scores))
+    check(rc, "asr_ctc_beam_search")
+    return ids, out_len, scores
+
+
 def cmn_pspec(pspec, nframes):
     B, Fmax, nbins = pspec.shape
     check(_lib.lib().asr_cmn_pspec(stream(), ptr(pspec), ptr(nframes), B, Fmax, nbins), "asr_cmn_pspec")

@@ -1,4 +1,4 @@
-"""Greedy-decode error rates with the reference's function names (asr/error.py:7-68).
+"""Greedy-decode error rates with the reference's function names (asr/error.py:7-68), and the beam decoder.
 
 ``compute_minibatch_error`` keeps the reference's signature.  Given device tensors it runs the blank / repeat collapse and
 the Levenshtein distances of the whole minibatch on the GPU (``libasr_hip``: asr_ctc_collapse, asr_edit_distance) and brings
@@ -47,14 +47,23 @@ def _needs_retokenisation(vocab_id_to_token, vocab_token_to_id):
     return False
 
 
-def compute_minibatch_error(y_batch, t_batch, BLANK, vocab_token_to_id, vocab_id_to_token, print_sequences=False):
-    """y_batch (B, T): argmax ids per frame; t_batch (B, L): labels padded with BLANK.  Mean over the minibatch of
-    Levenshtein(pred, true) / len(true)  (len(pred) where the transcription is empty)."""
-    dev = torch.device("cuda", torch.cuda.current_device())
-    y = torch.as_tensor(np.asarray(y_batch) if not isinstance(y_batch, torch.Tensor) else y_batch).to(dev, torch.int32).contiguous()
-    t = torch.as_tensor(np.asarray(t_batch) if not isinstance(t_batch, torch.Tensor) else t_batch).to(dev, torch.int32).contiguous()
-    pred, pred_len = _ops.ctc_collapse(y, None, BLANK, True)
-    true, true_len = _ops.ctc_collapse(t, None, BLANK, False)
+def beam_decode(logits, beam_width=16, top_k=16, blank=0, lengths=None, min_logp=None):
+    """(T, B, V) f32 logits on the GPU -> (ids (B, beam_width, T) int32 padded with blank, lengths (B, beam_width) int32,
+    scores (B, beam_width) f32): the N-best labellings of a CTC prefix beam search, best first, each with its log-probability
+    log p(labelling | x) as far as the beam kept its paths (a lower bound on it).  Unused slots: length 0, score -inf.
+    Per frame the candidates are the `top_k` non-blank ids with the largest logits, restricted to those whose log-softmax is
+    at least `min_logp` (None: no threshold).  `lengths` (B) int32 restricts the decode to the valid frames, as in
+    ``greedy_decode``.  The search runs over token ids: with the Gram-CTC inventory two token sequences that spell the same
+    string (a bigram token and its two unigrams) stay two hypotheses and are not merged; ``compute_sequence_error`` retokenises.
+    The reference has no beam decoder; this extends its greedy call sites (run/ctc/cnn/dev.py:102, run/ctc/cnn/test.py:102)."""
+    if lengths is not None:
+        lengths = lengths.to(logits.device, torch.int32).contiguous()
+    return _ops.ctc_beam_search(logits.contiguous(), lengths, blank, beam_width, top_k, min_logp)
+
+
+def _error_rate(pred, pred_len, true, true_len, BLANK, vocab_token_to_id, vocab_id_to_token, print_sequences):
+    """mean over the batch of Levenshtein(pred, true) / len(true) for collapsed id rows on the GPU (asr/error.py:49-68)"""
+    dev = pred.device
     if _needs_retokenisation(vocab_id_to_token, vocab_token_to_id):
         # string work: inherently host side (only for inventories with multi-unigram tokens)
         ph, pl = pred.cpu().numpy(), pred_len.cpu().numpy()
@@ -79,3 +88,35 @@ def compute_minibatch_error(y_batch, t_batch, BLANK, vocab_token_to_id, vocab_id
             print("pred:\t" + "".join(vocab_id_to_token[int(i)] for i in ph[b, :pl[b]]))
             print("true:\t" + "".join(vocab_id_to_token[int(i)] for i in th[b, :tl[b]]))
     return float(per.sum() / len(per))
+
+
+def _device_ids(a, dev):
+    return torch.as_tensor(np.asarray(a) if not isinstance(a, torch.Tensor) else a).to(dev, torch.int32).contiguous()
+
+
+def compute_minibatch_error(y_batch, t_batch, BLANK, vocab_token_to_id, vocab_id_to_token, print_sequences=False):
+    """y_batch (B, T): argmax ids per frame; t_batch (B, L): labels padded with BLANK.  Mean over the minibatch of
+    Levenshtein(pred, true) / len(true)  (len(pred) where the transcription is empty)."""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    y = _device_ids(y_batch, dev)
+    t = _device_ids(t_batch, dev)
+    pred, pred_len = _ops.ctc_collapse(y, None, BLANK, True)
+    true, true_len = _ops.ctc_collapse(t, None, BLANK, False)
+    return _error_rate(pred, pred_len, true, true_len, BLANK, vocab_token_to_id, vocab_id_to_token, print_sequences)
+
+
+def compute_sequence_error(pred, pred_len, t_batch, BLANK, vocab_token_to_id, vocab_id_to_token, print_sequences=False):
+    """The error rate of ``compute_minibatch_error`` for hypotheses that are already collapsed label sequences, e.g. one slot
+    of ``beam_decode``: pred (B, L) ids (entries past pred_len[b] are ignored), pred_len (B); t_batch (B, L') labels padded
+    with BLANK.  Same retokenisation (Gram-CTC inventories) and the same edit-distance tail."""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    p = _device_ids(pred, dev)
+    pl = _device_ids(pred_len, dev)
+    if p.dim() != 2 or pl.shape != (p.shape[0],):
+        raise ValueError("pred must be (B, L) and pred_len (B)")
+    pl = pl.clamp(0, p.shape[1]).contiguous()
+    if p.shape[1] == 0:
+        p = torch.full((p.shape[0], 1), BLANK, dtype=torch.int32, device=dev)
+    t = _device_ids(t_batch, dev)
+    true, true_len = _ops.ctc_collapse(t, None, BLANK, False)
+    return _error_rate(p, pl, true, true_len, BLANK, vocab_token_to_id, vocab_id_to_token, print_sequences)

@@ -1,0 +1,522 @@
+// CTC prefix beam search on the GPU (gfx950): the N most probable labellings of every utterance, with their log-probabilities.
+//
+// The reference decodes greedily only (xp.argmax + the collapse loop: run/ctc/cnn/dev.py:102-106, run/ctc/cnn/test.py:102;
+// csrc/decode.hip here).  This is the standard prefix beam search in log space, in two passes:
+//
+// cand_kernel : one wave per (t, b) row of the (T, B, V) f32 logits, like argmax_rows_kernel; the row is read once.  Writes the
+//               row's log-sum-exp, lp[blank] and the top_k non-blank (id, lp) pairs in rank order (value descending, lower id on
+//               equal values), cut where lp < min_logp.  Each lane keeps the 4 best of its stripe in registers; the wave pops the
+//               best lane head top_k times, and a lane whose 4 were all taken rescans its stripe (L2-hot) for the next 4.
+// beam_kernel : one workgroup per utterance, sequential over frames t < lengths[b].  The beam (label prefixes with pb / pnb, a
+//               64-bit prefix hash, length, last token and the hash / last token of the parent prefix) and the frame's
+//               m + m * n scored entries (stays first, then extensions in (parent rank, candidate rank) order) live in LDS.
+//               An extension h + c that is already a beam prefix is merged into that stay: the stay finds its parent in the
+//               beam by (hash, length, last token).  The best beam_width entries (ties: earlier canonical position) are found
+//               by a radix select on the scores (8 bits per pass); each extension that survives becomes a node (parent node,
+//               token) of the utterance's prefix table in the workspace, and a final backtrack writes the N-best ids.  The next
+//               frame's candidate row and repeat-stay logits are loaded one frame ahead.
+// Integer atomics only, on LDS histograms: the same inputs give bitwise the same outputs on every launch.
+#include "common.hpp"
+#include "../../include/asr_hip.h"
+
+namespace asr {
+namespace beam {
+
+constexpr int MAX_BEAM = 128, MAX_TOPK = 64, MAX_EXT = 4096;      // beam_width, top_k, beam_width * top_k
+constexpr int MAX_ENTRIES = MAX_BEAM + MAX_EXT;
+constexpr int THREADS = 256;
+constexpr int NONE = 0x7fffffff;
+
+struct Ws {
+    float* lse;         // (T * B)           row log-sum-exp
+    float* lpb;         // (T * B)           lp[blank]
+    int* n;             // (T * B)           number of candidates kept
+    int* cid;           // (T * B, K)        candidate ids in rank order
+    float* clp;         // (T * B, K)        their log-probabilities
+    int2* node;         // (B, T * W)        prefix table: (parent node or -1, token)
+};
+
+__host__ __device__ inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// K = min(top_k, V - 1): the candidates a row can have
+__host__ __device__ inline size_t ws_layout(int T, int B, int W, int K, char* base, Ws* ws) {
+    const size_t rows = (size_t)T * B;
+    size_t off = 0;
+    const size_t o_lse = off; off += align256(rows * 4);
+    const size_t o_lpb = off; off += align256(rows * 4);
+    const size_t o_n = off; off += align256(rows * 4);
+    const size_t o_cid = off; off += align256(rows * K * 4);
+    const size_t o_clp = off; off += align256(rows * K * 4);
+    const size_t o_node = off; off += align256(rows * W * 8);
+    if (ws) {
+        ws->lse = (float*)(base + o_lse);
+        ws->lpb = (float*)(base + o_lpb);
+        ws->n = (int*)(base + o_n);
+        ws->cid = (int*)(base + o_cid);
+        ws->clp = (float*)(base + o_clp);
+        ws->node = (int2*)(base + o_node);
+    }
+    return off;
+}
+
+// (v, i) ranks before (w, j): larger value first, lower id on equal values (a total order on non-NaN f32)
+__device__ inline bool before(float v, int i, float w, int j) { return v > w || (v == w && i < j); }
+
+struct Top4 {
+    float v[4];
+    int i[4];
+};
+
+__device__ inline void top4_clear(Top4& s) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { s.v[k] = -INFINITY; s.i[k] = NONE; }
+}
+
+// ids arrive in increasing order within a lane
+__device__ inline void top4_insert(Top4& s, float x, int id) {
+    if (!before(x, id, s.v[3], s.i[3])) return;
+    s.v[3] = x;
+    s.i[3] = id;
+#pragma unroll
+    for (int k = 3; k > 0; --k) {
+        if (before(s.v[k], s.i[k], s.v[k - 1], s.i[k - 1])) {
+            const float tv = s.v[k]; s.v[k] = s.v[k - 1]; s.v[k - 1] = tv;
+            const int ti = s.i[k]; s.i[k] = s.i[k - 1]; s.i[k - 1] = ti;
+        }
+    }
+}
+
+template <int CTRL>
+__device__ inline void best_dpp(float& v, int& i) {
+    const float ov = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
+    const int oi = __builtin_amdgcn_update_dpp(0, i, CTRL, 0xf, 0xf, false);
+    if (before(ov, oi, v, i)) { v = ov; i = oi; }
+}
+
+// the best (v, i) of the wave in every lane: within rows of 16 lanes by DPP (quad swaps, half-row and row mirrors), then two
+// cross-row shuffles -- the selection's serial step, so two LDS round trips instead of six
+__device__ inline void wave_best(float& v, int& i) {
+    best_dpp<0xB1>(v, i);       // quad_perm [1, 0, 3, 2]
+    best_dpp<0x4E>(v, i);       // quad_perm [2, 3, 0, 1]
+    best_dpp<0x141>(v, i);      // row_half_mirror
+    best_dpp<0x140>(v, i);      // row_mirror
+#pragma unroll
+    for (int off = 16; off < 64; off <<= 1) {
+        const float ov = __shfl_xor(v, off);
+        const int oi = __shfl_xor(i, off);
+        if (before(ov, oi, v, i)) { v = ov; i = oi; }
+    }
+}
+
+// the 4 best non-blank elements of this lane's stripe that rank after (av, ai); with LSE also the lane's (max, sum exp)
+template <bool LSE>
+__device__ inline void scan_stripe(const float* __restrict__ p, int V, int blank, int lane, float av, int ai, Top4& s, float& m,
+                                   float& sum) {
+    top4_clear(s);
+    auto take = [&](float f, int v) {
+        if (LSE) {
+            const float hi = fmaxf(m, f), lo = fminf(m, f);
+            const float e = lo == -INFINITY ? 0.f : __expf(lo - hi);
+            sum = f > m ? sum * e + 1.f : sum + e;
+            m = hi;
+        }
+        if (v != blank && before(av, ai, f, v)) top4_insert(s, f, v);
+    };
+    int v = lane;
+    for (; v + 64 * 7 < V; v += 64 * 8) {
+        float f[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) f[k] = p[v + 64 * k];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) take(f[k], v + 64 * k);
+    }
+    for (; v < V; v += 64) take(p[v], v);
+}
+
+__global__ __launch_bounds__(256) void cand_kernel(const float* __restrict__ x, const int32_t* __restrict__ lengths, int T, int B,
+                                                   int V, int blank, int K, float min_logp, Ws ws) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + wave;       // row = t * B + b
+    if (row >= (long long)T * B) return;
+    const int t = (int)(row / B), b = (int)(row - (long long)t * B);
+    if (lengths && t >= lengths[b]) return;                        // frames past the utterance are never read
+    const float* p = x + row * V;
+    Top4 s;
+    float m = -INFINITY, sum = 0.f;
+    scan_stripe<true>(p, V, blank, lane, INFINITY, -1, s, m, sum);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float om = __shfl_xor(m, off), os = __shfl_xor(sum, off);
+        const float hi = fmaxf(m, om);
+        if (hi != -INFINITY) sum = (m == -INFINITY ? 0.f : sum * __expf(m - hi)) + (om == -INFINITY ? 0.f : os * __expf(om - hi));
+        m = hi;
+    }
+    const float lse = m + logf(sum);
+    int my_id = 0, n = 0, taken = 0;
+    float my_lp = 0.f;
+    for (int r = 0; r < K; ++r) {
+        float bv = s.v[0];
+        int bi = s.i[0];
+        wave_best(bv, bi);
+        if (bi == NONE) break;                       // fewer than K orderable elements (NaN rows)
+        const float lp = bv - lse;
+        if (lp < min_logp) break;                    // ranks are by value: the rest are below the threshold too
+        if (lane == r) { my_id = bi; my_lp = lp; }
+        n = r + 1;
+        if (s.i[0] == bi) {                          // this lane held it: pop
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { s.v[k] = s.v[k + 1]; s.i[k] = s.i[k + 1]; }
+            s.v[3] = -INFINITY;
+            s.i[3] = NONE;
+            if (++taken == 4 && r + 1 < K) {        // all 4 taken: the next 4 of the stripe, after the one just taken
+                taken = 0;
+                float dm = 0.f, ds = 0.f;
+                scan_stripe<false>(p, V, blank, lane, bv, bi, s, dm, ds);
+            }
+        }
+    }
+    if (lane < n) {
+        ws.cid[row * K + lane] = my_id;
+        ws.clp[row * K + lane] = my_lp;
+    }
+    if (lane == 0) {
+        ws.lse[row] = lse;
+        ws.lpb[row] = p[blank] - lse;
+        ws.n[row] = n;
+    }
+}
+
+__device__ inline float lae(float a, float b) {       // log(exp(a) + exp(b))
+    const float hi = fmaxf(a, b), lo = fminf(a, b);
+    if (lo == -INFINITY) return hi;
+    return hi + log1pf(expf(lo - hi));
+}
+
+__device__ inline unsigned long long fin64(unsigned long long z) {   // splitmix64 finaliser (a bijection)
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+constexpr unsigned long long ROOT_HASH = 0x9E3779B97F4A7C15ull;
+
+// hash of the prefix h + c from the hash of h
+__device__ inline unsigned long long hash_append(unsigned long long h, int c) {
+    return fin64(fin64(h) ^ (unsigned long long)(unsigned)(c + 1));
+}
+
+// larger score -> larger key; NaN and -inf entries are not valid and never get here
+__device__ inline unsigned order_key(float f) {
+    const unsigned u = __float_as_uint(f + 0.f);          // -0 -> +0
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ inline bool valid(float f) { return f > -INFINITY; }     // false for -inf and NaN
+
+struct Beam {
+    float pb[MAX_BEAM], pnb[MAX_BEAM];
+    unsigned long long hash[MAX_BEAM], phash[MAX_BEAM];       // prefix hash, hash of the prefix without its last token
+    int len[MAX_BEAM], last[MAX_BEAM], plast[MAX_BEAM], node[MAX_BEAM];   // last = -1 for the empty prefix
+    float xl[MAX_BEAM];                                         // the logit of `last` in the frame the beam goes into
+};
+
+// exclusive scan over the workgroup's 256 threads (wsum: 4 ints of LDS); *total = the sum over all threads
+__device__ inline int block_excl_scan(int v, int* wsum, int* total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int incl = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int o = __shfl_up(incl, off);
+        if (lane >= off) incl += o;
+    }
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    int before_me = 0;
+    for (int w = 0; w < wave; ++w) before_me += wsum[w];
+    *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    __syncthreads();
+    return before_me + incl - v;
+}
+
+__global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__ x, const int32_t* __restrict__ lengths, int T, int B,
+                                                       int V, int W, int K, int blank, Ws ws, int32_t* __restrict__ out_ids,
+                                                       int32_t* __restrict__ out_len, float* __restrict__ out_score) {
+    __shared__ Beam bm[2];
+    __shared__ float tot[MAX_ENTRIES];                 // scores of the frame's entries in canonical order
+    __shared__ float btot[MAX_BEAM], spb[MAX_BEAM], spnb[MAX_BEAM];
+    __shared__ int par[MAX_BEAM], cnd[MAX_BEAM];      // a stay's parent prefix (beam slot) and the candidate rank of its last token
+    __shared__ int cid[MAX_TOPK];
+    __shared__ float clp[MAX_TOPK];
+    __shared__ unsigned hist[2][256];
+    __shared__ float sv_tot[MAX_BEAM];
+    __shared__ int sv_pos[MAX_BEAM];
+    __shared__ float xnext[MAX_BEAM + MAX_TOPK];       // next frame's logits of the beam's last tokens, then of the candidates
+    __shared__ int wsum[4];
+    __shared__ int s_digit, s_need, s_all, s_done;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int len_b = lengths ? min(max(lengths[b], 0), T) : T;
+    int2* nodes = ws.node + (size_t)b * T * W;
+    if (tid == 0) {
+        bm[0].pb[0] = 0.f;
+        bm[0].pnb[0] = -INFINITY;
+        bm[0].hash[0] = ROOT_HASH;
+        bm[0].phash[0] = 0;
+        bm[0].len[0] = 0;
+        bm[0].last[0] = -1;
+        bm[0].plast[0] = -2;
+        bm[0].node[0] = -1;
+    }
+    int cur = 0, m = 1;
+    // a frame's candidate row, loaded one frame ahead so that its latency stays off the serial path
+    int q_n = 0, q_id = 0;
+    float q_lse = 0.f, q_lpb = 0.f, q_lp = 0.f;
+    auto load_row = [&](int t) {
+        const size_t row = (size_t)t * B + b;
+        q_n = ws.n[row];
+        q_lse = ws.lse[row];
+        q_lpb = ws.lpb[row];
+        if (tid < K) {                                 // entries past n are never used
+            q_id = ws.cid[row * K + tid];
+            q_lp = ws.clp[row * K + tid];
+        }
+    };
+    if (len_b > 0) load_row(0);
+    __syncthreads();
+    for (int t = 0; t < len_b; ++t) {
+        const Beam& o = bm[cur];
+        Beam& nx = bm[cur ^ 1];
+        const int n = min(q_n, K);
+        const float lse = q_lse, lpb = q_lpb;
+        // A: the frame's candidates
+        if (tid < n) {
+            cid[tid] = q_id;
+            clp[tid] = q_lp;
+        }
+        if (tid < m) {
+            btot[tid] = lae(o.pb[tid], o.pnb[tid]);
+            par[tid] = -1;
+            cnd[tid] = -1;
+        }
+        hist[0][tid] = 0;
+        __syncthreads();
+        // issue the next frame's loads now; they land during this frame's work: its candidate row, and the logit of every
+        // token that can end a prefix after this frame (the beam's last tokens and this frame's candidates), for the repeat stays
+        float gx = 0.f;
+        if (t + 1 < len_b) {
+            load_row(t + 1);
+            const float* xr = x + ((size_t)(t + 1) * B + b) * V;
+            if (tid < m) {
+                if (o.len[tid] > 0) gx = xr[o.last[tid]];
+            } else if (tid < m + n) {
+                gx = xr[cid[tid - m]];
+            }
+        }
+        // B: extension scores; for every non-empty stay, its parent prefix in the beam (by hash, length and last token) and the
+        // candidate rank of its last token -- the extension of that parent which equals the stay's prefix
+        const int E = m + m * n;
+        for (int e = m + tid; e < E; e += THREADS) {
+            const int q = e - m, j = q / n, r = q - j * n;
+            const float base = o.last[j] == cid[r] ? o.pb[j] : btot[j];
+            tot[e] = base + clp[r];
+        }
+        for (int p = tid; p < m * m; p += THREADS) {
+            const int i = p / m, j = p - i * m;
+            if (o.len[i] > 0 && o.hash[j] == o.phash[i] && o.len[j] == o.len[i] - 1 && o.last[j] == o.plast[i]) par[i] = j;
+        }
+        for (int p = tid; p < m * n; p += THREADS) {
+            const int i = p / n, r = p - i * n;
+            if (o.len[i] > 0 && cid[r] == o.last[i]) cnd[i] = r;
+        }
+        __syncthreads();
+        // C: stays, merged with that extension (one entry, at the stay's position)
+        if (tid < m) {
+            const int i = tid, j = par[i], r = cnd[i];
+            const float npb = btot[i] + lpb;
+            float npnb = o.len[i] > 0 ? o.pnb[i] + (o.xl[i] - lse) : -INFINITY;
+            if (j >= 0 && r >= 0) {
+                const float base = o.last[j] == o.last[i] ? o.pb[j] : btot[j];
+                npnb = lae(npnb, base + clp[r]);
+                tot[m + j * n + r] = -INFINITY;
+            }
+            spb[i] = npb;
+            spnb[i] = npnb;
+            tot[i] = lae(npb, npnb);
+        }
+        __syncthreads();
+        // D: radix select of the W best valid entries, 8 bits of the key per pass from the top: key >> sh > tau >> sh, and the
+        // first `need` (canonical order) with key >> sh == tau >> sh.  It stops early once the boundary digit's entries are all kept.
+        const int chunk = (E + THREADS - 1) / THREADS, e0 = min(E, tid * chunk), e1 = min(E, e0 + chunk);
+        unsigned prefix = 0;
+        int need = W, all = 0, sh = 0;
+        for (int shift = 24, pass = 0; shift >= 0; shift -= 8, ++pass) {
+            unsigned* h = hist[pass & 1];
+            hist[(pass + 1) & 1][tid] = 0;           // the next pass's histogram; the last reader of it was the pass before
+            for (int e = e0; e < e1; ++e) {
+                const float f = tot[e];
+                if (!valid(f)) continue;
+                const unsigned key = order_key(f);
+                if (shift == 24 || (key >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&h[(key >> shift) & 255u], 1u);
+            }
+            __syncthreads();
+            if (wave == 0) {
+                int c[4], sum = 0;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { c[k] = (int)h[255 - 4 * lane - k]; sum += c[k]; }
+                int incl = sum;
+#pragma unroll
+                for (int off = 1; off < 64; off <<= 1) {
+                    const int u = __shfl_up(incl, off);
+                    if (lane >= off) incl += u;
+                }
+                const int count = __shfl(incl, 63);
+                if (shift == 24 && count <= W) {
+                    if (lane == 0) s_all = 1;
+                } else {
+                    if (lane == 0) s_all = 0;
+                    const unsigned long long hit = __ballot(incl >= need);
+                    const int L = __ffsll((long long)hit) - 1;
+                    if (lane == L) {
+                        int acc = incl - sum;
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            if (acc + c[k] >= need) {
+                                s_digit = 255 - 4 * lane - k;
+                                s_need = need - acc;
+                                s_done = acc + c[k] == need;
+                                break;
+                            }
+                            acc += c[k];
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+            if (s_all) { all = 1; break; }
+            prefix |= (unsigned)s_digit << shift;
+            need = s_need;
+            sh = shift;
+            if (s_done) break;          // (s_digit / s_need / s_done are rewritten after the next pass's first barrier)
+        }
+        const unsigned tau = all ? 0u : prefix;
+        const int need_eq = all ? 0 : need;
+        // E: compact the kept entries in canonical order
+        int gt = 0, eq = 0;
+        for (int e = e0; e < e1; ++e) {
+            const float f = tot[e];
+            if (!valid(f)) continue;
+            const unsigned key = order_key(f) >> sh;
+            gt += key > tau >> sh;
+            eq += key == tau >> sh;
+        }
+        int packed_total;
+        const int packed = block_excl_scan((gt << 16) | eq, wsum, &packed_total);
+        int g = packed >> 16, q = packed & 0xffff;
+        for (int e = e0; e < e1; ++e) {
+            const float f = tot[e];
+            if (!valid(f)) continue;
+            const unsigned key = order_key(f) >> sh;
+            int slot = -1;
+            if (key > tau >> sh) slot = g + min(q, need_eq), ++g;
+            else if (key == tau >> sh) { if (q < need_eq) slot = g + q; ++q; }
+            if (slot >= 0) { sv_pos[slot] = e; sv_tot[slot] = f; }
+        }
+        const int M = (packed_total >> 16) + min(packed_total & 0xffff, need_eq);
+        if (tid < m + n) xnext[tid] = gx;
+        __syncthreads();
+        // F: rank the survivors (score descending, canonical position on ties) into the next beam
+        if (tid < M) {
+            const float f = sv_tot[tid];
+            int rank = 0;
+            for (int u = 0; u < M; ++u) {
+                const float g2 = sv_tot[u];
+                rank += g2 > f || (g2 == f && u < tid);
+            }
+            const int e = sv_pos[tid];
+            if (e < m) {
+                nx.pb[rank] = spb[e];
+                nx.pnb[rank] = spnb[e];
+                nx.hash[rank] = o.hash[e];
+                nx.phash[rank] = o.phash[e];
+                nx.len[rank] = o.len[e];
+                nx.last[rank] = o.last[e];
+                nx.plast[rank] = o.plast[e];
+                nx.node[rank] = o.node[e];
+                nx.xl[rank] = xnext[e];
+            } else {
+                const int q2 = e - m, j = q2 / n, r = q2 - j * n, c = cid[r];
+                const int id = t * W + rank;
+                nx.pb[rank] = -INFINITY;
+                nx.pnb[rank] = f;
+                nx.hash[rank] = hash_append(o.hash[j], c);
+                nx.phash[rank] = o.hash[j];
+                nx.len[rank] = o.len[j] + 1;
+                nx.last[rank] = c;
+                nx.plast[rank] = o.last[j];
+                nx.node[rank] = id;
+                nx.xl[rank] = xnext[m + r];
+                nodes[id] = make_int2(o.node[j], c);
+            }
+        }
+        __syncthreads();
+        cur ^= 1;
+        m = M;
+    }
+    __threadfence();
+    __syncthreads();
+    const Beam& o = bm[cur];
+    // the N-best, sorted by score: ids padded with blank, then each hypothesis walks its prefix table chain back to the root
+    int32_t* ids = out_ids + (size_t)b * W * T;
+    for (size_t k = tid; k < (size_t)W * T; k += THREADS) {
+        const int i = (int)(k / T), p = (int)(k - (size_t)i * T);
+        if (p >= (i < m ? o.len[i] : 0)) ids[k] = blank;
+    }
+    if (tid < W) {
+        if (tid < m) {
+            const int L = o.len[tid];
+            out_len[b * W + tid] = L;
+            out_score[b * W + tid] = lae(o.pb[tid], o.pnb[tid]);
+            int nd = o.node[tid];
+            for (int p = L - 1; p >= 0; --p) {
+                const int2 e = nodes[nd];
+                ids[(size_t)tid * T + p] = e.y;
+                nd = e.x;
+            }
+        } else {
+            out_len[b * W + tid] = 0;
+            out_score[b * W + tid] = -INFINITY;
+        }
+    }
+}
+
+}  // namespace beam
+}  // namespace asr
+
+using namespace asr;
+using namespace asr::beam;
+
+extern "C" size_t asr_ctc_beam_workspace_bytes(int T, int B, int V, int beam_width, int top_k) {
+    if (T <= 0 || B <= 0 || V <= 0 || beam_width <= 0 || top_k <= 0) return 0;
+    return ws_layout(T, B, beam_width, min(top_k, V - 1), nullptr, nullptr);
+}
+
+extern "C" int asr_ctc_beam_search(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank,
+                                   int beam_width, int top_k, float min_logp, void* workspace, size_t workspace_bytes,
+                                   int32_t* out_ids, int32_t* out_len, float* out_score) {
+    if (!logits || !workspace || !out_ids || !out_len || !out_score || T <= 0 || B <= 0 || V <= 0 || blank < 0 || blank >= V ||
+        beam_width <= 0 || top_k <= 0)
+        return ASR_ERR_BAD_ARG;
+    if (beam_width > MAX_BEAM || top_k > MAX_TOPK || beam_width * top_k > MAX_EXT) return ASR_ERR_UNSUPPORTED;
+    if ((long long)T * beam_width > 0x7fffffffLL) return ASR_ERR_UNSUPPORTED;     // prefix table node ids are int32
+    const int K = min(top_k, V - 1);
+    Ws ws;
+    const size_t need = ws_layout(T, B, beam_width, K, (char*)workspace, &ws);
+    if (workspace_bytes < need) return ASR_ERR_WORKSPACE;
+    const long long rows = (long long)T * B;
+    hipLaunchKernelGGL(cand_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, lengths, T, B, V,
+                       blank, K, min_logp, ws);
+    ASR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(beam_kernel, dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V, beam_width, K, blank, ws,
+                       out_ids, out_len, out_score);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}

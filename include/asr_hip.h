@@ -134,6 +134,20 @@ int asr_ctc_collapse(void* stream, const int32_t* ids, const int32_t* lengths, i
                      int32_t* out, int32_t* out_len);
 int asr_edit_distance(void* stream, const int32_t* ref, const int32_t* ref_len, int ref_pitch, const int32_t* hyp,
                       const int32_t* hyp_len, int hyp_pitch, int pairs, int32_t* dist);
+/* CTC prefix beam search: the N-best counterpart of the greedy decode above (xp.argmax at run/ctc/cnn/dev.py:102-106 and
+ * run/ctc/cnn/test.py:102, then the collapse of asr/error.py:38-47); the reference has no beam decoder.  Log-space prefix beam
+ * search over (T, B, V) f32 pre-softmax logits (the CTC loss's input), frames < lengths[b] (NULL: all T; later frames are never
+ * read).  Per frame the candidates are the top_k non-blank ids by value (lower id on equal values; top_k above V - 1 acts as
+ * V - 1), those with log-softmax >= min_logp (-INFINITY: no threshold); the beam keeps the beam_width best prefixes by
+ * log p = logaddexp(p_blank, p_nonblank), ties to the earlier canonical position.
+ *   out_ids   (B, beam_width, T) the final beam sorted by score descending, label ids padded with blank
+ *   out_len   (B, beam_width)    labelling lengths; unused slots 0       out_score (B, beam_width) f32 log-probability, unused -inf
+ *   workspace asr_ctc_beam_workspace_bytes(T, B, V, beam_width, top_k) bytes
+ * beam_width <= 128, top_k <= 64, beam_width * top_k <= 4096, else ASR_ERR_UNSUPPORTED.  Bitwise reproducible. */
+size_t asr_ctc_beam_workspace_bytes(int T, int B, int V, int beam_width, int top_k);
+int asr_ctc_beam_search(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank, int beam_width,
+                        int top_k, float min_logp, void* workspace, size_t workspace_bytes, int32_t* out_ids, int32_t* out_len,
+                        float* out_score);
 
 /* ---------------------------------------------------------------------------------------- dense projections
  * bf16 MFMA GEMMs (f32 accumulate).  Replace the BLAS/cuDNN calls behind chainer.links.Linear, the 1x1
