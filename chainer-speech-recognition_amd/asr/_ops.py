@@ -775,6 +775,28 @@ def ctc_beam_search(logits, lengths, blank, beam_width, top_k, min_logp=None):
     return ids, out_len, scores
 
 
+def ctc_align(xs, label_unigram, label_bigram, x_len, l_len, blank):
+    """(T, B, V) f32 logits + labels (B, Lmax) int32 (label_bigram None: CTC, else Gram-CTC) -> the forced alignment
+    (frame_ids (B, T), tok_ids, tok_pos, tok_start, tok_end (B, Lmax) int32, tok_logp (B, Lmax) f32, n_tok (B) int32,
+    score (B) f32) of asr_ctc_align; x_len / l_len (B) int32 or None."""
+    T, B, V = xs.shape
+    Lmax = label_unigram.shape[1]
+    dev = xs.device
+    gram = label_bigram is not None
+    nbytes = _lib.lib().asr_ctc_align_workspace_bytes(T, B, V, Lmax, int(gram))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    frames = torch.empty((B, T), dtype=I32, device=dev)
+    tok = [torch.empty((B, Lmax), dtype=I32, device=dev) for _ in range(4)]
+    tok_logp = torch.empty((B, Lmax), dtype=torch.float32, device=dev)
+    n_tok = torch.empty((B,), dtype=I32, device=dev)
+    score = torch.empty((B,), dtype=torch.float32, device=dev)
+    rc = _lib.lib().asr_ctc_align(stream(), ptr(xs), ptr(label_unigram), ptr(label_bigram), ptr(x_len), ptr(l_len), T, B, V, Lmax,
+                                  int(blank), ptr(frames), ptr(tok[0]), ptr(tok[1]), ptr(tok[2]), ptr(tok[3]), ptr(tok_logp),
+                                  ptr(n_tok), ptr(score), ptr(ws), nbytes)
+    check(rc, "asr_ctc_align")
+    return frames, tok[0], tok[1], tok[2], tok[3], tok_logp, n_tok, score
+
+
 def cmn_pspec(pspec, nframes):
     B, Fmax, nbins = pspec.shape
     check(_lib.lib().asr_cmn_pspec(stream(), ptr(pspec), ptr(nframes), B, Fmax, nbins), "asr_cmn_pspec")

@@ -1,1 +1,2 @@
 from .ctc import gram_ctc, connectionist_temporal_classification  # noqa: F401
+from .ctc import Alignment, ctc_align, gram_ctc_align  # noqa: F401

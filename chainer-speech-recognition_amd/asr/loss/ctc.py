@@ -9,7 +9,13 @@ Drop-in for (reference file:line)
 ``xs`` may be the reference's tuple/list of T arrays (B, V) or ONE (T, B, V) tensor (what the models
 of this package return with ``split_into_variables=True``: a tuple of views of one buffer, which is
 recognised and used without a copy).
+
+``ctc_align`` / ``gram_ctc_align`` answer the other question about the same lattices: not the sum over all paths but the best
+one, i.e. which frames belong to which token (forced alignment).  The reference has no counterpart; its
+run/gram_ctc/cnn/refine.py:94-107 counts grams on a per-frame argmax that ignores the transcript.
 """
+import collections
+
 import torch
 
 from .. import _lib
@@ -113,3 +119,48 @@ def gram_ctc(xs, label_unigram, label_bigram, blank_symbol, input_length=None, l
     assert label_unigram.shape[1] == label_bigram.shape[1]
     from ..functions import ctc_box_of
     return _CTCFunction.apply(x, label_unigram, label_bigram, input_length, length_unigram, blank_symbol, reduce, ctc_box_of(x))
+
+
+Alignment = collections.namedtuple("Alignment", "frames tokens positions starts ends token_logp n_tokens score")
+Alignment.__doc__ = """Forced alignment of a batch, device tensors: frames (B, T) int32 token id per frame (blank on blank frames and
+past the utterance's length); for k < n_tokens[b]: tokens / positions / starts / ends (B, Lmax) int32 -- the token, the index
+into the unigram labels of the first unigram it covers, its frames [start, end) -- and token_logp (B, Lmax) f32, the sum of its
+log-softmax over those frames (rows k >= n_tokens[b]: blank, 0, 0, 0, 0); n_tokens (B) int32; score (B) f32 log-probability of
+the best path, -inf (with n_tokens 0 and all-blank frames) for an utterance the loss reports as infeasible."""
+
+
+def _align(xs, label_unigram, label_bigram, input_length, label_length, blank):
+    from .. import _ops
+    if xs.dtype != torch.float32:
+        raise TypeError("xs must be float32")                 # asr/loss/gram_ctc.py:241-244
+    for t in (label_unigram, label_bigram, input_length, label_length):
+        if t is not None and t.dtype != torch.int32:
+            raise TypeError("labels and lengths must be int32")   # asr/loss/gram_ctc.py:234-235
+    xs = xs.detach().contiguous()
+    _lib.ptr(xs)                # raises on a CPU tensor: there is no CPU path
+    gram = label_bigram is not None
+    if gram and label_bigram.shape != label_unigram.shape:
+        raise ValueError("label_unigram and label_bigram must have the same shape")   # asr/loss/gram_ctc.py:308
+    cont = lambda t: None if t is None else t.contiguous()      # noqa: E731  (one slot of beam_decode is a strided view)
+    return Alignment(*_ops.ctc_align(xs, cont(label_unigram), cont(label_bigram), cont(input_length), cont(label_length), blank))
+
+
+def ctc_align(x, t, blank_symbol, input_length=None, label_length=None):
+    """Forced (Viterbi) alignment of the labels ``t`` (B, Lmax) int32 to the logits ``x`` under CTC: the best path through the
+    lattice of ``connectionist_temporal_classification``, argument for argument like that loss.  Returns an ``Alignment`` of
+    device tensors; no gradient flows through it.  Decisions are taken in float64 on the raw logits; among equal candidates
+    the smallest step wins (stay, next node, skip), among equal final nodes the last.  ``score <= -loss``.
+    The ids and lengths that ``asr.error.greedy_decode`` returns, and one slot of ``asr.error.beam_decode``
+    (``ids[:, k]``, ``lengths[:, k]``), can be passed as ``t`` / ``label_length`` as they come: that is how a decoded
+    hypothesis gets its time stamps."""
+    xs = _check_common(x, blank_symbol, "no")
+    return _align(xs, t, None, input_length, label_length, blank_symbol)
+
+
+def gram_ctc_align(xs, label_unigram, label_bigram, blank_symbol, input_length=None, length_unigram=None):
+    """Forced alignment under Gram-CTC, argument for argument like ``gram_ctc``: the best path through the unigram + bigram
+    lattice, which also says which decomposition of the transcript the model prefers (``tokens`` holds unigram and bigram ids,
+    ``positions`` where each starts in ``label_unigram``; a bigram covers two positions).  See ``ctc_align``."""
+    x = _check_common(xs, blank_symbol, "no")
+    assert label_unigram.shape[1] == label_bigram.shape[1]
+    return _align(x, label_unigram, label_bigram, input_length, length_unigram, blank_symbol)

@@ -148,6 +148,27 @@ size_t asr_ctc_beam_workspace_bytes(int T, int B, int V, int beam_width, int top
 int asr_ctc_beam_search(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank, int beam_width,
                         int top_k, float min_logp, void* workspace, size_t workspace_bytes, int32_t* out_ids, int32_t* out_len,
                         float* out_score);
+/* CTC / Gram-CTC forced (Viterbi) alignment: the best path through the lattice of the loss above (the same node labels and edges,
+ * built by the same code: label_bigram == NULL is CTC, otherwise Gram-CTC), i.e. which frames belong to which token.  The reference
+ * has no aligner (run/gram_ctc/cnn/refine.py:94-107 counts the grams of a per-frame argmax instead).  Arguments up to `blank` as for
+ * the loss; xl = min(x_len[b], T) (T if NULL), L = clamp(l_len[b], 0, Lmax) (Lmax if NULL).  Every element of every output is
+ * written on every call:
+ *   frame_ids (B, T)     token id the best path emits at frame t; blank on blank frames and for t >= xl
+ *   n_tok     (B)        tokens of the chosen segmentation (CTC: L; Gram-CTC: ceil(L/2) .. L)
+ *   tok_ids, tok_pos, tok_start, tok_end (B, Lmax) int32, tok_logp (B, Lmax) f32, for k < n_tok[b]: the token, the index into
+ *                        label_unigram[b] of the first unigram it covers (the bigram label_bigram[b][i] ends at i: its position is
+ *                        i - 1), the frames [tok_start, tok_end) it occupies and the sum of its log-softmax over them;
+ *                        k >= n_tok[b]: id blank, the rest 0
+ *   score     (B)        log-probability of the best path (<= -loss); an utterance without a live path (the loss reports 1e10):
+ *                        score -inf, n_tok 0, frame_ids all blank
+ * Decisions are taken in float64 on the raw logits; ties go to the smallest diagonal offset, among final nodes to the largest
+ * node index.  Bitwise reproducible.  workspace: the bytes the query below names for (T, B, V, Lmax, gram);
+ * ASR_ERR_UNSUPPORTED where the loss gives it (path too long for LDS). */
+size_t asr_ctc_align_workspace_bytes(int T, int B, int V, int Lmax, int gram);
+int asr_ctc_align(void* stream, const float* xs, const int32_t* label_unigram, const int32_t* label_bigram, const int32_t* x_len,
+                  const int32_t* l_len, int T, int B, int V, int Lmax, int blank, int32_t* frame_ids, int32_t* tok_ids,
+                  int32_t* tok_pos, int32_t* tok_start, int32_t* tok_end, float* tok_logp, int32_t* n_tok, float* score,
+                  void* workspace, size_t workspace_bytes);
 
 /* ---------------------------------------------------------------------------------------- dense projections
  * bf16 MFMA GEMMs (f32 accumulate).  Replace the BLAS/cuDNN calls behind chainer.links.Linear, the 1x1
