@@ -775,6 +775,45 @@ def ctc_beam_search(logits, lengths, blank, beam_width, top_k, min_logp=None):
     return ids, out_len, scores
 
 
+def _lm_args(image):
+    """(uni, vlm, keys, vals, slots, max_probe, order) of a device image of asr.lm.NGramLM.to(device)"""
+    return (ptr(image["uni"]), int(image["uni"].shape[0]), ptr(image["keys"]), ptr(image["vals"]), int(image["slots"]),
+            int(image["max_probe"]), int(image["order"]))
+
+
+def ngram_score(image, ids, lengths=None, bos=-1, eos=-1):
+    """ids (N, Lmax) int32, lengths (N) int32 or None -> (tok (N, Lmax) f32: log P(token | context) of every token, 0 past the
+    length; total (N) f32: their sum plus the eos term) of asr_ngram_score over the device image of an asr.lm.NGramLM"""
+    N, Lmax = ids.shape
+    dev = ids.device
+    tok = torch.empty((N, Lmax), dtype=torch.float32, device=dev)
+    total = torch.empty((N,), dtype=torch.float32, device=dev)
+    if N == 0 or Lmax == 0:
+        raise ValueError("ngram_score needs at least one sequence and one column")
+    rc = _lib.lib().asr_ngram_score(stream(), *_lm_args(image), ptr(ids), ptr(lengths), N, Lmax, int(bos), int(eos), ptr(tok),
+                                    ptr(total))
+    check(rc, "asr_ngram_score")
+    return tok, total
+
+
+def ctc_beam_search_lm(logits, lengths, blank, beam_width, top_k, image, alpha, beta, bos=-1, eos=-1, min_logp=None):
+    """ctc_beam_search ranked by ctc + alpha * lm + beta * len (asr_ctc_beam_search_lm) -> (ids, lengths, scores, ctc_scores,
+    lm_scores); `image`: the device image of an asr.lm.NGramLM"""
+    T, B, V = logits.shape
+    dev = logits.device
+    nbytes = _lib.lib().asr_ctc_beam_lm_workspace_bytes(T, B, V, int(beam_width), int(top_k))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    ids = torch.empty((B, beam_width, T), dtype=I32, device=dev)
+    out_len = torch.empty((B, beam_width), dtype=I32, device=dev)
+    scores, ctc, lm = (torch.empty((B, beam_width), dtype=torch.float32, device=dev) for _ in range(3))
+    rc = _lib.lib().asr_ctc_beam_search_lm(stream(), ptr(logits), None if lengths is None else ptr(lengths), T, B, V, int(blank),
+                                           int(beam_width), int(top_k), float("-inf") if min_logp is None else float(min_logp),
+                                           *_lm_args(image), int(bos), int(eos), float(alpha), float(beta), ptr(ws), nbytes,
+                                           ptr(ids), ptr(out_len), ptr(scores), ptr(ctc), ptr(lm))
+    check(rc, "asr_ctc_beam_search_lm")
+    return ids, out_len, scores, ctc, lm
+
+
 def ctc_align(xs, label_unigram, label_bigram, x_len, l_len, blank):
     """(T, B, V) f32 logits + labels (B, Lmax) int32 (label_bigram None: CTC, else Gram-CTC) -> the forced alignment
     (frame_ids (B, T), tok_ids, tok_pos, tok_start, tok_end (B, Lmax) int32, tok_logp (B, Lmax) f32, n_tok (B) int32,

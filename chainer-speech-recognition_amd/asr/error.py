@@ -61,6 +61,20 @@ def beam_decode(logits, beam_width=16, top_k=16, blank=0, lengths=None, min_logp
     return _ops.ctc_beam_search(logits.contiguous(), lengths, blank, beam_width, top_k, min_logp)
 
 
+def beam_decode_lm(logits, lm, lm_weight, length_bonus, beam_width=16, top_k=16, blank=0, lengths=None, min_logp=None,
+                   use_eos=True):
+    """``beam_decode`` with an n-gram language model in the ranking while the beam is open: hypotheses are kept and sorted by
+    log p_ctc(h | x) + lm_weight * log p_lm(h) + length_bonus * |h|.  `lm` is an ``asr.lm.NGramLM`` (moved to the logits' device
+    on first use); its `bos` starts every context and, with `use_eos`, its `eos` closes every hypothesis after the last frame.
+    -> (ids, lengths, scores (the combined score), ctc_scores, lm_scores), the last three (B, beam_width) f32, so that a caller
+    can re-weight the N-best without decoding again.  Unused slots: length 0, scores and ctc_scores -inf, lm_scores 0."""
+    if lengths is not None:
+        lengths = lengths.to(logits.device, torch.int32).contiguous()
+    lm = lm.to(logits.device)
+    return _ops.ctc_beam_search_lm(logits.contiguous(), lengths, blank, beam_width, top_k, lm.image, lm_weight, length_bonus,
+                                   lm.bos_id, lm.eos_id if use_eos else -1, min_logp)
+
+
 def _error_rate(pred, pred_len, true, true_len, BLANK, vocab_token_to_id, vocab_id_to_token, print_sequences):
     """mean over the batch of Levenshtein(pred, true) / len(true) for collapsed id rows on the GPU (asr/error.py:49-68)"""
     dev = pred.device

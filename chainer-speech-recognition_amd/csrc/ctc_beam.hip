@@ -17,6 +17,7 @@
 //               frame's candidate row and repeat-stay logits are loaded one frame ahead.
 // Integer atomics only, on LDS histograms: the same inputs give bitwise the same outputs on every launch.
 #include "common.hpp"
+#include "ngram.hpp"
 #include "../../include/asr_hip.h"
 
 namespace asr {
@@ -238,10 +239,36 @@ __device__ inline int block_excl_scan(int v, int* wsum, int* total) {
     return before_me + incl - v;
 }
 
+// The language-model side of the fused search (asr_ctc_beam_search_lm): beam_kernel<true> ranks by
+// total + (alpha * lm + beta * len); beam_kernel<false> carries none of this and is the unfused search as it was.
+template <bool LM>
+struct Fuse {};                                                  // kernel arguments
+
+template <>
+struct Fuse<true> {
+    ngram::Lm lm;
+    int bos, eos;
+    float alpha, beta;
+    float* out_ctc;
+    float* out_lm;
+};
+
+template <bool LM>
+struct FuseLds {};
+
+template <>
+struct FuseLds<true> {
+    float lm[2][MAX_BEAM];                                       // lm(h) of the beam's prefixes
+    int c0[2][MAX_BEAM], c1[2][MAX_BEAM], c2[2][MAX_BEAM];       // their last tokens, newest first (-1: none), from (bos)
+    float step[MAX_EXT];                                         // log P(c | context of the parent) of the frame's extensions
+};
+
+template <bool LM>
 __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__ x, const int32_t* __restrict__ lengths, int T, int B,
                                                        int V, int W, int K, int blank, Ws ws, int32_t* __restrict__ out_ids,
-                                                       int32_t* __restrict__ out_len, float* __restrict__ out_score) {
+                                                       int32_t* __restrict__ out_len, float* __restrict__ out_score, Fuse<LM> fz) {
     __shared__ Beam bm[2];
+    __shared__ FuseLds<LM> fl;
     __shared__ float tot[MAX_ENTRIES];                 // scores of the frame's entries in canonical order
     __shared__ float btot[MAX_BEAM], spb[MAX_BEAM], spnb[MAX_BEAM];
     __shared__ int par[MAX_BEAM], cnd[MAX_BEAM];      // a stay's parent prefix (beam slot) and the candidate rank of its last token
@@ -265,6 +292,12 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
         bm[0].last[0] = -1;
         bm[0].plast[0] = -2;
         bm[0].node[0] = -1;
+        if constexpr (LM) {
+            fl.lm[0][0] = 0.f;
+            fl.c0[0][0] = fz.bos;
+            fl.c1[0][0] = -1;
+            fl.c2[0][0] = -1;
+        }
     }
     int cur = 0, m = 1;
     // a frame's candidate row, loaded one frame ahead so that its latency stays off the serial path
@@ -314,10 +347,20 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
         // B: extension scores; for every non-empty stay, its parent prefix in the beam (by hash, length and last token) and the
         // candidate rank of its last token -- the extension of that parent which equals the stay's prefix
         const int E = m + m * n;
-        for (int e = m + tid; e < E; e += THREADS) {
-            const int q = e - m, j = q / n, r = q - j * n;
-            const float base = o.last[j] == cid[r] ? o.pb[j] : btot[j];
-            tot[e] = base + clp[r];
+        ngram::Step st;
+        if constexpr (LM) {
+            // the m * n step look-ups, one or more per thread: the first one's loads are started here and are in flight during
+            // the parent / candidate matching below
+            if (m + tid < E) {
+                const int j = tid / n, r = tid - j * n;
+                st = ngram::step_issue(fz.lm, fl.c0[cur][j], fl.c1[cur][j], fl.c2[cur][j], cid[r]);
+            }
+        } else {
+            for (int e = m + tid; e < E; e += THREADS) {
+                const int q = e - m, j = q / n, r = q - j * n;
+                const float base = o.last[j] == cid[r] ? o.pb[j] : btot[j];
+                tot[e] = base + clp[r];
+            }
         }
         for (int p = tid; p < m * m; p += THREADS) {
             const int i = p / m, j = p - i * m;
@@ -326,6 +369,16 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
         for (int p = tid; p < m * n; p += THREADS) {
             const int i = p / n, r = p - i * n;
             if (o.len[i] > 0 && cid[r] == o.last[i]) cnd[i] = r;
+        }
+        if constexpr (LM) {
+            for (int e = m + tid; e < E; e += THREADS) {
+                const int q = e - m, j = q / n, r = q - j * n;
+                if (q >= THREADS) st = ngram::step_issue(fz.lm, fl.c0[cur][j], fl.c1[cur][j], fl.c2[cur][j], cid[r]);
+                const float s = ngram::step_finish(fz.lm, st);
+                fl.step[q] = s;
+                const float base = o.last[j] == cid[r] ? o.pb[j] : btot[j];
+                tot[e] = (base + clp[r]) + (fz.alpha * (fl.lm[cur][j] + s) + fz.beta * (float)(o.len[j] + 1));
+            }
         }
         __syncthreads();
         // C: stays, merged with that extension (one entry, at the stay's position)
@@ -340,7 +393,8 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
             }
             spb[i] = npb;
             spnb[i] = npnb;
-            tot[i] = lae(npb, npnb);
+            if constexpr (LM) tot[i] = lae(npb, npnb) + (fz.alpha * fl.lm[cur][i] + fz.beta * (float)o.len[i]);
+            else tot[i] = lae(npb, npnb);
         }
         __syncthreads();
         // D: radix select of the W best valid entries, 8 bits of the key per pass from the top: key >> sh > tau >> sh, and the
@@ -442,11 +496,26 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
                 nx.plast[rank] = o.plast[e];
                 nx.node[rank] = o.node[e];
                 nx.xl[rank] = xnext[e];
+                if constexpr (LM) {
+                    fl.lm[cur ^ 1][rank] = fl.lm[cur][e];
+                    fl.c0[cur ^ 1][rank] = fl.c0[cur][e];
+                    fl.c1[cur ^ 1][rank] = fl.c1[cur][e];
+                    fl.c2[cur ^ 1][rank] = fl.c2[cur][e];
+                }
             } else {
                 const int q2 = e - m, j = q2 / n, r = q2 - j * n, c = cid[r];
                 const int id = t * W + rank;
                 nx.pb[rank] = -INFINITY;
-                nx.pnb[rank] = f;
+                if constexpr (LM) {
+                    // f is the ranking score here; the CTC score is phase B's sum again, bit for bit
+                    nx.pnb[rank] = (o.last[j] == c ? o.pb[j] : btot[j]) + clp[r];
+                    fl.lm[cur ^ 1][rank] = fl.lm[cur][j] + fl.step[q2];
+                    fl.c0[cur ^ 1][rank] = c;
+                    fl.c1[cur ^ 1][rank] = fl.c0[cur][j];
+                    fl.c2[cur ^ 1][rank] = fl.c1[cur][j];
+                } else {
+                    nx.pnb[rank] = f;
+                }
                 nx.hash[rank] = hash_append(o.hash[j], c);
                 nx.phash[rank] = o.hash[j];
                 nx.len[rank] = o.len[j] + 1;
@@ -466,6 +535,52 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
     const Beam& o = bm[cur];
     // the N-best, sorted by score: ids padded with blank, then each hypothesis walks its prefix table chain back to the root
     int32_t* ids = out_ids + (size_t)b * W * T;
+    if constexpr (LM) {
+        // the end term, then the final order: score descending, ties to the earlier slot
+        float ctc = 0.f, lmv = 0.f, sc = 0.f;
+        if (tid < m) {
+            ctc = lae(o.pb[tid], o.pnb[tid]);
+            lmv = fl.lm[cur][tid];
+            if (fz.eos >= 0) lmv += ngram::step(fz.lm, fl.c0[cur][tid], fl.c1[cur][tid], fl.c2[cur][tid], fz.eos);
+            sc = ctc + (fz.alpha * lmv + fz.beta * (float)o.len[tid]);
+            sv_tot[tid] = sc;
+        }
+        __syncthreads();
+        if (tid < m) {
+            int rank = 0;
+            for (int u = 0; u < m; ++u) {
+                const float g2 = sv_tot[u];
+                rank += g2 > sc || (g2 == sc && u < tid);
+            }
+            sv_pos[rank] = tid;
+            out_score[b * W + rank] = sc;
+            fz.out_ctc[b * W + rank] = ctc;
+            fz.out_lm[b * W + rank] = lmv;
+        }
+        __syncthreads();
+        for (size_t k = tid; k < (size_t)W * T; k += THREADS) {
+            const int i = (int)(k / T), p = (int)(k - (size_t)i * T);
+            if (p >= (i < m ? o.len[sv_pos[i]] : 0)) ids[k] = blank;
+        }
+        if (tid < W) {
+            if (tid < m) {
+                const int h = sv_pos[tid], L = o.len[h];
+                out_len[b * W + tid] = L;
+                int nd = o.node[h];
+                for (int p = L - 1; p >= 0; --p) {
+                    const int2 e = nodes[nd];
+                    ids[(size_t)tid * T + p] = e.y;
+                    nd = e.x;
+                }
+            } else {
+                out_len[b * W + tid] = 0;
+                out_score[b * W + tid] = -INFINITY;
+                fz.out_ctc[b * W + tid] = -INFINITY;
+                fz.out_lm[b * W + tid] = 0.f;
+            }
+        }
+        return;
+    }
     for (size_t k = tid; k < (size_t)W * T; k += THREADS) {
         const int i = (int)(k / T), p = (int)(k - (size_t)i * T);
         if (p >= (i < m ? o.len[i] : 0)) ids[k] = blank;
@@ -515,8 +630,107 @@ extern "C" int asr_ctc_beam_search(void* stream, const float* logits, const int3
     hipLaunchKernelGGL(cand_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, lengths, T, B, V,
                        blank, K, min_logp, ws);
     ASR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(beam_kernel, dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V, beam_width, K, blank, ws,
-                       out_ids, out_len, out_score);
+    hipLaunchKernelGGL(beam_kernel<false>, dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V, beam_width, K,
+                       blank, ws, out_ids, out_len, out_score, Fuse<false>{});
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- language model entries
+namespace asr {
+namespace beam {
+
+// one workgroup per sequence; a thread scores the positions tid, tid + 256, ...; the sum is the threads' partial sums (each in
+// position order) reduced by a fixed tree, so it repeats bitwise
+__global__ __launch_bounds__(THREADS) void ngram_score_kernel(ngram::Lm lm, const int32_t* __restrict__ ids,
+                                                              const int32_t* __restrict__ lengths, int Lmax, int bos, int eos,
+                                                              float* __restrict__ out_tok, float* __restrict__ out_sum) {
+    __shared__ float part[THREADS];
+    const int nseq = blockIdx.x, tid = threadIdx.x;
+    const int32_t* row = ids + (size_t)nseq * Lmax;
+    const int len = lengths ? min(max(lengths[nseq], 0), Lmax) : Lmax;
+    auto tok = [&](int i) { return i >= 0 ? row[i] : (i == -1 ? bos : -1); };
+    float acc = 0.f;
+    for (int p = tid; p < Lmax; p += THREADS) {
+        float v = 0.f;
+        if (p < len) v = ngram::step(lm, tok(p - 1), tok(p - 2), tok(p - 3), row[p]);
+        out_tok[(size_t)nseq * Lmax + p] = v;
+        acc += v;
+    }
+    if (tid == THREADS - 1 && eos >= 0) acc += ngram::step(lm, tok(len - 1), tok(len - 2), tok(len - 3), eos);
+    part[tid] = acc;
+    __syncthreads();
+    for (int off = THREADS / 2; off > 0; off >>= 1) {
+        if (tid < off) part[tid] += part[tid + off];
+        __syncthreads();
+    }
+    if (tid == 0) out_sum[nseq] = part[0];
+}
+
+static int make_lm(const float* uni, int vlm, const int32_t* keys, const float* vals, int slots, int max_probe, int order,
+                   ngram::Lm* lm) {
+    if (!uni || vlm <= 0 || order < 1 || slots < 0) return ASR_ERR_BAD_ARG;
+    if (order > ngram::MAX_ORDER) return ASR_ERR_UNSUPPORTED;
+    if (slots > 0 && ((slots & (slots - 1)) != 0 || max_probe <= 0 || !keys || !vals)) return ASR_ERR_BAD_ARG;
+    lm->uni = (const float2*)uni;
+    lm->keys = slots > 0 ? (const int4*)keys : nullptr;
+    lm->vals = (const float2*)vals;
+    lm->mask = slots > 0 ? (unsigned)slots - 1u : 0u;
+    lm->max_probe = max_probe;
+    lm->order = order;
+    lm->vlm = vlm;
+    return ASR_OK;
+}
+
+}  // namespace beam
+}  // namespace asr
+
+extern "C" int asr_ngram_score(void* stream, const float* uni, int vlm, const int32_t* keys, const float* vals, int slots,
+                               int max_probe, int order, const int32_t* ids, const int32_t* lengths, int N, int Lmax, int bos,
+                               int eos, float* out_tok, float* out_sum) {
+    if (!ids || !out_tok || !out_sum || N <= 0 || Lmax <= 0 || bos >= vlm || eos >= vlm) return ASR_ERR_BAD_ARG;
+    ngram::Lm lm;
+    const int rc = make_lm(uni, vlm, keys, vals, slots, max_probe, order, &lm);
+    if (rc != ASR_OK) return rc;
+    hipLaunchKernelGGL(ngram_score_kernel, dim3(N), dim3(THREADS), 0, (hipStream_t)stream, lm, ids, lengths, Lmax, bos < 0 ? -1 : bos,
+                       eos < 0 ? -1 : eos, out_tok, out_sum);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+extern "C" size_t asr_ctc_beam_lm_workspace_bytes(int T, int B, int V, int beam_width, int top_k) {
+    return asr_ctc_beam_workspace_bytes(T, B, V, beam_width, top_k);
+}
+
+extern "C" int asr_ctc_beam_search_lm(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank,
+                                      int beam_width, int top_k, float min_logp, const float* uni, int vlm, const int32_t* keys,
+                                      const float* vals, int slots, int max_probe, int order, int bos, int eos, float alpha,
+                                      float beta, void* workspace, size_t workspace_bytes, int32_t* out_ids, int32_t* out_len,
+                                      float* out_score, float* out_ctc, float* out_lm) {
+    if (!logits || !workspace || !out_ids || !out_len || !out_score || !out_ctc || !out_lm || T <= 0 || B <= 0 || V <= 0 ||
+        blank < 0 || blank >= V || beam_width <= 0 || top_k <= 0 || vlm < V || bos >= vlm || eos >= vlm)
+        return ASR_ERR_BAD_ARG;
+    Fuse<true> fz;
+    const int rc = make_lm(uni, vlm, keys, vals, slots, max_probe, order, &fz.lm);
+    if (rc != ASR_OK) return rc;
+    if (beam_width > MAX_BEAM || top_k > MAX_TOPK || beam_width * top_k > MAX_EXT) return ASR_ERR_UNSUPPORTED;
+    if ((long long)T * beam_width > 0x7fffffffLL) return ASR_ERR_UNSUPPORTED;
+    const int K = min(top_k, V - 1);
+    Ws ws;
+    const size_t need = ws_layout(T, B, beam_width, K, (char*)workspace, &ws);
+    if (workspace_bytes < need) return ASR_ERR_WORKSPACE;
+    fz.bos = bos < 0 ? -1 : bos;
+    fz.eos = eos < 0 ? -1 : eos;
+    fz.alpha = alpha;
+    fz.beta = beta;
+    fz.out_ctc = out_ctc;
+    fz.out_lm = out_lm;
+    const long long rows = (long long)T * B;
+    hipLaunchKernelGGL(cand_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, lengths, T, B, V,
+                       blank, K, min_logp, ws);
+    ASR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(beam_kernel<true>, dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V, beam_width, K,
+                       blank, ws, out_ids, out_len, out_score, fz);
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }

@@ -169,6 +169,41 @@ int asr_ctc_align(void* stream, const float* xs, const int32_t* label_unigram, c
                   const int32_t* l_len, int T, int B, int V, int Lmax, int blank, int32_t* frame_ids, int32_t* tok_ids,
                   int32_t* tok_pos, int32_t* tok_start, int32_t* tok_end, float* tok_logp, int32_t* n_tok, float* score,
                   void* workspace, size_t workspace_bytes);
+/* Back-off n-gram language model over token ids (order 1-4, natural log, ARPA semantics) and the beam search fused with it
+ * (asr/lm.py builds and uploads the image).  The reference has no language model.
+ * Image:
+ *   uni  (vlm, 2) f32    (logp, backoff) of every id 0 .. vlm - 1: dense.  vlm >= V; <s> and </s>, where used, are ids >= V
+ *   keys (slots, 4) i32  the tokens of an n-gram of order 2-4, oldest first, padded with -1; an unused slot is -1 -1 -1 -1
+ *   vals (slots, 2) f32  (logp, backoff) of the n-gram in the same slot
+ *   slots is 0 (keys, vals NULL: unigrams only) or a power of two; load <= 0.5; linear probing from
+ *       h = 0x9E3779B97F4A7C15;  for the four key words k, as uint32:  h = (h ^ k) * 0xBF58476D1CE4E5B9 mod 2^64;  h ^= h >> 32
+ *       slot = (uint32)h & (slots - 1)
+ *   keys are compared in full; a probe sequence ends at a match, at an unused slot, or after max_probe slots (the builder's
+ *   longest displacement + 1), so no table content can make a kernel spin.
+ * Step: log P(w | c) with c the last min(order - 1, available) tokens, (bos) first when bos >= 0: the longest suffix of c whose
+ * extension by w is in the model gives the log-probability (the unigram when none is).  The f32 sum, in this order: 0, + the
+ * backoff of every longer suffix, longest first (0 where that suffix is not in the model), + the log-probability.  A context
+ * token outside 0 .. vlm - 1 ends the context there; a scored token outside gives NaN.
+ * asr_ngram_score: ids (N, Lmax) i32, lengths (N) or NULL (all Lmax) -> out_tok (N, Lmax) f32 the step of every token (0 past the
+ * length), out_sum (N) f32 their sum plus, when eos >= 0, log P(eos | the last tokens).  bos / eos < 0: none.  Bitwise reproducible.
+ * asr_ctc_beam_search_lm: asr_ctc_beam_search with every prefix h carrying lm(h) = lm(parent) + step(parent, c) (f32, fixed
+ * when the prefix enters the beam) and ranked, in every frame, by  total + (alpha * lm + beta * len)  in f32; ties and merging
+ * as in the unfused search (the merged entry keeps the stay's lm).  After the last frame, when eos >= 0, lm += log P(eos | h);
+ * the beam is then sorted by  out_score = out_ctc + (alpha * out_lm + beta * len),  ties to the earlier slot.
+ *   out_ids, out_len, out_score as asr_ctc_beam_search (out_score: the combined score)
+ *   out_ctc (B, beam_width) f32 logaddexp(p_blank, p_nonblank), unused -inf       out_lm (B, beam_width) f32 lm(h), unused 0
+ * With alpha = beta = 0 and eos < 0 out_ids, out_len and out_score equal asr_ctc_beam_search's bit for bit.  Model values must
+ * be finite.  Limits of asr_ctc_beam_search; order > 4 is ASR_ERR_UNSUPPORTED; order < 1, a slots that is neither 0 nor a power
+ * of two, max_probe <= 0 with slots > 0, vlm < V, bos or eos >= vlm are ASR_ERR_BAD_ARG. */
+int asr_ngram_score(void* stream, const float* uni, int vlm, const int32_t* keys, const float* vals, int slots, int max_probe,
+                    int order, const int32_t* ids, const int32_t* lengths, int N, int Lmax, int bos, int eos, float* out_tok,
+                    float* out_sum);
+size_t asr_ctc_beam_lm_workspace_bytes(int T, int B, int V, int beam_width, int top_k);
+int asr_ctc_beam_search_lm(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank,
+                           int beam_width, int top_k, float min_logp, const float* uni, int vlm, const int32_t* keys,
+                           const float* vals, int slots, int max_probe, int order, int bos, int eos, float alpha, float beta,
+                           void* workspace, size_t workspace_bytes, int32_t* out_ids, int32_t* out_len, float* out_score,
+                           float* out_ctc, float* out_lm);
 
 /* ---------------------------------------------------------------------------------------- dense projections
  * bf16 MFMA GEMMs (f32 accumulate).  Replace the BLAS/cuDNN calls behind chainer.links.Linear, the 1x1
