@@ -775,6 +775,27 @@ def ctc_beam_search(logits, lengths, blank, beam_width, top_k, min_logp=None):
     return ids, out_len, scores
 
 
+def gram_ctc_beam_search(logits, lengths, blank, beam_width, top_k, gram, min_logp=None):
+    """(T, B, V) f32 logits, gram (V, 2) int32 on the same device -> (ids (B, beam_width, 2T) int32 unigram ids padded with blank,
+    lengths (B, beam_width) int32, scores (B, beam_width) f32): the N-best strings of the Gram-CTC beam search
+    (asr_gram_ctc_beam_search), best first; unused slots have length 0 and score -inf.  The table is not checked here
+    (asr.error.gram_beam_decode does)."""
+    T, B, V = logits.shape
+    dev = logits.device
+    if gram.dtype != I32 or tuple(gram.shape) != (V, 2) or gram.device != dev or not gram.is_contiguous():
+        raise ValueError("gram must be a contiguous (V, 2) int32 tensor on the logits' device")
+    nbytes = _lib.lib().asr_gram_ctc_beam_workspace_bytes(T, B, V, int(beam_width), int(top_k))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    ids = torch.empty((B, beam_width, 2 * T), dtype=I32, device=dev)
+    out_len = torch.empty((B, beam_width), dtype=I32, device=dev)
+    scores = torch.empty((B, beam_width), dtype=torch.float32, device=dev)
+    rc = _lib.lib().asr_gram_ctc_beam_search(stream(), ptr(logits), None if lengths is None else ptr(lengths), T, B, V, int(blank),
+                                             int(beam_width), int(top_k), float("-inf") if min_logp is None else float(min_logp),
+                                             ptr(gram), ptr(ws), nbytes, ptr(ids), ptr(out_len), ptr(scores))
+    check(rc, "asr_gram_ctc_beam_search")
+    return ids, out_len, scores
+
+
 def _lm_args(image):
     """(uni, vlm, keys, vals, slots, max_probe, order) of a device image of asr.lm.NGramLM.to(device)"""
     return (ptr(image["uni"]), int(image["uni"].shape[0]), ptr(image["keys"]), ptr(image["vals"]), int(image["slots"]),

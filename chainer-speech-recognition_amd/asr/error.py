@@ -54,7 +54,7 @@ def beam_decode(logits, beam_width=16, top_k=16, blank=0, lengths=None, min_logp
     Per frame the candidates are the `top_k` non-blank ids with the largest logits, restricted to those whose log-softmax is
     at least `min_logp` (None: no threshold).  `lengths` (B) int32 restricts the decode to the valid frames, as in
     ``greedy_decode``.  The search runs over token ids: with the Gram-CTC inventory two token sequences that spell the same
-    string (a bigram token and its two unigrams) stay two hypotheses and are not merged; ``compute_sequence_error`` retokenises.
+    string (a bigram token and its two unigrams) stay two hypotheses here; ``gram_beam_decode`` is the search that merges them.
     The reference has no beam decoder; this extends its greedy call sites (run/ctc/cnn/dev.py:102, run/ctc/cnn/test.py:102)."""
     if lengths is not None:
         lengths = lengths.to(logits.device, torch.int32).contiguous()
@@ -73,6 +73,44 @@ def beam_decode_lm(logits, lm, lm_weight, length_bonus, beam_width=16, top_k=16,
     lm = lm.to(logits.device)
     return _ops.ctc_beam_search_lm(logits.contiguous(), lengths, blank, beam_width, top_k, lm.image, lm_weight, length_bonus,
                                    lm.bos_id, lm.eos_id if use_eos else -1, min_logp)
+
+
+def check_gram_table(gram, V, blank=0):
+    """Raise ValueError unless `gram` (NumPy) is a (V, 2) integer table as ``asr.vocab.gram_table`` makes it: (-1, -1) for the
+    blank, every other row (-1, -1), (u, -1) or (u1, u2) with ids in [0, V), and no two tokens with the same spelling."""
+    g = np.asarray(gram)
+    if g.ndim != 2 or g.shape != (V, 2) or g.dtype.kind not in "iu":
+        raise ValueError("gram must be an integer array of shape (V, 2) = (%d, 2)" % V)
+    if not 0 <= blank < V or tuple(g[blank]) != (-1, -1):
+        raise ValueError("the blank row of gram must be (-1, -1)")
+    if np.any(g >= V) or np.any(g < -1):
+        raise ValueError("gram spells with ids outside [0, V)")
+    if np.any((g[:, 0] < 0) & (g[:, 1] >= 0)):
+        raise ValueError("a bigram row of gram must name its first unigram")
+    used = g[g[:, 0] >= 0]
+    if len(np.unique(used, axis=0)) != len(used):
+        raise ValueError("two tokens of gram have the same spelling")
+
+
+def gram_beam_decode(logits, gram, beam_width=16, top_k=16, blank=0, lengths=None, min_logp=None):
+    """``beam_decode`` for the Gram-CTC inventory, over spelled strings: (T, B, V) f32 logits on the GPU and the table `gram`
+    (V, 2) of ``asr.vocab.gram_table`` (NumPy, checked here; or an int32 device tensor, checked too, at the cost of a copy to
+    the host) -> (ids (B, beam_width, 2T) int32 padded with blank, lengths (B, beam_width) int32, scores (B, beam_width) f32).
+    A hypothesis is a string of unigrams; its score sums every way of cutting it into unigram and bigram tokens that the beam
+    kept, so it is log p(string | x) under Gram-CTC (a lower bound on it), no string takes two slots, and the ranking and the
+    pruning see whole strings.  The ids are unigram ids already: one slot goes straight into
+    ``compute_sequence_error(ids[:, k], lengths[:, k], t_batch, blank, None, None)`` with no retokenisation on the host.
+    Candidates, `lengths` and `min_logp` as in ``beam_decode``.  ``gram_ctc_align`` on a decoded string gives its best cut."""
+    V = logits.shape[2]
+    if isinstance(gram, torch.Tensor):
+        check_gram_table(gram.cpu().numpy(), V, blank)
+        table = gram.to(logits.device, torch.int32).contiguous()
+    else:
+        check_gram_table(gram, V, blank)
+        table = torch.from_numpy(np.ascontiguousarray(gram, np.int32)).to(logits.device)
+    if lengths is not None:
+        lengths = lengths.to(logits.device, torch.int32).contiguous()
+    return _ops.gram_ctc_beam_search(logits.contiguous(), lengths, blank, beam_width, top_k, table, min_logp)
 
 
 def _error_rate(pred, pred_len, true, true_len, BLANK, vocab_token_to_id, vocab_id_to_token, print_sequences):

@@ -46,6 +46,35 @@ def load_unigram_and_bigram_ids(filename):
     return ids, {v: k for k, v in ids.items()}
 
 
+def gram_table(vocab_token_to_id, blank=0):
+    """The (V, 2) int32 NumPy table that spells every token of a Gram-CTC inventory in unigram ids, for
+    ``asr.error.gram_beam_decode``: (u, -1) for a token that ``convert_sentence_to_unigram_ids`` spells with one id, (u1, u2) for
+    one it spells with two, (-1, -1) for the blank and for ids no token has.  V = the largest id + 1.  ValueError for a token
+    that is spelled by none or more than two unigrams or cannot be tokenised, for two tokens with one id or one spelling."""
+    import numpy as np
+    if not vocab_token_to_id:
+        raise ValueError("empty inventory")
+    ids = list(vocab_token_to_id.values())
+    if min(ids) < 0 or len(set(ids)) != len(ids):
+        raise ValueError("token ids must be distinct and non-negative")
+    table = np.full((max(max(ids), blank) + 1, 2), -1, dtype=np.int32)
+    seen = {}
+    for tok, tid in vocab_token_to_id.items():
+        if tid == blank:
+            continue
+        try:
+            spelled = convert_sentence_to_unigram_ids(tok, vocab_token_to_id)
+        except AssertionError as e:
+            raise ValueError("token %r cannot be spelled with the inventory's unigrams (%s)" % (tok, e))
+        if len(spelled) not in (1, 2) or blank in spelled:
+            raise ValueError("token %r is spelled by %d unigrams; a Gram-CTC token is one or two" % (tok, len(spelled)))
+        if tuple(spelled) in seen:
+            raise ValueError("tokens %r and %r have the same spelling" % (seen[tuple(spelled)], tok))
+        seen[tuple(spelled)] = tok
+        table[tid, :len(spelled)] = spelled
+    return table
+
+
 def get_all_bigram_tokens():
     return [(a, b) for a in UNIGRAM_TOKENS for b in UNIGRAM_TOKENS]
 

@@ -15,6 +15,7 @@
 //               by a radix select on the scores (8 bits per pass); each extension that survives becomes a node (parent node,
 //               token) of the utterance's prefix table in the workspace, and a final backtrack writes the N-best ids.  The next
 //               frame's candidate row and repeat-stay logits are loaded one frame ahead.
+// gram_beam_kernel : the same frame loop for the Gram-CTC inventory, over spelled strings (the end of this file).
 // Integer atomics only, on LDS histograms: the same inputs give bitwise the same outputs on every launch.
 #include "common.hpp"
 #include "ngram.hpp"
@@ -731,6 +732,422 @@ extern "C" int asr_ctc_beam_search_lm(void* stream, const float* logits, const i
     ASR_LAUNCH_CHECK();
     hipLaunchKernelGGL(beam_kernel<true>, dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V, beam_width, K,
                        blank, ws, out_ids, out_len, out_score, fz);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+// ------------------------------------------------------------------------------ Gram-CTC: beam search over spelled strings
+// asr_gram_ctc_beam_search.  The hypotheses are strings of unigrams; a string carries the mass of the paths
+// that end in blank (pb), in the unigram token of its last character (pu) and in the bigram token of its last two (pg), so every
+// way of cutting it into unigram and bigram tokens is summed.  cand_kernel is the one above; gram_rows_kernel spells its
+// candidates; gram_beam_kernel is beam_kernel's frame loop with three masses, a three-deep identity (the hashes and last
+// characters of s, s[:-1] and s[:-2]) and one more merge: two extensions of one frame that spell the same string.
+namespace asr {
+namespace beam {
+
+constexpr unsigned short NO_MATE = 0xffff;
+
+// the (V, 2) spelling of every candidate, so that the serial pass gets it with the candidate row instead of chasing the id
+__global__ __launch_bounds__(256) void gram_rows_kernel(const int32_t* __restrict__ lengths, int T, int B, int K, Ws ws,
+                                                        const int2* __restrict__ gram, int2* __restrict__ cgr) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)T * B * K) return;
+    const long long row = i / K;
+    const int k = (int)(i - row * K), t = (int)(row / B), b = (int)(row - (long long)t * B);
+    if (lengths && t >= lengths[b]) return;
+    if (k < ws.n[row]) cgr[i] = gram[ws.cid[i]];
+}
+
+struct GBeam {
+    float pb[MAX_BEAM], pu[MAX_BEAM], pg[MAX_BEAM];
+    unsigned long long h0[MAX_BEAM], h1[MAX_BEAM], h2[MAX_BEAM];   // hash of s, of s[:-1], of s[:-2] (0 where s is too short)
+    int len[MAX_BEAM], c1[MAX_BEAM], c2[MAX_BEAM], c3[MAX_BEAM];  // s[-1], s[-2], s[-3]; -1 where s is too short
+    int utok[MAX_BEAM], gtok[MAX_BEAM];                            // the token ids behind pu and pg; -1 until a candidate named them
+    int node[MAX_BEAM];
+    float xu[MAX_BEAM], xg[MAX_BEAM];                              // the logits of utok / gtok in the frame the beam goes into
+};
+
+__device__ inline float lae3(float a, float b, float c) { return lae(lae(a, b), c); }
+
+__global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restrict__ x, const int32_t* __restrict__ lengths, int T,
+                                                            int B, int V, int W, int K, int blank, Ws ws,
+                                                            const int2* __restrict__ cgr, int32_t* __restrict__ out_ids,
+                                                            int32_t* __restrict__ out_len, float* __restrict__ out_score) {
+    __shared__ GBeam bm[2];
+    __shared__ float tot[MAX_ENTRIES];                 // scores of the frame's entries in canonical order
+    __shared__ unsigned short mt[MAX_EXT];             // an extension that took in a second one of the same string: that one's index
+    __shared__ float btot[MAX_BEAM], bpu[MAX_BEAM], bpg[MAX_BEAM];     // pb + pu + pg, pb + pu, pb + pg of the beam
+    __shared__ float spb[MAX_BEAM], spu[MAX_BEAM], spg[MAX_BEAM];      // the stays' new masses
+    __shared__ int par1[MAX_BEAM], par2[MAX_BEAM];     // the beam slots of s[:-1] and s[:-2]
+    __shared__ int cu[MAX_BEAM], cg[MAX_BEAM];         // the candidate ranks of the unigram token of s[-1] and the bigram of s[-2:]
+    __shared__ int cid[MAX_TOPK], ca[MAX_TOPK], cb[MAX_TOPK], cmate[MAX_TOPK];   // id, spelling (a, b or -1); for a bigram
+    __shared__ float clp[MAX_TOPK];                                              // candidate, the rank of the unigram (b)
+    __shared__ unsigned hist[2][256];
+    __shared__ float sv_tot[MAX_BEAM];
+    __shared__ int sv_pos[MAX_BEAM];
+    __shared__ float xnext[2 * MAX_BEAM + MAX_TOPK];   // next frame's logits of the beam's utok, of its gtok, of the candidates
+    __shared__ int wsum[4];
+    __shared__ int s_digit, s_need, s_all, s_done;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int len_b = lengths ? min(max(lengths[b], 0), T) : T;
+    const int T2 = 2 * T;
+    int2* nodes = ws.node + (size_t)b * T2 * W;
+    if (tid == 0) {
+        GBeam& r = bm[0];
+        r.pb[0] = 0.f;
+        r.pu[0] = r.pg[0] = -INFINITY;
+        r.h0[0] = ROOT_HASH;
+        r.h1[0] = r.h2[0] = 0;
+        r.len[0] = 0;
+        r.c1[0] = r.c2[0] = r.c3[0] = -1;
+        r.utok[0] = r.gtok[0] = -1;
+        r.node[0] = -1;
+    }
+    int cur = 0, m = 1;
+    int q_n = 0, q_id = 0;
+    int2 q_g = make_int2(-1, -1);
+    float q_lse = 0.f, q_lpb = 0.f, q_lp = 0.f;
+    auto load_row = [&](int t) {
+        const size_t row = (size_t)t * B + b;
+        q_n = ws.n[row];
+        q_lse = ws.lse[row];
+        q_lpb = ws.lpb[row];
+        if (tid < K) {                                 // entries past n are never used
+            q_id = ws.cid[row * K + tid];
+            q_lp = ws.clp[row * K + tid];
+            q_g = cgr[row * K + tid];
+        }
+    };
+    if (len_b > 0) load_row(0);
+    __syncthreads();
+    for (int t = 0; t < len_b; ++t) {
+        const GBeam& o = bm[cur];
+        GBeam& nx = bm[cur ^ 1];
+        const int n = min(q_n, K);
+        const float lse = q_lse, lpb = q_lpb;
+        // A: the frame's candidates and their spellings; a candidate that spells nothing (a < 0) keeps its rank and scores -inf
+        if (tid < n) {
+            cid[tid] = q_id;
+            clp[tid] = q_lp;
+            ca[tid] = q_g.x;
+            cb[tid] = q_g.x < 0 ? -1 : q_g.y;
+            cmate[tid] = -1;
+        }
+        if (tid < m) {
+            btot[tid] = lae3(o.pb[tid], o.pu[tid], o.pg[tid]);
+            bpu[tid] = lae(o.pb[tid], o.pu[tid]);
+            bpg[tid] = lae(o.pb[tid], o.pg[tid]);
+            par1[tid] = par2[tid] = -1;
+            cu[tid] = cg[tid] = -1;
+        }
+        hist[0][tid] = 0;
+        __syncthreads();
+        // the next frame's loads: its candidate row, and the logit of every token that can be behind a pu or a pg after this
+        // frame (the beam's utok and gtok, and this frame's candidates)
+        float gxu = 0.f, gxg = 0.f, gxc = 0.f;
+        if (t + 1 < len_b) {
+            load_row(t + 1);
+            const float* xr = x + ((size_t)(t + 1) * B + b) * V;
+            if (tid < m) {
+                if (o.utok[tid] >= 0) gxu = xr[o.utok[tid]];
+                if (o.gtok[tid] >= 0) gxg = xr[o.gtok[tid]];
+            }
+            if (tid < n) gxc = xr[cid[tid]];
+        }
+        // the score of the extension of beam slot j by candidate r.  A token cannot follow itself without a blank: the unigram
+        // (a) after a string that ends in a starts from pb + pg, the bigram (a, b) after one that ends in ab from pb + pu.
+        auto ext_val = [&](int j, int r) -> float {
+            const int a = ca[r], b2 = cb[r];
+            if (a < 0) return -INFINITY;
+            const float base = b2 < 0 ? (o.c1[j] == a ? bpg[j] : btot[j]) : (o.c2[j] == a && o.c1[j] == b2 ? bpu[j] : btot[j]);
+            return base + clp[r];
+        };
+        // B: extension scores; for every stay the beam slots of s[:-1] and s[:-2] and the candidates that lead from them to s
+        const int E = m + m * n;
+        for (int q = tid; q < m * n; q += THREADS) {
+            const int j = q / n, r = q - j * n;
+            tot[m + q] = ext_val(j, r);
+            mt[q] = NO_MATE;
+        }
+        for (int p = tid; p < m * m; p += THREADS) {
+            const int i = p / m, j = p - i * m;
+            if (o.len[i] > 0 && o.h0[j] == o.h1[i] && o.len[j] == o.len[i] - 1 && o.c1[j] == o.c2[i]) par1[i] = j;
+            if (o.len[i] > 1 && o.h0[j] == o.h2[i] && o.len[j] == o.len[i] - 2 && o.c1[j] == o.c3[i]) par2[i] = j;
+        }
+        for (int p = tid; p < m * n; p += THREADS) {
+            const int i = p / n, r = p - i * n;
+            if (ca[r] < 0) continue;
+            if (cb[r] < 0) { if (ca[r] == o.c1[i]) cu[i] = r; }
+            else if (ca[r] == o.c2[i] && cb[r] == o.c1[i]) cg[i] = r;
+        }
+        for (int p = tid; p < n * n; p += THREADS) {
+            const int r2 = p / n, r = p - r2 * n;
+            if (cb[r2] >= 0 && ca[r] == cb[r2] && ca[r] >= 0 && cb[r] < 0) cmate[r2] = r;
+        }
+        __syncthreads();
+        // C1: two extensions that spell one string: slot j holds s' + a, its parent slot j2 holds s', candidate r2 is the bigram
+        // (a, b) and candidate r the unigram (b).  Spellings are unique, so an entry is in at most one such pair; the earlier
+        // entry takes the sum (the unigram part first) and remembers the other one.
+        for (int p = tid; p < m * n; p += THREADS) {
+            const int j = p / n, r2 = p - j * n, j2 = par1[j];
+            if (j2 < 0 || cb[r2] < 0 || ca[r2] != o.c1[j] || cmate[r2] < 0) continue;
+            const int qu = j * n + cmate[r2], qg = j2 * n + r2;
+            const float s = lae(tot[m + qu], tot[m + qg]);
+            const int lo = min(qu, qg), hi = max(qu, qg);
+            tot[m + lo] = s;
+            tot[m + hi] = -INFINITY;
+            mt[lo] = (unsigned short)hi;
+        }
+        __syncthreads();
+        // C2: stays, merged with the unigram extension of s[:-1] and the bigram extension of s[:-2] (one entry, at the stay's position)
+        if (tid < m) {
+            const int i = tid;
+            const float npb = btot[i] + lpb;
+            float npu = o.utok[i] >= 0 ? o.pu[i] + (o.xu[i] - lse) : -INFINITY;
+            float npg = o.gtok[i] >= 0 ? o.pg[i] + (o.xg[i] - lse) : -INFINITY;
+            if (par1[i] >= 0 && cu[i] >= 0) {
+                npu = lae(npu, ext_val(par1[i], cu[i]));
+                tot[m + par1[i] * n + cu[i]] = -INFINITY;
+            }
+            if (par2[i] >= 0 && cg[i] >= 0) {
+                npg = lae(npg, ext_val(par2[i], cg[i]));
+                tot[m + par2[i] * n + cg[i]] = -INFINITY;
+            }
+            spb[i] = npb;
+            spu[i] = npu;
+            spg[i] = npg;
+            tot[i] = lae3(npb, npu, npg);
+        }
+        __syncthreads();
+        // D: radix select of the W best valid entries (as in beam_kernel)
+        const int chunk = (E + THREADS - 1) / THREADS, e0 = min(E, tid * chunk), e1 = min(E, e0 + chunk);
+        unsigned prefix = 0;
+        int need = W, all = 0, sh = 0;
+        for (int shift = 24, pass = 0; shift >= 0; shift -= 8, ++pass) {
+            unsigned* h = hist[pass & 1];
+            hist[(pass + 1) & 1][tid] = 0;
+            for (int e = e0; e < e1; ++e) {
+                const float f = tot[e];
+                if (!valid(f)) continue;
+                const unsigned key = order_key(f);
+                if (shift == 24 || (key >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&h[(key >> shift) & 255u], 1u);
+            }
+            __syncthreads();
+            if (wave == 0) {
+                int c[4], sum = 0;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { c[k] = (int)h[255 - 4 * lane - k]; sum += c[k]; }
+                int incl = sum;
+#pragma unroll
+                for (int off = 1; off < 64; off <<= 1) {
+                    const int u = __shfl_up(incl, off);
+                    if (lane >= off) incl += u;
+                }
+                const int count = __shfl(incl, 63);
+                if (shift == 24 && count <= W) {
+                    if (lane == 0) s_all = 1;
+                } else {
+                    if (lane == 0) s_all = 0;
+                    const unsigned long long hit = __ballot(incl >= need);
+                    const int L = __ffsll((long long)hit) - 1;
+                    if (lane == L) {
+                        int acc = incl - sum;
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            if (acc + c[k] >= need) {
+                                s_digit = 255 - 4 * lane - k;
+                                s_need = need - acc;
+                                s_done = acc + c[k] == need;
+                                break;
+                            }
+                            acc += c[k];
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+            if (s_all) { all = 1; break; }
+            prefix |= (unsigned)s_digit << shift;
+            need = s_need;
+            sh = shift;
+            if (s_done) break;
+        }
+        const unsigned tau = all ? 0u : prefix;
+        const int need_eq = all ? 0 : need;
+        // E: compact the kept entries in canonical order
+        int gt = 0, eq = 0;
+        for (int e = e0; e < e1; ++e) {
+            const float f = tot[e];
+            if (!valid(f)) continue;
+            const unsigned key = order_key(f) >> sh;
+            gt += key > tau >> sh;
+            eq += key == tau >> sh;
+        }
+        int packed_total;
+        const int packed = block_excl_scan((gt << 16) | eq, wsum, &packed_total);
+        int g = packed >> 16, q = packed & 0xffff;
+        for (int e = e0; e < e1; ++e) {
+            const float f = tot[e];
+            if (!valid(f)) continue;
+            const unsigned key = order_key(f) >> sh;
+            int slot = -1;
+            if (key > tau >> sh) slot = g + min(q, need_eq), ++g;
+            else if (key == tau >> sh) { if (q < need_eq) slot = g + q; ++q; }
+            if (slot >= 0) { sv_pos[slot] = e; sv_tot[slot] = f; }
+        }
+        const int M = (packed_total >> 16) + min(packed_total & 0xffff, need_eq);
+        if (tid < m) {
+            xnext[tid] = gxu;
+            xnext[m + tid] = gxg;
+        }
+        if (tid < n) xnext[2 * m + tid] = gxc;
+        __syncthreads();
+        // F: rank the survivors (score descending, canonical position on ties) into the next beam
+        if (tid < M) {
+            const float f = sv_tot[tid];
+            int rank = 0;
+            for (int u = 0; u < M; ++u) {
+                const float g2 = sv_tot[u];
+                rank += g2 > f || (g2 == f && u < tid);
+            }
+            const int e = sv_pos[tid];
+            if (e < m) {
+                // a stay whose pu (pg) was empty so far learns the token from the candidate that spells s[-1] (s[-2:])
+                const bool ku = o.utok[e] >= 0, kg = o.gtok[e] >= 0;
+                nx.pb[rank] = spb[e];
+                nx.pu[rank] = spu[e];
+                nx.pg[rank] = spg[e];
+                nx.h0[rank] = o.h0[e];
+                nx.h1[rank] = o.h1[e];
+                nx.h2[rank] = o.h2[e];
+                nx.len[rank] = o.len[e];
+                nx.c1[rank] = o.c1[e];
+                nx.c2[rank] = o.c2[e];
+                nx.c3[rank] = o.c3[e];
+                nx.node[rank] = o.node[e];
+                nx.utok[rank] = ku ? o.utok[e] : (cu[e] >= 0 ? cid[cu[e]] : -1);
+                nx.gtok[rank] = kg ? o.gtok[e] : (cg[e] >= 0 ? cid[cg[e]] : -1);
+                nx.xu[rank] = ku ? xnext[e] : (cu[e] >= 0 ? xnext[2 * m + cu[e]] : 0.f);
+                nx.xg[rank] = kg ? xnext[m + e] : (cg[e] >= 0 ? xnext[2 * m + cg[e]] : 0.f);
+            } else {
+                const int q2 = e - m, j = q2 / n, r = q2 - j * n, a = ca[r], b2 = cb[r];
+                const int mate = mt[q2];
+                // the other extension of the pair, if any: (jm, rm); f is then the sum and the parts are phase B's again
+                const int jm = mate == NO_MATE ? -1 : mate / n, rm = mate == NO_MATE ? -1 : mate - jm * n;
+                const float own = jm < 0 ? f : ext_val(j, r);
+                const float oth = jm < 0 ? -INFINITY : ext_val(jm, rm);
+                const int id = 2 * (t * W + rank);
+                nx.pb[rank] = -INFINITY;
+                if (b2 < 0) {                           // s + a
+                    nx.pu[rank] = own;
+                    nx.pg[rank] = oth;
+                    nx.utok[rank] = cid[r];
+                    nx.gtok[rank] = jm < 0 ? -1 : cid[rm];
+                    nx.xu[rank] = xnext[2 * m + r];
+                    nx.xg[rank] = jm < 0 ? 0.f : xnext[2 * m + rm];
+                    nx.h0[rank] = hash_append(o.h0[j], a);
+                    nx.h1[rank] = o.h0[j];
+                    nx.h2[rank] = o.h1[j];
+                    nx.len[rank] = o.len[j] + 1;
+                    nx.c1[rank] = a;
+                    nx.c2[rank] = o.c1[j];
+                    nx.c3[rank] = o.c2[j];
+                    nx.node[rank] = id;
+                    nodes[id] = make_int2(o.node[j], a);
+                } else {                                // s + a + b: two nodes
+                    const unsigned long long ha = hash_append(o.h0[j], a);
+                    nx.pg[rank] = own;
+                    nx.pu[rank] = oth;
+                    nx.gtok[rank] = cid[r];
+                    nx.utok[rank] = jm < 0 ? -1 : cid[rm];
+                    nx.xg[rank] = xnext[2 * m + r];
+                    nx.xu[rank] = jm < 0 ? 0.f : xnext[2 * m + rm];
+                    nx.h0[rank] = hash_append(ha, b2);
+                    nx.h1[rank] = ha;
+                    nx.h2[rank] = o.h0[j];
+                    nx.len[rank] = o.len[j] + 2;
+                    nx.c1[rank] = b2;
+                    nx.c2[rank] = a;
+                    nx.c3[rank] = o.c1[j];
+                    nx.node[rank] = id + 1;
+                    nodes[id] = make_int2(o.node[j], a);
+                    nodes[id + 1] = make_int2(id, b2);
+                }
+            }
+        }
+        __syncthreads();
+        cur ^= 1;
+        m = M;
+    }
+    __threadfence();
+    __syncthreads();
+    const GBeam& o = bm[cur];
+    // the N-best strings, sorted by score: ids padded with blank, then each walks its prefix table chain back to the root
+    int32_t* ids = out_ids + (size_t)b * W * T2;
+    for (size_t k = tid; k < (size_t)W * T2; k += THREADS) {
+        const int i = (int)(k / T2), p = (int)(k - (size_t)i * T2);
+        if (p >= (i < m ? o.len[i] : 0)) ids[k] = blank;
+    }
+    if (tid < W) {
+        if (tid < m) {
+            const int L = o.len[tid];
+            out_len[b * W + tid] = L;
+            out_score[b * W + tid] = lae3(o.pb[tid], o.pu[tid], o.pg[tid]);
+            int nd = o.node[tid];
+            for (int p = L - 1; p >= 0; --p) {
+                const int2 e = nodes[nd];
+                ids[(size_t)tid * T2 + p] = e.y;
+                nd = e.x;
+            }
+        } else {
+            out_len[b * W + tid] = 0;
+            out_score[b * W + tid] = -INFINITY;
+        }
+    }
+}
+
+// the workspace of asr_ctc_beam_search with a prefix table of 2 * T * W nodes per utterance (a bigram extension adds two), then
+// the candidates' spellings (T * B, K) int2
+static size_t gram_ws_layout(int T, int B, int W, int K, char* base, Ws* ws, int2** cgr) {
+    size_t off = ws_layout(T, B, 2 * W, K, base, ws);
+    if (cgr) *cgr = (int2*)(base + off);
+    off += align256((size_t)T * B * K * 8);
+    return off;
+}
+
+}  // namespace beam
+}  // namespace asr
+
+extern "C" size_t asr_gram_ctc_beam_workspace_bytes(int T, int B, int V, int beam_width, int top_k) {
+    if (T <= 0 || B <= 0 || V <= 0 || beam_width <= 0 || top_k <= 0) return 0;
+    return gram_ws_layout(T, B, beam_width, min(top_k, V - 1), nullptr, nullptr, nullptr);
+}
+
+extern "C" int asr_gram_ctc_beam_search(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank,
+                                        int beam_width, int top_k, float min_logp, const int32_t* gram, void* workspace,
+                                        size_t workspace_bytes, int32_t* out_ids, int32_t* out_len, float* out_score) {
+    if (!logits || !workspace || !out_ids || !out_len || !out_score || T <= 0 || B <= 0 || V <= 0 || blank < 0 || blank >= V ||
+        beam_width <= 0 || top_k <= 0)
+        return ASR_ERR_BAD_ARG;
+    if (!gram) return ASR_ERR_UNSUPPORTED;
+    if (beam_width > MAX_BEAM || top_k > MAX_TOPK || beam_width * top_k > MAX_EXT) return ASR_ERR_UNSUPPORTED;
+    if (2LL * T * beam_width > 0x7fffffffLL) return ASR_ERR_UNSUPPORTED;         // prefix table node ids are int32
+    const int K = min(top_k, V - 1);
+    Ws ws;
+    int2* cgr;
+    const size_t need = gram_ws_layout(T, B, beam_width, K, (char*)workspace, &ws, &cgr);
+    if (workspace_bytes < need) return ASR_ERR_WORKSPACE;
+    const long long rows = (long long)T * B;
+    hipLaunchKernelGGL(cand_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, lengths, T, B, V,
+                       blank, K, min_logp, ws);
+    ASR_LAUNCH_CHECK();
+    if (K > 0) {
+        hipLaunchKernelGGL(gram_rows_kernel, dim3((unsigned)((rows * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, lengths, T,
+                           B, K, ws, (const int2*)gram, cgr);
+        ASR_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(gram_beam_kernel, dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V, beam_width, K,
+                       blank, ws, (const int2*)cgr, out_ids, out_len, out_score);
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }

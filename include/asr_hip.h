@@ -204,6 +204,24 @@ int asr_ctc_beam_search_lm(void* stream, const float* logits, const int32_t* len
                            const float* vals, int slots, int max_probe, int order, int bos, int eos, float alpha, float beta,
                            void* workspace, size_t workspace_bytes, int32_t* out_ids, int32_t* out_len, float* out_score,
                            float* out_ctc, float* out_lm);
+/* Gram-CTC beam search over spelled strings: asr_ctc_beam_search for an inventory of a blank, unigrams and
+ * bigrams spelled by two unigrams (the loss asr_ctc_forward computes with label_bigram).  The hypotheses are strings of unigrams; a
+ * string carries the mass of its paths that end in blank, in the unigram token of its last character and in the bigram token of its
+ * last two, so every way of cutting it into tokens that the beam kept is summed: out_score is log p(string | x) as far as the beam
+ * kept its paths (a lower bound on minus the Gram-CTC loss of the string with every bigram of the table offered).
+ *   gram      (V, 2) i32 on the device: (u, -1) a unigram token, (u1, u2) a bigram token, (-1, -1) the blank and any id that is
+ *             never emitted (such a candidate is dropped after the top_k / min_logp choice).  No two tokens share a row.
+ *   out_ids   (B, beam_width, 2T) unigram ids of the final beam sorted by score descending, padded with blank (a bigram token adds
+ *             two characters in one frame)      out_len, out_score (B, beam_width) as asr_ctc_beam_search
+ *   workspace asr_gram_ctc_beam_workspace_bytes(T, B, V, beam_width, top_k) bytes
+ * Candidates, limits, tie rules and error codes of asr_ctc_beam_search; gram == NULL is ASR_ERR_UNSUPPORTED.  Every element of
+ * every output is written on every call; an utterance without frames gives the empty string with score 0 in slot 0.  With a table
+ * without bigram rows whose unigram ids are the token ids, the first T columns, out_len and out_score are asr_ctc_beam_search's.
+ * Bitwise reproducible. */
+size_t asr_gram_ctc_beam_workspace_bytes(int T, int B, int V, int beam_width, int top_k);
+int asr_gram_ctc_beam_search(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank,
+                             int beam_width, int top_k, float min_logp, const int32_t* gram, void* workspace, size_t workspace_bytes,
+                             int32_t* out_ids, int32_t* out_len, float* out_score);
 
 /* ---------------------------------------------------------------------------------------- dense projections
  * bf16 MFMA GEMMs (f32 accumulate).  Replace the BLAS/cuDNN calls behind chainer.links.Linear, the 1x1

@@ -1,0 +1,157 @@
+"""Gram-CTC beam search over spelled strings, host side: the float64 restatement (tests/gram_beam_reference.py) against an
+exhaustive enumeration of every path and against the token-level restatement, asr.vocab.gram_table, and the C entries (no GPU)."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+
+import ctc_beam_reference as ref
+import gram_beam_reference as gref
+from conftest import PKG, ROOT
+
+
+def test_restatement_equals_the_enumeration_when_the_beam_holds_everything():
+    """top_k = V - 1 and a beam of 128 >= the number of strings: the restatement returns exactly the strings with p > 0, each
+    with the sum over all of its paths, i.e. over every cut into unigram and bigram tokens (1e-9; the counts are the issue's)"""
+    for (T, rows, seed), count in gref.EXHAUSTIVE:
+        gram = gref.table(rows)
+        V = len(gram)
+        x = gref.exhaustive_logits(T, V, seed)
+        exact = gref.enumerate_strings(x, gram)
+        assert len(exact) == count, (T, rows, seed, len(exact))
+        got = gref.beam_search(x, gram, 128, V - 1)
+        strings = [s for s, _ in got]
+        assert len(got) == count and len(set(strings)) == count and set(strings) == set(exact)
+        scores = np.array([sc for _, sc in got])
+        assert np.all(np.isfinite(scores)) and np.all(np.diff(scores) <= 0)
+        worst = max(abs(sc - exact[s]) for s, sc in got)
+        assert worst <= 1e-9, (T, rows, seed, worst)
+
+
+def test_restatement_prunes_to_a_lower_bound_without_duplicates():
+    for (T, rows, seed), _ in gref.EXHAUSTIVE[:5]:
+        gram = gref.table(rows)
+        x = gref.exhaustive_logits(T, len(gram), seed)
+        exact = gref.enumerate_strings(x, gram)
+        got = gref.beam_search(x, gram, 3, 2)
+        assert 1 <= len(got) <= 3 and len({s for s, _ in got}) == len(got)
+        for s, sc in got:
+            assert sc <= exact[s] + 1e-12
+
+
+def test_a_bigram_free_table_gives_the_token_level_search():
+    """unigram rows only (token id = unigram id): the same labellings in the same order, scores to 1e-12"""
+    for T, V, W, K, blank, seed in ((12, 6, 8, 5, 0, 1), (20, 9, 4, 3, 2, 2), (7, 4, 128, 3, 0, 3), (30, 40, 16, 16, 0, 4)):
+        x = (np.random.RandomState(seed).randn(T, V) * 2).astype(np.float32)
+        gram = np.full((V, 2), -1, np.int32)
+        gram[:, 0] = np.arange(V)
+        gram[blank] = -1
+        want = ref.beam_search(x, W, K, blank)
+        got = gref.beam_search(x, gram, W, K, blank)
+        assert [s for s, _ in got] == [lab for lab, _ in want]
+        assert max(abs(a - b) for (_, a), (_, b) in zip(got, want)) <= 1e-12
+
+
+def test_rows_that_spell_nothing_are_dropped_after_the_candidate_choice():
+    """a (-1, -1) row among the top_k uses up its rank: the search equals the one on logits where that id can never be among
+    the candidates only if top_k still reaches the others"""
+    rows = ((1,), (2,), (), (1, 2))
+    gram = gref.table(rows)
+    x = gref.exhaustive_logits(4, 5, 9)
+    x[:, 3] += 3.0                                         # the row that spells nothing is often the best candidate
+    got = dict(gref.beam_search(x, gram, 128, 4))
+    exact = gref.enumerate_strings(x, gram)
+    assert set(got) == set(exact) and max(abs(got[s] - exact[s]) for s in got) <= 1e-9
+    narrow = gref.beam_search(x, gram, 128, 1)
+    assert all(sc <= exact[s] + 1e-12 for s, sc in narrow) and len(narrow) < len(exact)
+
+
+def test_gram_table_on_the_reference_inventory():
+    from asr import vocab
+    ids, _ = vocab.get_unigram_ids()
+    nuni = len(ids)
+    a, b = vocab.UNIGRAM_TOKENS[0], vocab.UNIGRAM_TOKENS[1]
+    small = [t for t in vocab.UNIGRAM_TOKENS if len(t) == 2 and t[1] in vocab.SUTEGANA and t not in vocab.UNIGRAM_COLLAPSE]
+    assert len(small) >= 2, "the inventory has unigrams that carry a small kana"
+    bigrams = [a + b, b + a, a + a, small[0] + small[1], a + small[0]]
+    for tok in bigrams:
+        ids[tok] = len(ids)
+    g = vocab.gram_table(ids)
+    assert g.shape == (nuni + len(bigrams), 2) and g.dtype == np.int32
+    assert tuple(g[0]) == (-1, -1)
+    for tok, tid in ids.items():
+        if tid == 0:
+            continue
+        want = vocab.convert_sentence_to_unigram_ids(tok, ids)
+        assert [int(u) for u in g[tid] if u >= 0] == want
+        assert len(want) == (1 if tid < nuni else 2)
+    assert tuple(g[ids[small[0] + small[1]]]) == (ids[small[0]], ids[small[1]])
+    from asr import error
+    error.check_gram_table(g, len(g), 0)                   # what gram_table makes passes gram_beam_decode's validation
+
+
+def test_gram_table_value_errors():
+    from asr import vocab
+    ids, _ = vocab.get_unigram_ids()
+    a, b, c = vocab.UNIGRAM_TOKENS[:3]
+    with pytest.raises(ValueError):
+        vocab.gram_table(dict(ids, **{a + b + c: len(ids)}))               # three unigrams
+    with pytest.raises(ValueError):
+        vocab.gram_table(dict(ids, **{"": len(ids)}))                      # none
+    with pytest.raises(ValueError):
+        vocab.gram_table(dict(ids, **{a + "☃": len(ids)}))            # a character the inventory does not have
+    with pytest.raises(ValueError):
+        vocab.gram_table(dict(ids, **{vocab.SUTEGANA[0] + a: len(ids)}))   # starts with a small kana
+    with pytest.raises(ValueError):
+        vocab.gram_table(dict(ids, **{a + b: ids[a]}))                     # two tokens, one id
+    with pytest.raises(ValueError):
+        vocab.gram_table({})
+    collapsing = [k for k, v in vocab.UNIGRAM_COLLAPSE.items() if v in ids and k not in ids]
+    if collapsing:                                                          # a token the tokeniser rewrites to another's spelling
+        with pytest.raises(ValueError):
+            vocab.gram_table(dict(ids, **{collapsing[0]: len(ids)}))
+    assert vocab.gram_table(ids, blank=0).shape == (len(ids), 2)
+
+
+def test_check_gram_table_value_errors():
+    from asr import error
+    good = gref.table(((1,), (2,), (1, 2)))
+    error.check_gram_table(good, 4, 0)
+    bad = []
+    bad.append(good[:3])                                   # wrong shape
+    bad.append(good.astype(np.float32))                    # not integers
+    g = good.copy(); g[0] = (1, -1); bad.append(g)         # the blank row spells something
+    g = good.copy(); g[3] = (1, 4); bad.append(g)          # id outside [0, V)
+    g = good.copy(); g[3] = (-1, 2); bad.append(g)         # a bigram without its first unigram
+    g = good.copy(); g[2] = (1, -1); bad.append(g)         # two tokens, one spelling
+    g = good.copy(); g[3] = (-2, -1); bad.append(g)
+    for g in bad:
+        with pytest.raises(ValueError):
+            error.check_gram_table(g, 4, 0)
+    with pytest.raises(ValueError):
+        error.check_gram_table(good, 4, 1)                 # blank row must be (-1, -1)
+
+
+def test_entries_in_the_header_the_binding_and_both_libraries():
+    from asr import _lib
+    header = open(os.path.join(ROOT, "include", "asr_hip.h")).read()
+    for name in ("asr_gram_ctc_beam_workspace_bytes", "asr_gram_ctc_beam_search"):
+        assert re.search(r"\b%s\s*\(" % name, header), name
+        assert name in _lib.SIGNATURES
+    assert len(_lib.SIGNATURES["asr_gram_ctc_beam_search"][1]) == 16
+    for so in ("libasr_hip.so", "libasr_hip_f16.so"):
+        path = os.path.join(PKG, so)
+        assert os.path.isfile(path), "run `make -C chainer-speech-recognition_amd`"
+        lib = ctypes.CDLL(path)
+        assert hasattr(lib, "asr_gram_ctc_beam_search")
+        q, p = lib.asr_gram_ctc_beam_workspace_bytes, lib.asr_ctc_beam_workspace_bytes
+        for f in (q, p):
+            f.restype = ctypes.c_size_t
+            f.argtypes = [ctypes.c_int] * 5
+        T, B, V, W, K = 1000, 16, 3000, 16, 16
+        # the token-level workspace with a prefix table of 2 * T * W nodes, plus the candidates' spellings (T * B, K) int2
+        assert q(T, B, V, W, K) >= p(T, B, V, W, K) + T * B * (W * 8 + K * 8)
+        assert q(5, 1, 3, 4, 16) == q(5, 1, 3, 4, 2)       # top_k above V - 1 acts as V - 1
+        assert q(0, B, V, W, K) == 0 and q(T, B, V, 0, K) == 0
