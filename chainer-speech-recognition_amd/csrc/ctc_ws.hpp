@@ -40,5 +40,41 @@ static Workspace carve(void* base, int T, int B, int Lmax, int gram) {
     return w;
 }
 
+// Workspace of the N-best scoring (csrc/ctc_nbest.hip): the loss's tables for B * N lattices, "utterance" u = b * N + n, and ONE
+// log-sum-exp per logit row (the N hypotheses of an utterance share its rows).
+struct NbestWorkspace {
+    int* path_label;   // (B*N, Sp)
+    int* path_mask;    // (B*N, Sp)
+    int* path_len;     // (B*N)
+    int* x_len;        // (B*N)    frames of utterance b for a used slot, 0 for an unused one (the sweep then reports -inf)
+    float* lse;        // (T, B)
+    float* lp;         // (B*N, T, Sp)
+    double* alpha;     // (B*N, T, Sp)
+    double* beta;      // (B*N, T, Sp)
+    double* total;     // (B*N)    log p(h_n | x_b), -inf: unused or infeasible
+    float* loss;       // (B*N)    what the sweep writes beside total (unused here)
+    size_t bytes;
+};
+
+static NbestWorkspace carve_nbest(void* base, int T, int B, int N, int Lmax) {
+    NbestWorkspace w;
+    const size_t Sp = (size_t)path_pad(Lmax, 0), U = (size_t)B * N;
+    char* p = (char*)base;
+    size_t off = 0;
+    auto take = [&](size_t n) { char* r = p ? p + off : nullptr; off += align_up(n, 256); return r; };
+    w.path_label = (int*)take(sizeof(int) * U * Sp);
+    w.path_mask = (int*)take(sizeof(int) * U * Sp);
+    w.path_len = (int*)take(sizeof(int) * U);
+    w.x_len = (int*)take(sizeof(int) * U);
+    w.lse = (float*)take(sizeof(float) * (size_t)T * B);
+    w.lp = (float*)take(sizeof(float) * U * T * Sp);
+    w.alpha = (double*)take(sizeof(double) * U * T * Sp);
+    w.beta = (double*)take(sizeof(double) * U * T * Sp);
+    w.total = (double*)take(sizeof(double) * U);
+    w.loss = (float*)take(sizeof(float) * U);
+    w.bytes = off;
+    return w;
+}
+
 }  // namespace ctc
 }  // namespace asr

@@ -65,6 +65,28 @@ int asr_ctc_backward(void* stream, const float* xs, const int32_t* x_len, int T,
 int asr_ctc_loss_grad(void* stream, const float* xs, const int32_t* label_unigram, const int32_t* label_bigram,
                       const int32_t* x_len, const int32_t* l_len, int T, int B, int V, int Lmax, int blank, float scale,
                       float* loss_per_utt, float* loss_mean, float* grad, void* workspace, size_t workspace_bytes);
+/* N-best CTC scoring: the exact log p(h_n | x_b) of N hypotheses per utterance (all paths, not the lower bound a beam search
+ * reports) and the gradient of sum_{b,n} gy[b,n] log p(h_n | x_b) -- what expected-error (MWER) training and exact rescoring of
+ * an N-best list need.  The reference has no counterpart.  The lattices and the alpha / beta recursion are the loss's (the same
+ * code, float64 accumulation); the logit rows are read once per (t, b), whatever N is.
+ *   xs, x_len, blank  as above                     hyp (B, N, Lmax) int32 labels, hyp_len (B, N) int32
+ *   hyp_len[b][n] < 0   an unused slot: logp -inf.  0: the empty hypothesis, logp = sum_t log softmax(xs[t][b])[blank].
+ *                       Values above Lmax act as Lmax.  A hypothesis without a path (x_len[b] < length + adjacent repeats, or a
+ *                       label outside [0, V)) has logp -inf.
+ *   logp (B, N) f32     log p(h_n | x_b);  for N = 1 it is minus asr_ctc_forward's loss_per_utt
+ *   backward: grad (T, B, V) f32 = sum_n gy[b][n] (occupancy_n - softmax), zero rows for t >= x_len[b]; every row is written
+ *   once.  gy (B, N) f32; the gy of a slot whose logp is -inf is ignored (it may hold NaN).  The sign is the opposite of
+ *   asr_ctc_backward's: this is the gradient of +log p.
+ *   workspace  asr_ctc_nbest_workspace_bytes(T, B, V, N, Lmax) bytes (0: the dimensions are refused); it carries alpha / beta of
+ *   the B * N lattices from forward to backward.
+ * N > 128 (the beam's limit) or a path too long for LDS (where asr_ctc_forward_lse refuses it): ASR_ERR_UNSUPPORTED; a null
+ * pointer, a dimension or N <= 0, blank outside [0, V): ASR_ERR_BAD_ARG; a short workspace: ASR_ERR_WORKSPACE -- all before any
+ * launch. */
+size_t asr_ctc_nbest_workspace_bytes(int T, int B, int V, int N, int Lmax);
+int asr_ctc_nbest_forward(void* stream, const float* xs, const int32_t* hyp, const int32_t* hyp_len, const int32_t* x_len, int T,
+                          int B, int V, int N, int Lmax, int blank, float* logp, void* workspace, size_t workspace_bytes);
+int asr_ctc_nbest_backward(void* stream, const float* xs, const int32_t* x_len, int T, int B, int V, int N, int Lmax,
+                           const float* gy, float* grad, const void* workspace, size_t workspace_bytes);
 
 /* ---------------------------------------------------------------------------------------- log-mel features
  * Replace fft.get_specgram / compute_logmel / compute_deltas (asr/fft.py:52-66, 6-19, 90-99), the per-utterance loop of
