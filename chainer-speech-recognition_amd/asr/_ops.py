@@ -835,6 +835,28 @@ def ctc_beam_search_lm(logits, lengths, blank, beam_width, top_k, image, alpha, 
     return ids, out_len, scores, ctc, lm
 
 
+def gram_ctc_beam_search_lm(logits, lengths, blank, beam_width, top_k, gram, image, alpha, beta, bos=-1, eos=-1, min_logp=None):
+    """gram_ctc_beam_search ranked by ctc + alpha * lm + beta * len over the spelled characters (asr_gram_ctc_beam_search_lm) ->
+    (ids (B, beam_width, 2T), lengths, scores, ctc_scores, lm_scores); `image`: the device image of an asr.lm.NGramLM over the
+    unigram ids of `gram`.  The table is not checked here (asr.error.gram_beam_decode_lm does)."""
+    T, B, V = logits.shape
+    dev = logits.device
+    if gram.dtype != I32 or tuple(gram.shape) != (V, 2) or gram.device != dev or not gram.is_contiguous():
+        raise ValueError("gram must be a contiguous (V, 2) int32 tensor on the logits' device")
+    nbytes = _lib.lib().asr_gram_ctc_beam_lm_workspace_bytes(T, B, V, int(beam_width), int(top_k))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    ids = torch.empty((B, beam_width, 2 * T), dtype=I32, device=dev)
+    out_len = torch.empty((B, beam_width), dtype=I32, device=dev)
+    scores, ctc, lm = (torch.empty((B, beam_width), dtype=torch.float32, device=dev) for _ in range(3))
+    rc = _lib.lib().asr_gram_ctc_beam_search_lm(stream(), ptr(logits), None if lengths is None else ptr(lengths), T, B, V,
+                                                int(blank), int(beam_width), int(top_k),
+                                                float("-inf") if min_logp is None else float(min_logp), ptr(gram),
+                                                *_lm_args(image), int(bos), int(eos), float(alpha), float(beta), ptr(ws), nbytes,
+                                                ptr(ids), ptr(out_len), ptr(scores), ptr(ctc), ptr(lm))
+    check(rc, "asr_gram_ctc_beam_search_lm")
+    return ids, out_len, scores, ctc, lm
+
+
 def ctc_align(xs, label_unigram, label_bigram, x_len, l_len, blank):
     """(T, B, V) f32 logits + labels (B, Lmax) int32 (label_bigram None: CTC, else Gram-CTC) -> the forced alignment
     (frame_ids (B, T), tok_ids, tok_pos, tok_start, tok_end (B, Lmax) int32, tok_logp (B, Lmax) f32, n_tok (B) int32,

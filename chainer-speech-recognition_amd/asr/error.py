@@ -92,6 +92,16 @@ def check_gram_table(gram, V, blank=0):
         raise ValueError("two tokens of gram have the same spelling")
 
 
+def _gram_table_on(logits, gram, blank):
+    """`gram` (NumPy or a device tensor), checked, as a contiguous (V, 2) int32 tensor on the logits' device"""
+    V = logits.shape[2]
+    if isinstance(gram, torch.Tensor):
+        check_gram_table(gram.cpu().numpy(), V, blank)
+        return gram.to(logits.device, torch.int32).contiguous()
+    check_gram_table(gram, V, blank)
+    return torch.from_numpy(np.ascontiguousarray(gram, np.int32)).to(logits.device)
+
+
 def gram_beam_decode(logits, gram, beam_width=16, top_k=16, blank=0, lengths=None, min_logp=None):
     """``beam_decode`` for the Gram-CTC inventory, over spelled strings: (T, B, V) f32 logits on the GPU and the table `gram`
     (V, 2) of ``asr.vocab.gram_table`` (NumPy, checked here; or an int32 device tensor, checked too, at the cost of a copy to
@@ -100,17 +110,33 @@ def gram_beam_decode(logits, gram, beam_width=16, top_k=16, blank=0, lengths=Non
     kept, so it is log p(string | x) under Gram-CTC (a lower bound on it), no string takes two slots, and the ranking and the
     pruning see whole strings.  The ids are unigram ids already: one slot goes straight into
     ``compute_sequence_error(ids[:, k], lengths[:, k], t_batch, blank, None, None)`` with no retokenisation on the host.
-    Candidates, `lengths` and `min_logp` as in ``beam_decode``.  ``gram_ctc_align`` on a decoded string gives its best cut."""
-    V = logits.shape[2]
-    if isinstance(gram, torch.Tensor):
-        check_gram_table(gram.cpu().numpy(), V, blank)
-        table = gram.to(logits.device, torch.int32).contiguous()
-    else:
-        check_gram_table(gram, V, blank)
-        table = torch.from_numpy(np.ascontiguousarray(gram, np.int32)).to(logits.device)
+    Candidates, `lengths` and `min_logp` as in ``beam_decode``.  ``gram_ctc_align`` on a decoded string gives its best cut.
+    ``gram_beam_decode_lm`` is this search with a character n-gram language model in the ranking."""
+    table = _gram_table_on(logits, gram, blank)
     if lengths is not None:
         lengths = lengths.to(logits.device, torch.int32).contiguous()
     return _ops.gram_ctc_beam_search(logits.contiguous(), lengths, blank, beam_width, top_k, table, min_logp)
+
+
+def gram_beam_decode_lm(logits, gram, lm, lm_weight, length_bonus, beam_width=16, top_k=16, blank=0, lengths=None, min_logp=None,
+                        use_eos=True):
+    """``gram_beam_decode`` with an n-gram language model over the spelled characters in the ranking while the beam is open:
+    strings are kept and sorted by log p_gram_ctc(s | x) + lm_weight * log p_lm(s) + length_bonus * |s|, |s| in characters.
+    `gram` is validated as in ``gram_beam_decode``.  `lm` is an ``asr.lm.NGramLM`` over the unigram ids that the table spells
+    with (moved to the logits' device on first use): make it with ``NGramLM.from_arpa(text, unigram_token_to_id, V=V)``, V the
+    size of the logits' inventory, so that <s> / </s> become the ids V and V + 1 above every token id; a model with
+    ``lm.vlm < V`` raises ValueError.  Its `bos` starts every context and, with `use_eos`, its `eos` closes every string after
+    the last frame.  A bigram token adds the steps of its two characters, so log p_lm(s) does not depend on how s was cut.
+    -> (ids (B, beam_width, 2T), lengths, scores (the combined score), ctc_scores, lm_scores), the last three (B, beam_width)
+    f32.  Unused slots: length 0, scores and ctc_scores -inf, lm_scores 0."""
+    table = _gram_table_on(logits, gram, blank)
+    if lm.vlm < logits.shape[2]:
+        raise ValueError("the language model covers %d ids, fewer than the %d of the logits" % (lm.vlm, logits.shape[2]))
+    if lengths is not None:
+        lengths = lengths.to(logits.device, torch.int32).contiguous()
+    lm = lm.to(logits.device)
+    return _ops.gram_ctc_beam_search_lm(logits.contiguous(), lengths, blank, beam_width, top_k, table, lm.image, lm_weight,
+                                        length_bonus, lm.bos_id, lm.eos_id if use_eos else -1, min_logp)
 
 
 def _error_rate(pred, pred_len, true, true_len, BLANK, vocab_token_to_id, vocab_id_to_token, print_sequences):

@@ -769,11 +769,34 @@ struct GBeam {
 
 __device__ inline float lae3(float a, float b, float c) { return lae(lae(a, b), c); }
 
+// The language-model side of asr_gram_ctc_beam_search_lm: gram_beam_kernel<true> ranks by
+// total + (alpha * lm + beta * len) with lm over the string's characters, the arguments being section 17's Fuse<true>;
+// gram_beam_kernel<false> carries none of this and is the unfused string search as it was.
+template <bool LM>
+struct GFuseLds {};
+
+template <>
+struct GFuseLds<true> {
+    float lm[2][MAX_BEAM];                                       // lm(s) of the beam's strings
+    float elm[MAX_EXT];                                          // lm(s + a) or lm(s + a + b) of the frame's extensions
+};
+
+// the k-th newest character of the string in beam slot j as a model context: (bos) stands right before the string, nothing
+// before that; the identity fields c1 .. c3 keep their -1
+__device__ inline int lm_ctx(const GBeam& g, int j, int k, int bos) {
+    const int L = g.len[j];
+    if (k >= L) return k == L ? bos : -1;
+    return k == 0 ? g.c1[j] : (k == 1 ? g.c2[j] : g.c3[j]);
+}
+
+template <bool LM>
 __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restrict__ x, const int32_t* __restrict__ lengths, int T,
                                                             int B, int V, int W, int K, int blank, Ws ws,
                                                             const int2* __restrict__ cgr, int32_t* __restrict__ out_ids,
-                                                            int32_t* __restrict__ out_len, float* __restrict__ out_score) {
+                                                            int32_t* __restrict__ out_len, float* __restrict__ out_score,
+                                                            Fuse<LM> fz) {
     __shared__ GBeam bm[2];
+    __shared__ GFuseLds<LM> fl;
     __shared__ float tot[MAX_ENTRIES];                 // scores of the frame's entries in canonical order
     __shared__ unsigned short mt[MAX_EXT];             // an extension that took in a second one of the same string: that one's index
     __shared__ float btot[MAX_BEAM], bpu[MAX_BEAM], bpg[MAX_BEAM];     // pb + pu + pg, pb + pu, pb + pg of the beam
@@ -802,6 +825,7 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
         r.c1[0] = r.c2[0] = r.c3[0] = -1;
         r.utok[0] = r.gtok[0] = -1;
         r.node[0] = -1;
+        if constexpr (LM) fl.lm[0][0] = 0.f;
     }
     int cur = 0, m = 1;
     int q_n = 0, q_id = 0;
@@ -864,10 +888,27 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
         };
         // B: extension scores; for every stay the beam slots of s[:-1] and s[:-2] and the candidates that lead from them to s
         const int E = m + m * n;
-        for (int q = tid; q < m * n; q += THREADS) {
-            const int j = q / n, r = q - j * n;
-            tot[m + q] = ext_val(j, r);
-            mt[q] = NO_MATE;
+        ngram::Step st1, st2;
+        // the look-ups of extension q: one step for a unigram candidate, two for a bigram candidate (both contexts are known from
+        // the parent's last characters and a, so the second does not wait for the first), none for one that spells nothing
+        auto issue = [&](int q) {
+            if constexpr (LM) {
+                const int j = q / n, r = q - j * n, a = ca[r], b2 = cb[r];
+                if (a < 0) return;
+                const int x0 = lm_ctx(o, j, 0, fz.bos), x1 = lm_ctx(o, j, 1, fz.bos), x2 = lm_ctx(o, j, 2, fz.bos);
+                st1 = ngram::step_issue(fz.lm, x0, x1, x2, a);
+                if (b2 >= 0) st2 = ngram::step_issue(fz.lm, a, x0, x1, b2);
+            }
+        };
+        if constexpr (LM) {
+            // thread k takes extension k (and k + 256, ...): the first one's loads are in flight during the matching loops below
+            if (tid < m * n) issue(tid);
+        } else {
+            for (int q = tid; q < m * n; q += THREADS) {
+                const int j = q / n, r = q - j * n;
+                tot[m + q] = ext_val(j, r);
+                mt[q] = NO_MATE;
+            }
         }
         for (int p = tid; p < m * m; p += THREADS) {
             const int i = p / m, j = p - i * m;
@@ -884,6 +925,18 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
             const int r2 = p / n, r = p - r2 * n;
             if (cb[r2] >= 0 && ca[r] == cb[r2] && ca[r] >= 0 && cb[r] < 0) cmate[r2] = r;
         }
+        if constexpr (LM) {
+            for (int q = tid; q < m * n; q += THREADS) {
+                const int j = q / n, r = q - j * n, a = ca[r], b2 = cb[r];
+                mt[q] = NO_MATE;
+                if (a < 0) { tot[m + q] = -INFINITY; continue; }
+                if (q >= THREADS) issue(q);
+                float nl = fl.lm[cur][j] + ngram::step_finish(fz.lm, st1);       // the steps in string order: (lm + a) + b
+                if (b2 >= 0) nl += ngram::step_finish(fz.lm, st2);
+                fl.elm[q] = nl;
+                tot[m + q] = ext_val(j, r) + (fz.alpha * nl + fz.beta * (float)(o.len[j] + (b2 < 0 ? 1 : 2)));
+            }
+        }
         __syncthreads();
         // C1: two extensions that spell one string: slot j holds s' + a, its parent slot j2 holds s', candidate r2 is the bigram
         // (a, b) and candidate r the unigram (b).  Spellings are unique, so an entry is in at most one such pair; the earlier
@@ -892,8 +945,15 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
             const int j = p / n, r2 = p - j * n, j2 = par1[j];
             if (j2 < 0 || cb[r2] < 0 || ca[r2] != o.c1[j] || cmate[r2] < 0) continue;
             const int qu = j * n + cmate[r2], qg = j2 * n + r2;
-            const float s = lae(tot[m + qu], tot[m + qg]);
             const int lo = min(qu, qg), hi = max(qu, qg);
+            float s;
+            if constexpr (LM) {
+                // the acoustic parts again (phase B's sums, bit for bit), merged, then the string's bonus: both routes carry
+                // the same lm and length
+                s = lae(ext_val(j, cmate[r2]), ext_val(j2, r2)) + (fz.alpha * fl.elm[lo] + fz.beta * (float)(o.len[j] + 1));
+            } else {
+                s = lae(tot[m + qu], tot[m + qg]);
+            }
             tot[m + lo] = s;
             tot[m + hi] = -INFINITY;
             mt[lo] = (unsigned short)hi;
@@ -916,7 +976,8 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
             spb[i] = npb;
             spu[i] = npu;
             spg[i] = npg;
-            tot[i] = lae3(npb, npu, npg);
+            if constexpr (LM) tot[i] = lae3(npb, npu, npg) + (fz.alpha * fl.lm[cur][i] + fz.beta * (float)o.len[i]);
+            else tot[i] = lae3(npb, npu, npg);
         }
         __syncthreads();
         // D: radix select of the W best valid entries (as in beam_kernel)
@@ -1029,15 +1090,18 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
                 nx.gtok[rank] = kg ? o.gtok[e] : (cg[e] >= 0 ? cid[cg[e]] : -1);
                 nx.xu[rank] = ku ? xnext[e] : (cu[e] >= 0 ? xnext[2 * m + cu[e]] : 0.f);
                 nx.xg[rank] = kg ? xnext[m + e] : (cg[e] >= 0 ? xnext[2 * m + cg[e]] : 0.f);
+                if constexpr (LM) fl.lm[cur ^ 1][rank] = fl.lm[cur][e];
             } else {
                 const int q2 = e - m, j = q2 / n, r = q2 - j * n, a = ca[r], b2 = cb[r];
                 const int mate = mt[q2];
                 // the other extension of the pair, if any: (jm, rm); f is then the sum and the parts are phase B's again
                 const int jm = mate == NO_MATE ? -1 : mate / n, rm = mate == NO_MATE ? -1 : mate - jm * n;
-                const float own = jm < 0 ? f : ext_val(j, r);
+                // (with the language model f is the ranking score, and the own part is phase B's sum again as well)
+                const float own = !LM && jm < 0 ? f : ext_val(j, r);
                 const float oth = jm < 0 ? -INFINITY : ext_val(jm, rm);
                 const int id = 2 * (t * W + rank);
                 nx.pb[rank] = -INFINITY;
+                if constexpr (LM) fl.lm[cur ^ 1][rank] = fl.elm[q2];
                 if (b2 < 0) {                           // s + a
                     nx.pu[rank] = own;
                     nx.pg[rank] = oth;
@@ -1084,6 +1148,53 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
     const GBeam& o = bm[cur];
     // the N-best strings, sorted by score: ids padded with blank, then each walks its prefix table chain back to the root
     int32_t* ids = out_ids + (size_t)b * W * T2;
+    if constexpr (LM) {
+        // the end term, then the final order: score descending, ties to the earlier slot (as beam_kernel<true>)
+        float ctc = 0.f, lmv = 0.f, sc = 0.f;
+        if (tid < m) {
+            ctc = lae3(o.pb[tid], o.pu[tid], o.pg[tid]);
+            lmv = fl.lm[cur][tid];
+            if (fz.eos >= 0)
+                lmv += ngram::step(fz.lm, lm_ctx(o, tid, 0, fz.bos), lm_ctx(o, tid, 1, fz.bos), lm_ctx(o, tid, 2, fz.bos), fz.eos);
+            sc = ctc + (fz.alpha * lmv + fz.beta * (float)o.len[tid]);
+            sv_tot[tid] = sc;
+        }
+        __syncthreads();
+        if (tid < m) {
+            int rank = 0;
+            for (int u = 0; u < m; ++u) {
+                const float g2 = sv_tot[u];
+                rank += g2 > sc || (g2 == sc && u < tid);
+            }
+            sv_pos[rank] = tid;
+            out_score[b * W + rank] = sc;
+            fz.out_ctc[b * W + rank] = ctc;
+            fz.out_lm[b * W + rank] = lmv;
+        }
+        __syncthreads();
+        for (size_t k = tid; k < (size_t)W * T2; k += THREADS) {
+            const int i = (int)(k / T2), p = (int)(k - (size_t)i * T2);
+            if (p >= (i < m ? o.len[sv_pos[i]] : 0)) ids[k] = blank;
+        }
+        if (tid < W) {
+            if (tid < m) {
+                const int h = sv_pos[tid], L = o.len[h];
+                out_len[b * W + tid] = L;
+                int nd = o.node[h];
+                for (int p = L - 1; p >= 0; --p) {
+                    const int2 e = nodes[nd];
+                    ids[(size_t)tid * T2 + p] = e.y;
+                    nd = e.x;
+                }
+            } else {
+                out_len[b * W + tid] = 0;
+                out_score[b * W + tid] = -INFINITY;
+                fz.out_ctc[b * W + tid] = -INFINITY;
+                fz.out_lm[b * W + tid] = 0.f;
+            }
+        }
+        return;
+    }
     for (size_t k = tid; k < (size_t)W * T2; k += THREADS) {
         const int i = (int)(k / T2), p = (int)(k - (size_t)i * T2);
         if (p >= (i < m ? o.len[i] : 0)) ids[k] = blank;
@@ -1146,8 +1257,52 @@ extern "C" int asr_gram_ctc_beam_search(void* stream, const float* logits, const
                            B, K, ws, (const int2*)gram, cgr);
         ASR_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(gram_beam_kernel, dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V, beam_width, K,
-                       blank, ws, (const int2*)cgr, out_ids, out_len, out_score);
+    hipLaunchKernelGGL(gram_beam_kernel<false>, dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V, beam_width,
+                       K, blank, ws, (const int2*)cgr, out_ids, out_len, out_score, Fuse<false>{});
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+extern "C" size_t asr_gram_ctc_beam_lm_workspace_bytes(int T, int B, int V, int beam_width, int top_k) {
+    return asr_gram_ctc_beam_workspace_bytes(T, B, V, beam_width, top_k);
+}
+
+extern "C" int asr_gram_ctc_beam_search_lm(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank,
+                                           int beam_width, int top_k, float min_logp, const int32_t* gram, const float* uni, int vlm,
+                                           const int32_t* keys, const float* vals, int slots, int max_probe, int order, int bos,
+                                           int eos, float alpha, float beta, void* workspace, size_t workspace_bytes,
+                                           int32_t* out_ids, int32_t* out_len, float* out_score, float* out_ctc, float* out_lm) {
+    if (!logits || !workspace || !out_ids || !out_len || !out_score || !out_ctc || !out_lm || T <= 0 || B <= 0 || V <= 0 ||
+        blank < 0 || blank >= V || beam_width <= 0 || top_k <= 0 || vlm < V || bos >= vlm || eos >= vlm)
+        return ASR_ERR_BAD_ARG;
+    Fuse<true> fz;
+    const int rc = make_lm(uni, vlm, keys, vals, slots, max_probe, order, &fz.lm);
+    if (rc != ASR_OK) return rc;
+    if (!gram) return ASR_ERR_UNSUPPORTED;
+    if (beam_width > MAX_BEAM || top_k > MAX_TOPK || beam_width * top_k > MAX_EXT) return ASR_ERR_UNSUPPORTED;
+    if (2LL * T * beam_width > 0x7fffffffLL) return ASR_ERR_UNSUPPORTED;
+    const int K = min(top_k, V - 1);
+    Ws ws;
+    int2* cgr;
+    const size_t need = gram_ws_layout(T, B, beam_width, K, (char*)workspace, &ws, &cgr);
+    if (workspace_bytes < need) return ASR_ERR_WORKSPACE;
+    fz.bos = bos < 0 ? -1 : bos;
+    fz.eos = eos < 0 ? -1 : eos;
+    fz.alpha = alpha;
+    fz.beta = beta;
+    fz.out_ctc = out_ctc;
+    fz.out_lm = out_lm;
+    const long long rows = (long long)T * B;
+    hipLaunchKernelGGL(cand_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, lengths, T, B, V,
+                       blank, K, min_logp, ws);
+    ASR_LAUNCH_CHECK();
+    if (K > 0) {
+        hipLaunchKernelGGL(gram_rows_kernel, dim3((unsigned)((rows * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, lengths, T,
+                           B, K, ws, (const int2*)gram, cgr);
+        ASR_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(gram_beam_kernel<true>, dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V, beam_width,
+                       K, blank, ws, (const int2*)cgr, out_ids, out_len, out_score, fz);
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }

@@ -244,6 +244,38 @@ size_t asr_gram_ctc_beam_workspace_bytes(int T, int B, int V, int beam_width, in
 int asr_gram_ctc_beam_search(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank,
                              int beam_width, int top_k, float min_logp, const int32_t* gram, void* workspace, size_t workspace_bytes,
                              int32_t* out_ids, int32_t* out_len, float* out_score);
+/* Gram-CTC beam search fused with a character n-gram language model: asr_gram_ctc_beam_search with every
+ * string S carrying lm(S) and ranked, in every frame, by  total(S) + (alpha * lm(S) + beta * len(S))  in f32, the expression of
+ * asr_ctc_beam_search_lm with len counted in characters.
+ * Model: the image above (order 1-4) over the unigram ids that `gram` spells with (the table's values, not the token ids).
+ *   vlm >= V as above; <s> / </s> are ids >= V; the unigram entries of bigram-token ids are never queried.
+ * lm(S) is a function of the string alone: lm(()) = 0 and lm(S + c) = lm(S) + step(context(S), c) in f32, context(S) the last
+ *   order - 1 characters of S, (bos) before them when bos >= 0.  A bigram extension (a, b) adds its two steps in string order,
+ *   (lm(S) + step(ctx(S), a)) + step(ctx(S + a), b), so every route to a string (and a string pruned and created again) gives the
+ *   same f32 value: the left-to-right sum of its steps.
+ * total(S) is the frame's merged Gram-CTC total exactly as asr_gram_ctc_beam_search forms it (the stay plus the absorbed unigram
+ *   and bigram extensions; two extensions of one string merged); the bonus is added after the merges, every contributor of a
+ *   string having the same lm and len.  Merging, canonical positions, tie rules, dropped (-1, -1) candidates and the prefix table
+ *   are those of the unfused entry; the three masses stay pure Gram-CTC quantities.
+ * After the last frame, when eos >= 0, lm += step(ctx(S), eos); out_score = out_ctc + (alpha * out_lm + beta * len), and the beam
+ *   is ranked again by counting, ties to the earlier slot.
+ *   out_ids (B, beam_width, 2T), out_len, out_score (the combined score) as asr_gram_ctc_beam_search
+ *   out_ctc (B, beam_width) f32 logaddexp of the three masses, unused -inf       out_lm (B, beam_width) f32 lm(S), unused 0
+ *   workspace asr_gram_ctc_beam_lm_workspace_bytes(T, B, V, beam_width, top_k) bytes
+ * Every element of every output is written on every call; an utterance without frames gives the empty string in slot 0 with
+ * out_ctc 0, out_lm the eos step (0 without eos) and out_score combined accordingly.  With alpha = beta = 0 and eos < 0, out_ids,
+ * out_len and out_score equal asr_gram_ctc_beam_search's bit for bit and out_ctc == out_score.  With a table without bigram rows
+ * whose unigram ids are the token ids, the first T columns, out_len and the three scores are asr_ctc_beam_search_lm's.
+ * Limits and errors are the union of the two parents', all checked before the first launch: beam_width > 128, top_k > 64,
+ * beam_width * top_k > 4096, 2 * T * beam_width beyond int32, gram == NULL, order > 4: ASR_ERR_UNSUPPORTED; the model-argument
+ * checks of asr_ctc_beam_search_lm (order < 1, slots, max_probe, vlm < V, bos or eos >= vlm): ASR_ERR_BAD_ARG; a short workspace:
+ * ASR_ERR_WORKSPACE.  Frames past lengths[b] are never read.  Bitwise reproducible. */
+size_t asr_gram_ctc_beam_lm_workspace_bytes(int T, int B, int V, int beam_width, int top_k);
+int asr_gram_ctc_beam_search_lm(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank,
+                                int beam_width, int top_k, float min_logp, const int32_t* gram, const float* uni, int vlm,
+                                const int32_t* keys, const float* vals, int slots, int max_probe, int order, int bos, int eos,
+                                float alpha, float beta, void* workspace, size_t workspace_bytes, int32_t* out_ids,
+                                int32_t* out_len, float* out_score, float* out_ctc, float* out_lm);
 
 /* ---------------------------------------------------------------------------------------- dense projections
  * bf16 MFMA GEMMs (f32 accumulate).  Replace the BLAS/cuDNN calls behind chainer.links.Linear, the 1x1
