@@ -52,6 +52,9 @@ SIGNATURES = {
     "asr_ctc_nbest_workspace_bytes": (c_size_t, [c_int] * 5),
     "asr_ctc_nbest_forward": (c_int, [c_void_p] * 5 + [c_int] * 6 + [c_void_p, c_void_p, c_size_t]),
     "asr_ctc_nbest_backward": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 3 + [c_size_t]),
+    "asr_gram_ctc_nbest_workspace_bytes": (c_size_t, [c_int] * 5),
+    "asr_gram_ctc_nbest_forward": (c_int, [c_void_p] * 6 + [c_int] * 6 + [c_void_p, c_void_p, c_size_t]),
+    "asr_gram_ctc_nbest_backward": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 3 + [c_size_t]),
     "asr_specgram": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_longlong] + [c_int] * 4 + [c_float, c_void_p, c_void_p, c_int,
                                c_void_p, c_void_p, c_int, c_void_p]),
     "asr_mel_bands_bytes": (c_size_t, []),

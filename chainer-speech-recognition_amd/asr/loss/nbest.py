@@ -7,9 +7,14 @@ The reference has neither; its only sequence criterion is the CTC / Gram-CTC los
 
 The N hypotheses of an utterance share its logit rows: the kernels (csrc/ctc_nbest.hip) read the (T, B, V) logits once and
 write one (T, B, V) gradient, whatever N is; only the lattices are per hypothesis.
+
+``gram_ctc_nbest_logp`` and ``gram_mwer_loss`` are the same for a Gram-CTC model: the hypotheses are strings of characters (what
+``asr.error.gram_beam_decode`` returns) and log p(string | x) sums every way of cutting the string into the unigram and bigram
+tokens of the inventory.
 """
 import collections
 
+import numpy as np
 import torch
 
 from .. import _lib
@@ -18,7 +23,8 @@ from .ctc import _check_common
 
 class _NbestFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, xs, hyps, hyp_lengths, input_length, blank):
+    def forward(ctx, xs, hyps, hyp_lengths, input_length, blank, gram):
+        """gram None: CTC over labels; a checked (V, 2) int32 device table: Gram-CTC over characters"""
         lib = _lib.lib()
         if xs.dtype != torch.float32:
             raise TypeError("xs must be float32")
@@ -37,29 +43,37 @@ class _NbestFunction(torch.autograd.Function):
             hyps, Lmax = torch.full((B, N, 1), int(blank), dtype=torch.int32, device=xs.device), 1
         hyps, hyp_lengths = hyps.contiguous(), hyp_lengths.contiguous()
         input_length = None if input_length is None else input_length.contiguous()
-        nbytes = lib.asr_ctc_nbest_workspace_bytes(T, B, V, N, Lmax)
+        query = lib.asr_ctc_nbest_workspace_bytes if gram is None else lib.asr_gram_ctc_nbest_workspace_bytes
+        nbytes = query(T, B, V, N, Lmax)
         ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=xs.device)
         logp = torch.empty((B, N), dtype=torch.float32, device=xs.device)
-        rc = lib.asr_ctc_nbest_forward(_lib.stream(), _lib.ptr(xs), _lib.ptr(hyps), _lib.ptr(hyp_lengths), _lib.ptr(input_length),
-                                       T, B, V, N, Lmax, int(blank), _lib.ptr(logp), _lib.ptr(ws), nbytes)
-        _lib.check(rc, "asr_ctc_nbest_forward")
+        if gram is None:
+            rc = lib.asr_ctc_nbest_forward(_lib.stream(), _lib.ptr(xs), _lib.ptr(hyps), _lib.ptr(hyp_lengths), _lib.ptr(input_length),
+                                           T, B, V, N, Lmax, int(blank), _lib.ptr(logp), _lib.ptr(ws), nbytes)
+            _lib.check(rc, "asr_ctc_nbest_forward")
+        else:
+            rc = lib.asr_gram_ctc_nbest_forward(_lib.stream(), _lib.ptr(xs), _lib.ptr(hyps), _lib.ptr(hyp_lengths),
+                                                _lib.ptr(input_length), _lib.ptr(gram), T, B, V, N, Lmax, int(blank), _lib.ptr(logp),
+                                                _lib.ptr(ws), nbytes)
+            _lib.check(rc, "asr_gram_ctc_nbest_forward")
         ctx.save_for_backward(xs, input_length, ws)
-        ctx.dims = (T, B, V, N, Lmax, nbytes)
+        ctx.dims = (T, B, V, N, Lmax, nbytes, gram is not None)
         return logp
 
     @staticmethod
     def backward(ctx, gy):
         lib = _lib.lib()
         xs, input_length, ws = ctx.saved_tensors
-        T, B, V, N, Lmax, nbytes = ctx.dims
+        T, B, V, N, Lmax, nbytes, is_gram = ctx.dims
         gy = gy.contiguous().to(torch.float32)
         # an ordinary (T, B, V) gradient: logits that come straight out of a LayerNormalization receive it through autograd beside
         # the recipe a CTC loss on the same logits may have left there (functions._CtcBox), and the normalisation adds the two
         grad = torch.empty_like(xs)
-        rc = lib.asr_ctc_nbest_backward(_lib.stream(), _lib.ptr(xs), _lib.ptr(input_length), T, B, V, N, Lmax, _lib.ptr(gy),
-                                        _lib.ptr(grad), _lib.ptr(ws), nbytes)
-        _lib.check(rc, "asr_ctc_nbest_backward")
-        return grad, None, None, None, None
+        name = "asr_gram_ctc_nbest_backward" if is_gram else "asr_ctc_nbest_backward"
+        rc = getattr(lib, name)(_lib.stream(), _lib.ptr(xs), _lib.ptr(input_length), T, B, V, N, Lmax, _lib.ptr(gy),
+                                _lib.ptr(grad), _lib.ptr(ws), nbytes)
+        _lib.check(rc, name)
+        return grad, None, None, None, None, None
 
 
 def ctc_nbest_logp(x, hyps, hyp_lengths, blank_symbol, input_length=None):
@@ -70,7 +84,37 @@ def ctc_nbest_logp(x, hyps, hyp_lengths, blank_symbol, input_length=None):
     gradient, whatever gradient arrives for them.  For N = 1 this is minus the CTC loss with ``reduce="no"``.
     ``asr.error.beam_decode``'s ids and lengths (unused slots set to -1) can be passed as they come."""
     xs = _check_common(x, blank_symbol, "no")
-    return _NbestFunction.apply(xs, hyps, hyp_lengths, input_length, blank_symbol)
+    return _NbestFunction.apply(xs, hyps, hyp_lengths, input_length, blank_symbol, None)
+
+
+def _checked_gram_table(xs, gram, blank_symbol):
+    """`gram` through ``asr.error._gram_table_on`` (validated on the host, -> (V, 2) int32 on the logits' device) and one more
+    check: every character a bigram row spells with has a unigram row.  A string over such a table never meets a character it
+    cannot emit alone, which is the only lattice the kernels (and the float64 oracle) model."""
+    from ..error import _gram_table_on
+    table = _gram_table_on(xs, gram, blank_symbol)
+    g = gram.cpu().numpy() if isinstance(gram, torch.Tensor) else np.asarray(gram)
+    unigrams = g[(g[:, 0] >= 0) & (g[:, 1] < 0), 0]
+    spelled = g[g[:, 1] >= 0].reshape(-1)
+    missing = np.setdiff1d(spelled, unigrams)
+    if len(missing):
+        raise ValueError("gram has bigram rows that spell with %s, which no unigram row spells" % missing[:8].tolist())
+    return table
+
+
+def gram_ctc_nbest_logp(x, hyps, hyp_lengths, gram, blank_symbol, input_length=None):
+    """Exact Gram-CTC log-probabilities of N strings per utterance: ``x`` and the hypotheses as ``ctc_nbest_logp`` takes them, with
+    ``hyps`` (B, N, L) int32 in characters (unigram ids), and ``gram`` the (V, 2) table of ``asr.vocab.gram_table`` (NumPy or a
+    device tensor, validated on the host as ``asr.error.gram_beam_decode`` validates it; every character a bigram row spells with
+    must have a unigram row, else ValueError) -> (B, N) float32 log p(string_n | x_b), differentiable with respect to ``x``.
+    log p sums every way of cutting the string into unigram and bigram tokens of the table: it is minus ``gram_ctc`` with
+    label_unigram[i] = the token of (s[i]) and label_bigram[i] = the token of (s[i-1], s[i]) or -1, reduce="no".
+    A negative length marks an unused slot (log p = -inf); length 0 is the empty string; a string that does not fit into the
+    utterance's frames, or holds a character without a unigram token, has log p = -inf.  Slots with -inf send no gradient.
+    ``asr.error.gram_beam_decode``'s / ``gram_beam_decode_lm``'s ids and lengths (unused slots set to -1) can be passed as they
+    come.  There is no CPU path."""
+    xs = _check_common(x, blank_symbol, "no")
+    return _NbestFunction.apply(xs, hyps, hyp_lengths, input_length, blank_symbol, _checked_gram_table(xs, gram, blank_symbol))
 
 
 MWER = collections.namedtuple("MWER", "loss logp errors posteriors hyps hyp_lengths")
@@ -134,9 +178,31 @@ def mwer_loss(x, t, blank_symbol, input_length=None, label_length=None, beam_wid
         mwer = mwer_loss(ys, t, 0, x_len, t_len, beam_width=8)
         loss = mwer.loss + lam * connectionist_temporal_classification(ys, t, 0, x_len, t_len)
     """
-    from .. import _ops
     from ..error import beam_decode
     xs = _check_common(x, blank_symbol, reduce)
+    if hyps is None:
+        ids, lens, scores = beam_decode(xs.detach(), beam_width, top_k, blank_symbol, input_length, min_logp)
+        hyps, hyp_lengths = _cut_list(ids, lens, scores, max_length)
+    return _mwer_over_list(xs, t, blank_symbol, input_length, label_length, hyps, hyp_lengths, add_reference, normalize, reduce,
+                           ctc_nbest_logp)
+
+
+def _cut_list(ids, lens, scores, max_length):
+    """a beam's N-best as a hypothesis set: unused slots (score -inf) get length -1, the ids are cut to the longest hypothesis
+    (ONE host synchronisation) or, with ``max_length``, there (none; longer hypotheses become unused)"""
+    lens = torch.where(scores > float("-inf"), lens, torch.full_like(lens, -1))
+    if max_length is None:
+        width = max(1, int(lens.max().item()))          # the one host synchronisation
+    else:
+        width = max(1, min(int(max_length), ids.shape[2]))
+        lens = torch.where(lens > width, torch.full_like(lens, -1), lens)
+    return ids[:, :, :width].contiguous(), lens
+
+
+def _mwer_over_list(xs, t, blank_symbol, input_length, label_length, hyps, hyp_lengths, add_reference, normalize, reduce, logp_fn):
+    """what ``mwer_loss`` and ``gram_mwer_loss`` do once the hypothesis set is there; ``logp_fn(xs, hyps, hyp_lengths, blank_symbol,
+    input_length)`` scores it"""
+    from .. import _ops
     T, B, V = xs.shape
     dev = xs.device
     if t.dtype != torch.int32 or (label_length is not None and label_length.dtype != torch.int32):
@@ -145,24 +211,14 @@ def mwer_loss(x, t, blank_symbol, input_length=None, label_length=None, beam_wid
         raise ValueError("t must be (B, L)")
     if label_length is None:
         label_length = torch.full((B,), t.shape[1], dtype=torch.int32, device=dev)
-    if hyps is None:
-        ids, lens, scores = beam_decode(xs.detach(), beam_width, top_k, blank_symbol, input_length, min_logp)
-        lens = torch.where(scores > float("-inf"), lens, torch.full_like(lens, -1))
-        if max_length is None:
-            width = max(1, int(lens.max().item()))          # the one host synchronisation
-        else:
-            width = max(1, min(int(max_length), T))
-            lens = torch.where(lens > width, torch.full_like(lens, -1), lens)
-        hyps, hyp_lengths = ids[:, :, :width].contiguous(), lens
-    else:
-        if hyp_lengths is None:
-            raise ValueError("hyp_lengths must be given with hyps")
-        if hyps.dtype != torch.int32 or hyp_lengths.dtype != torch.int32:
-            raise TypeError("labels and lengths must be int32")
-        if hyps.dim() != 3 or hyps.shape[0] != B or tuple(hyp_lengths.shape) != tuple(hyps.shape[:2]):
-            raise ValueError("hyps must be (B, N, L) and hyp_lengths (B, N)")
-        if hyps.shape[2] == 0:
-            hyps = torch.full((B, hyps.shape[1], 1), int(blank_symbol), dtype=torch.int32, device=dev)
+    if hyp_lengths is None:
+        raise ValueError("hyp_lengths must be given with hyps")
+    if hyps.dtype != torch.int32 or hyp_lengths.dtype != torch.int32:
+        raise TypeError("labels and lengths must be int32")
+    if hyps.dim() != 3 or hyps.shape[0] != B or tuple(hyp_lengths.shape) != tuple(hyps.shape[:2]):
+        raise ValueError("hyps must be (B, N, L) and hyp_lengths (B, N)")
+    if hyps.shape[2] == 0:
+        hyps = torch.full((B, hyps.shape[1], 1), int(blank_symbol), dtype=torch.int32, device=dev)
     N = hyps.shape[1]
 
     def distances(h, hl):           # (B, n, L), (B, n) -> (B, n) f32 Levenshtein distance to the transcript, on the device
@@ -186,9 +242,42 @@ def mwer_loss(x, t, blank_symbol, input_length=None, label_length=None, beam_wid
         errors = torch.cat([errors, torch.zeros((B, 1), dtype=torch.float32, device=dev)], dim=1)
     if normalize:
         errors = errors / label_length.clamp_min(1).to(torch.float32)[:, None]
-    logp = ctc_nbest_logp(xs, hyps, hyp_lengths, blank_symbol, input_length)
+    logp = logp_fn(xs, hyps, hyp_lengths, blank_symbol, input_length)
     # float64 for the (B, N) part: the coefficients are products of posteriors that differ by many orders of magnitude
     loss_b, post = mwer_parts(logp.double(), errors.double())
     loss_b = loss_b.to(torch.float32)
     loss = loss_b.mean() if reduce == "mean" else loss_b
     return MWER(loss, logp.detach(), errors, post.to(torch.float32), hyps, hyp_lengths)
+
+
+def gram_mwer_loss(x, t, gram, blank_symbol, input_length=None, label_length=None, beam_width=8, top_k=8, min_logp=None, hyps=None,
+                   hyp_lengths=None, add_reference=False, normalize=False, max_length=None, reduce="mean", lm=None, lm_weight=0.0,
+                   length_bonus=0.0, use_eos=True):
+    """``mwer_loss`` for a Gram-CTC model: the transcript ``t`` (B, L) int32 and the hypotheses are strings of characters (unigram
+    ids), e_n is the Levenshtein distance over characters, and log p(string_n | x_b) is exact under Gram-CTC
+    (``gram_ctc_nbest_logp`` with the table ``gram``).  Everything else -- P_n, loss_b, ``add_reference``, ``normalize``,
+    ``reduce``, the returned ``MWER`` -- is ``mwer_loss``'s.
+
+    Without ``hyps`` the list is ``asr.error.gram_beam_decode(x.detach(), gram, beam_width, top_k, blank_symbol, input_length,
+    min_logp)``, or with ``lm`` (an ``asr.lm.NGramLM`` over the characters) ``gram_beam_decode_lm(..., lm, lm_weight, length_bonus,
+    ..., use_eos)``: the language model chooses the list, the criterion stays the acoustic model's expected error.  Its 2T-wide
+    ids are cut as ``mwer_loss`` cuts them (one host synchronisation, none with ``max_length``).  The usual training criterion:
+
+        mwer = gram_mwer_loss(ys, t, gram, 0, x_len, t_len, beam_width=8)
+        loss = mwer.loss + lam * gram_ctc(ys, label_unigram, label_bigram, 0, x_len, t_len)
+    """
+    from ..error import gram_beam_decode, gram_beam_decode_lm
+    xs = _check_common(x, blank_symbol, reduce)
+    table = _checked_gram_table(xs, gram, blank_symbol)
+    if hyps is None:
+        if lm is None:
+            ids, lens, scores = gram_beam_decode(xs.detach(), gram, beam_width, top_k, blank_symbol, input_length, min_logp)
+        else:
+            ids, lens, scores = gram_beam_decode_lm(xs.detach(), gram, lm, lm_weight, length_bonus, beam_width, top_k, blank_symbol,
+                                                    input_length, min_logp, use_eos)[:3]
+        hyps, hyp_lengths = _cut_list(ids, lens, scores, max_length)
+
+    def logp_fn(xs, hyps, hyp_lengths, blank_symbol, input_length):
+        return _NbestFunction.apply(xs, hyps, hyp_lengths, input_length, blank_symbol, table)
+    return _mwer_over_list(xs, t, blank_symbol, input_length, label_length, hyps, hyp_lengths, add_reference, normalize, reduce,
+                           logp_fn)

@@ -53,12 +53,27 @@ struct NbestWorkspace {
     double* beta;      // (B*N, T, Sp)
     double* total;     // (B*N)    log p(h_n | x_b), -inf: unused or infeasible
     float* loss;       // (B*N)    what the sweep writes beside total (unused here)
+    // Gram-CTC only (gram = 1): the lattice's two label rows, looked up from the hypothesis' characters, and the spelling index
+    int* lab_uni;      // (B*N, Lmax)  token that spells (s[i]), -1: none
+    int* lab_big;      // (B*N, Lmax)  token that spells (s[i-1], s[i]), -1: none; [0] = -1
+    int* eff_len;      // (B*N)    hyp_len clamped to Lmax; -1: unused, or a character without a unigram token
+    unsigned long long* idx_key;   // (capacity)  spelling, first character in the high word; all ones (the blank's (-1, -1)): empty
+    int* idx_val;      // (capacity)  the smallest token id with that spelling
+    size_t idx_cap;    // the power of two >= 2 V
     size_t bytes;
 };
 
-static NbestWorkspace carve_nbest(void* base, int T, int B, int N, int Lmax) {
+// capacity of the spelling index: the power of two >= 2 V (load <= 0.5: every linear probe ends at an empty slot)
+static inline size_t gram_index_capacity(int V) {
+    size_t cap = 2;
+    while (cap < 2 * (size_t)V) cap <<= 1;
+    return cap;
+}
+
+// gram = 0: the CTC lattices (V is not used); gram = 1: the Gram-CTC lattices, their label rows and the spelling index of V tokens
+static NbestWorkspace carve_nbest(void* base, int T, int B, int N, int Lmax, int gram, int V) {
     NbestWorkspace w;
-    const size_t Sp = (size_t)path_pad(Lmax, 0), U = (size_t)B * N;
+    const size_t Sp = (size_t)path_pad(Lmax, gram), U = (size_t)B * N;
     char* p = (char*)base;
     size_t off = 0;
     auto take = [&](size_t n) { char* r = p ? p + off : nullptr; off += align_up(n, 256); return r; };
@@ -72,6 +87,17 @@ static NbestWorkspace carve_nbest(void* base, int T, int B, int N, int Lmax) {
     w.beta = (double*)take(sizeof(double) * U * T * Sp);
     w.total = (double*)take(sizeof(double) * U);
     w.loss = (float*)take(sizeof(float) * U);
+    w.lab_uni = w.lab_big = w.eff_len = w.idx_val = nullptr;
+    w.idx_key = nullptr;
+    w.idx_cap = 0;
+    if (gram) {
+        w.idx_cap = gram_index_capacity(V);
+        w.lab_uni = (int*)take(sizeof(int) * U * Lmax);
+        w.lab_big = (int*)take(sizeof(int) * U * Lmax);
+        w.eff_len = (int*)take(sizeof(int) * U);
+        w.idx_key = (unsigned long long*)take(sizeof(unsigned long long) * w.idx_cap);
+        w.idx_val = (int*)take(sizeof(int) * w.idx_cap);
+    }
     w.bytes = off;
     return w;
 }

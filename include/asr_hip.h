@@ -87,6 +87,32 @@ int asr_ctc_nbest_forward(void* stream, const float* xs, const int32_t* hyp, con
                           int B, int V, int N, int Lmax, int blank, float* logp, void* workspace, size_t workspace_bytes);
 int asr_ctc_nbest_backward(void* stream, const float* xs, const int32_t* x_len, int T, int B, int V, int N, int Lmax,
                            const float* gy, float* grad, const void* workspace, size_t workspace_bytes);
+/* The same for Gram-CTC: the exact log p(string_n | x_b) of N strings of characters per utterance, every way of cutting a
+ * string into the unigram and bigram tokens of the table summed, and the gradient of sum_{b,n} gy[b,n] log p (DESIGN.md section
+ * 21).  The lattice of a string is asr_ctc_forward's Gram-CTC lattice with label_unigram[i] = the token that spells (s[i]) and
+ * label_bigram[i] = the token that spells (s[i-1], s[i]), -1 where the table has none: every bigram of the table is offered.
+ *   xs, x_len, blank, logp, gy, grad  as in asr_ctc_nbest_*; for N = 1 logp is minus asr_ctc_forward's loss_per_utt on those labels
+ *   hyp (B, N, Lmax) int32 characters (the ids asr_gram_ctc_beam_search returns), hyp_len (B, N) int32
+ *   gram (V, 2) int32   the inventory, as asr_gram_ctc_beam_search takes it: (u, -1) a unigram token, (u1, u2) a bigram token,
+ *                       (-1, -1) the blank or an id that is never emitted.  It alone describes the inventory; it is read on every
+ *                       call (an index spelling -> token is built in the workspace).  Its entries are only hashed and compared,
+ *                       never used as an index; a row with an entry outside [0, V) (second entry: [-1, V)) spells nothing; of two
+ *                       rows with the same spelling the smaller token id is used, on every run.
+ *   hyp_len[b][n] < 0   an unused slot: logp -inf.  0: the empty string, logp = sum_t log softmax(xs[t][b])[blank].  Values above
+ *                       Lmax act as Lmax.  A string with a character that has no unigram token (a negative or out-of-range
+ *                       character included) is treated as an unused slot: logp -inf, no gradient -- a lattice with dead unigram
+ *                       nodes is not modelled.  A string without a path (more than 2 x_len[b] characters, ...) has logp -inf.
+ *   workspace  asr_gram_ctc_nbest_workspace_bytes(T, B, V, N, Lmax) bytes (0: the dimensions are refused); it carries alpha / beta
+ *   of the B * N lattices (3 Lmax + 1 nodes, padded to a multiple of 64) from forward to backward.
+ * N outside [1, 128], a path too long for LDS, B * N * padded path length beyond int32, or gram == NULL: ASR_ERR_UNSUPPORTED;
+ * another null pointer, another dimension <= 0, blank outside [0, V): ASR_ERR_BAD_ARG; a short workspace: ASR_ERR_WORKSPACE -- all
+ * before any launch.  No host synchronisation. */
+size_t asr_gram_ctc_nbest_workspace_bytes(int T, int B, int V, int N, int Lmax);
+int asr_gram_ctc_nbest_forward(void* stream, const float* xs, const int32_t* hyp, const int32_t* hyp_len, const int32_t* x_len,
+                               const int32_t* gram, int T, int B, int V, int N, int Lmax, int blank, float* logp, void* workspace,
+                               size_t workspace_bytes);
+int asr_gram_ctc_nbest_backward(void* stream, const float* xs, const int32_t* x_len, int T, int B, int V, int N, int Lmax,
+                                const float* gy, float* grad, const void* workspace, size_t workspace_bytes);
 
 /* ---------------------------------------------------------------------------------------- log-mel features
  * Replace fft.get_specgram / compute_logmel / compute_deltas (asr/fft.py:52-66, 6-19, 90-99), the per-utterance loop of
