@@ -835,6 +835,49 @@ def ctc_beam_search_lm(logits, lengths, blank, beam_width, top_k, image, alpha, 
     return ids, out_len, scores, ctc, lm
 
 
+def _graph_args(image):
+    """(keys, vals, slots, max_probe, ret, n_states) of a device image of asr.bias.ContextGraph.to(device)"""
+    return (ptr(image["keys"]), ptr(image["vals"]), int(image["slots"]), int(image["max_probe"]), ptr(image["ret"]),
+            int(image["n_states"]))
+
+
+def ctx_score(image, V, ids, lengths=None, finalize=True):
+    """ids (N, Lmax) int32, lengths (N) int32 or None -> (tok (N, Lmax) f32: the bonus step of every token, 0 past the length;
+    total (N) f32: their sum, plus ret[state] with `finalize`) of asr_ctx_score over the device image of an
+    asr.bias.ContextGraph"""
+    N, Lmax = ids.shape
+    dev = ids.device
+    if N == 0 or Lmax == 0:
+        raise ValueError("ctx_score needs at least one sequence and one column")
+    tok = torch.empty((N, Lmax), dtype=torch.float32, device=dev)
+    total = torch.empty((N,), dtype=torch.float32, device=dev)
+    rc = _lib.lib().asr_ctx_score(stream(), *_graph_args(image), int(V), ptr(ids), ptr(lengths), N, Lmax, int(bool(finalize)),
+                                  ptr(tok), ptr(total))
+    check(rc, "asr_ctx_score")
+    return tok, total
+
+
+def ctc_beam_search_bias(logits, lengths, blank, beam_width, top_k, graph, image=None, alpha=0.0, beta=0.0, bos=-1, eos=-1,
+                         min_logp=None):
+    """ctc_beam_search (image None) or ctc_beam_search_lm ranked with the phrase bonus of `graph` on top
+    (asr_ctc_beam_search_bias) -> (ids, lengths, scores, ctc_scores, lm_scores, bias_scores); `graph`: the device image of an
+    asr.bias.ContextGraph, `image`: that of an asr.lm.NGramLM"""
+    T, B, V = logits.shape
+    dev = logits.device
+    nbytes = _lib.lib().asr_ctc_beam_bias_workspace_bytes(T, B, V, int(beam_width), int(top_k))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    ids = torch.empty((B, beam_width, T), dtype=I32, device=dev)
+    out_len = torch.empty((B, beam_width), dtype=I32, device=dev)
+    scores, ctc, lm, bias = (torch.empty((B, beam_width), dtype=torch.float32, device=dev) for _ in range(4))
+    lm_args = (None, 0, None, None, 0, 0, 0) if image is None else _lm_args(image)
+    rc = _lib.lib().asr_ctc_beam_search_bias(stream(), ptr(logits), None if lengths is None else ptr(lengths), T, B, V, int(blank),
+                                             int(beam_width), int(top_k), float("-inf") if min_logp is None else float(min_logp),
+                                             *lm_args, int(bos), int(eos), float(alpha), float(beta), ptr(ws), nbytes, ptr(ids),
+                                             ptr(out_len), ptr(scores), ptr(ctc), ptr(lm), *_graph_args(graph), ptr(bias))
+    check(rc, "asr_ctc_beam_search_bias")
+    return ids, out_len, scores, ctc, lm, bias
+
+
 def gram_ctc_beam_search_lm(logits, lengths, blank, beam_width, top_k, gram, image, alpha, beta, bos=-1, eos=-1, min_logp=None):
     """gram_ctc_beam_search ranked by ctc + alpha * lm + beta * len over the spelled characters (asr_gram_ctc_beam_search_lm) ->
     (ids (B, beam_width, 2T), lengths, scores, ctc_scores, lm_scores); `image`: the device image of an asr.lm.NGramLM over the

@@ -75,6 +75,31 @@ def beam_decode_lm(logits, lm, lm_weight, length_bonus, beam_width=16, top_k=16,
                                    lm.bos_id, lm.eos_id if use_eos else -1, min_logp)
 
 
+def beam_decode_biased(logits, graph, lm=None, lm_weight=0.0, length_bonus=0.0, beam_width=16, top_k=16, blank=0, lengths=None,
+                       min_logp=None, use_eos=True):
+    """``beam_decode`` (`lm` None) or ``beam_decode_lm`` with contextual phrase biasing in the ranking while the beam is open:
+    `graph` is an ``asr.bias.ContextGraph`` over the logits' inventory (moved to the logits' device on first use).  Every
+    hypothesis carries the bonus of the phrases it contains plus an advance on the phrase it is in the middle of, which is
+    taken back if the phrase is not completed, so the beam keeps the start of a listed phrase alive until its last token
+    arrives.  Hypotheses are kept and sorted by log p_ctc(h | x) + lm_weight * log p_lm(h) + length_bonus * |h| + bias(h),
+    bias(h) the sum of weight * length over every occurrence of every phrase in h.
+    -> (ids, lengths, scores (the combined score), ctc_scores, lm_scores, bias_scores), the last four (B, beam_width) f32.
+    Unused slots: length 0, scores and ctc_scores -inf, lm_scores and bias_scores 0.  Without `lm`, lm_scores is all 0 and
+    `lm_weight`, `length_bonus` and `use_eos` have no effect."""
+    if graph.V != logits.shape[2] or graph.blank != blank:
+        raise ValueError("the context graph was built for %d ids with blank %d, the logits have %d with blank %d"
+                         % (graph.V, graph.blank, logits.shape[2], blank))
+    if lengths is not None:
+        lengths = lengths.to(logits.device, torch.int32).contiguous()
+    graph = graph.to(logits.device)
+    if lm is None:
+        return _ops.ctc_beam_search_bias(logits.contiguous(), lengths, blank, beam_width, top_k, graph.image, None, 0.0, 0.0, -1, -1,
+                                         min_logp)
+    lm = lm.to(logits.device)
+    return _ops.ctc_beam_search_bias(logits.contiguous(), lengths, blank, beam_width, top_k, graph.image, lm.image, lm_weight,
+                                     length_bonus, lm.bos_id, lm.eos_id if use_eos else -1, min_logp)
+
+
 def check_gram_table(gram, V, blank=0):
     """Raise ValueError unless `gram` (NumPy) is a (V, 2) integer table as ``asr.vocab.gram_table`` makes it: (-1, -1) for the
     blank, every other row (-1, -1), (u, -1) or (u1, u2) with ids in [0, V), and no two tokens with the same spelling."""

@@ -15,10 +15,13 @@
 //               by a radix select on the scores (8 bits per pass); each extension that survives becomes a node (parent node,
 //               token) of the utterance's prefix table in the workspace, and a final backtrack writes the N-best ids.  The next
 //               frame's candidate row and repeat-stay logits are loaded one frame ahead.
+//               beam_kernel<LM, BIAS>: with a language model (section 17) and / or contextual phrase biasing (section 22) in the
+//               ranking; beam_kernel<false, false> is the search described here.
 // gram_beam_kernel : the same frame loop for the Gram-CTC inventory, over spelled strings (the end of this file).
 // Integer atomics only, on LDS histograms: the same inputs give bitwise the same outputs on every launch.
 #include "common.hpp"
 #include "ngram.hpp"
+#include "ctxgraph.hpp"
 #include "../../include/asr_hip.h"
 
 namespace asr {
@@ -240,8 +243,8 @@ __device__ inline int block_excl_scan(int v, int* wsum, int* total) {
     return before_me + incl - v;
 }
 
-// The language-model side of the fused search (asr_ctc_beam_search_lm): beam_kernel<true> ranks by
-// total + (alpha * lm + beta * len); beam_kernel<false> carries none of this and is the unfused search as it was.
+// The language-model side of the fused search (asr_ctc_beam_search_lm): beam_kernel<true, .> ranks by
+// total + (alpha * lm + beta * len); beam_kernel<false, .> carries none of this and is the unfused search as it was.
 template <bool LM>
 struct Fuse {};                                                  // kernel arguments
 
@@ -264,12 +267,38 @@ struct FuseLds<true> {
     float step[MAX_EXT];                                         // log P(c | context of the parent) of the frame's extensions
 };
 
-template <bool LM>
+// The phrase-biasing side of asr_ctc_beam_search_bias: beam_kernel<LM, true> adds bias_open(h) to the ranking
+// of either search; beam_kernel<LM, false> carries none of this.  Per prefix: bias_open and the automaton state, both fixed when
+// the prefix enters the beam.  Nothing is kept per extension: a frame's m * n look-ups give the ranking its deltas, and the
+// <= beam_width extensions that survive repeat theirs (the same loads, so the same bits) for the delta and the next state.
+template <bool BIAS>
+struct Bias {};                                                  // kernel arguments
+
+template <>
+struct Bias<true> {
+    ctx::Graph g;
+    float* out_ctc;
+    float* out_lm;
+    float* out_bias;
+};
+
+template <bool BIAS>
+struct BiasLds {};
+
+template <>
+struct BiasLds<true> {
+    float open[2][MAX_BEAM];                                     // bias_open(h) of the beam's prefixes
+    int state[2][MAX_BEAM];                                      // their automaton states
+};
+
+template <bool LM, bool BIAS>
 __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__ x, const int32_t* __restrict__ lengths, int T, int B,
                                                        int V, int W, int K, int blank, Ws ws, int32_t* __restrict__ out_ids,
-                                                       int32_t* __restrict__ out_len, float* __restrict__ out_score, Fuse<LM> fz) {
+                                                       int32_t* __restrict__ out_len, float* __restrict__ out_score, Fuse<LM> fz,
+                                                       Bias<BIAS> bz) {
     __shared__ Beam bm[2];
     __shared__ FuseLds<LM> fl;
+    __shared__ BiasLds<BIAS> bl;
     __shared__ float tot[MAX_ENTRIES];                 // scores of the frame's entries in canonical order
     __shared__ float btot[MAX_BEAM], spb[MAX_BEAM], spnb[MAX_BEAM];
     __shared__ int par[MAX_BEAM], cnd[MAX_BEAM];      // a stay's parent prefix (beam slot) and the candidate rank of its last token
@@ -298,6 +327,10 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
             fl.c0[0][0] = fz.bos;
             fl.c1[0][0] = -1;
             fl.c2[0][0] = -1;
+        }
+        if constexpr (BIAS) {
+            bl.open[0][0] = 0.f;
+            bl.state[0][0] = 0;
         }
     }
     int cur = 0, m = 1;
@@ -349,12 +382,14 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
         // candidate rank of its last token -- the extension of that parent which equals the stay's prefix
         const int E = m + m * n;
         ngram::Step st;
-        if constexpr (LM) {
+        ctx::Step cs;
+        if constexpr (LM || BIAS) {
             // the m * n step look-ups, one or more per thread: the first one's loads are started here and are in flight during
             // the parent / candidate matching below
             if (m + tid < E) {
                 const int j = tid / n, r = tid - j * n;
-                st = ngram::step_issue(fz.lm, fl.c0[cur][j], fl.c1[cur][j], fl.c2[cur][j], cid[r]);
+                if constexpr (LM) st = ngram::step_issue(fz.lm, fl.c0[cur][j], fl.c1[cur][j], fl.c2[cur][j], cid[r]);
+                if constexpr (BIAS) cs = ctx::step_issue(bz.g, bl.state[cur][j], cid[r]);
             }
         } else {
             for (int e = m + tid; e < E; e += THREADS) {
@@ -371,7 +406,7 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
             const int i = p / n, r = p - i * n;
             if (o.len[i] > 0 && cid[r] == o.last[i]) cnd[i] = r;
         }
-        if constexpr (LM) {
+        if constexpr (LM && !BIAS) {
             for (int e = m + tid; e < E; e += THREADS) {
                 const int q = e - m, j = q / n, r = q - j * n;
                 if (q >= THREADS) st = ngram::step_issue(fz.lm, fl.c0[cur][j], fl.c1[cur][j], fl.c2[cur][j], cid[r]);
@@ -379,6 +414,24 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
                 fl.step[q] = s;
                 const float base = o.last[j] == cid[r] ? o.pb[j] : btot[j];
                 tot[e] = (base + clp[r]) + (fz.alpha * (fl.lm[cur][j] + s) + fz.beta * (float)(o.len[j] + 1));
+            }
+        }
+        if constexpr (BIAS) {
+            for (int e = m + tid; e < E; e += THREADS) {
+                const int q = e - m, j = q / n, r = q - j * n;
+                if (q >= THREADS) {
+                    if constexpr (LM) st = ngram::step_issue(fz.lm, fl.c0[cur][j], fl.c1[cur][j], fl.c2[cur][j], cid[r]);
+                    cs = ctx::step_issue(bz.g, bl.state[cur][j], cid[r]);
+                }
+                const float base = o.last[j] == cid[r] ? o.pb[j] : btot[j];
+                float v = base + clp[r];
+                if constexpr (LM) {
+                    const float s = ngram::step_finish(fz.lm, st);
+                    fl.step[q] = s;
+                    v += fz.alpha * (fl.lm[cur][j] + s) + fz.beta * (float)(o.len[j] + 1);
+                }
+                int unused;
+                tot[e] = v + (bl.open[cur][j] + ctx::step_finish(bz.g, cs, &unused));     // + bias_open(h + c)
             }
         }
         __syncthreads();
@@ -396,6 +449,7 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
             spnb[i] = npnb;
             if constexpr (LM) tot[i] = lae(npb, npnb) + (fz.alpha * fl.lm[cur][i] + fz.beta * (float)o.len[i]);
             else tot[i] = lae(npb, npnb);
+            if constexpr (BIAS) tot[i] += bl.open[cur][i];
         }
         __syncthreads();
         // D: radix select of the W best valid entries, 8 bits of the key per pass from the top: key >> sh > tau >> sh, and the
@@ -481,12 +535,16 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
         // F: rank the survivors (score descending, canonical position on ties) into the next beam
         if (tid < M) {
             const float f = sv_tot[tid];
+            const int e = sv_pos[tid];
+            if constexpr (BIAS) {
+                // a surviving extension looks its step up again, for the delta and the next state; the loads fly during the count
+                if (e >= m) cs = ctx::step_issue(bz.g, bl.state[cur][(e - m) / n], cid[(e - m) % n]);
+            }
             int rank = 0;
             for (int u = 0; u < M; ++u) {
                 const float g2 = sv_tot[u];
                 rank += g2 > f || (g2 == f && u < tid);
             }
-            const int e = sv_pos[tid];
             if (e < m) {
                 nx.pb[rank] = spb[e];
                 nx.pnb[rank] = spnb[e];
@@ -503,6 +561,10 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
                     fl.c1[cur ^ 1][rank] = fl.c1[cur][e];
                     fl.c2[cur ^ 1][rank] = fl.c2[cur][e];
                 }
+                if constexpr (BIAS) {
+                    bl.open[cur ^ 1][rank] = bl.open[cur][e];
+                    bl.state[cur ^ 1][rank] = bl.state[cur][e];
+                }
             } else {
                 const int q2 = e - m, j = q2 / n, r = q2 - j * n, c = cid[r];
                 const int id = t * W + rank;
@@ -514,8 +576,15 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
                     fl.c0[cur ^ 1][rank] = c;
                     fl.c1[cur ^ 1][rank] = fl.c0[cur][j];
                     fl.c2[cur ^ 1][rank] = fl.c1[cur][j];
+                } else if constexpr (BIAS) {
+                    nx.pnb[rank] = (o.last[j] == c ? o.pb[j] : btot[j]) + clp[r];
                 } else {
                     nx.pnb[rank] = f;
+                }
+                if constexpr (BIAS) {
+                    int next;
+                    bl.open[cur ^ 1][rank] = bl.open[cur][j] + ctx::step_finish(bz.g, cs, &next);
+                    bl.state[cur ^ 1][rank] = next;
                 }
                 nx.hash[rank] = hash_append(o.hash[j], c);
                 nx.phash[rank] = o.hash[j];
@@ -536,14 +605,25 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
     const Beam& o = bm[cur];
     // the N-best, sorted by score: ids padded with blank, then each hypothesis walks its prefix table chain back to the root
     int32_t* ids = out_ids + (size_t)b * W * T;
-    if constexpr (LM) {
-        // the end term, then the final order: score descending, ties to the earlier slot
-        float ctc = 0.f, lmv = 0.f, sc = 0.f;
+    if constexpr (LM || BIAS) {
+        // the end terms, then the final order: score descending, ties to the earlier slot
+        float* o_ctc;
+        float* o_lm;
+        if constexpr (BIAS) { o_ctc = bz.out_ctc; o_lm = bz.out_lm; }
+        else { o_ctc = fz.out_ctc; o_lm = fz.out_lm; }
+        float ctc = 0.f, lmv = 0.f, bv = 0.f, sc = 0.f;
         if (tid < m) {
             ctc = lae(o.pb[tid], o.pnb[tid]);
-            lmv = fl.lm[cur][tid];
-            if (fz.eos >= 0) lmv += ngram::step(fz.lm, fl.c0[cur][tid], fl.c1[cur][tid], fl.c2[cur][tid], fz.eos);
-            sc = ctc + (fz.alpha * lmv + fz.beta * (float)o.len[tid]);
+            sc = ctc;
+            if constexpr (LM) {
+                lmv = fl.lm[cur][tid];
+                if (fz.eos >= 0) lmv += ngram::step(fz.lm, fl.c0[cur][tid], fl.c1[cur][tid], fl.c2[cur][tid], fz.eos);
+                sc = ctc + (fz.alpha * lmv + fz.beta * (float)o.len[tid]);
+            }
+            if constexpr (BIAS) {
+                bv = bl.open[cur][tid] + bz.g.ret[bl.state[cur][tid]];        // the advance of an unfinished match goes back
+                sc += bv;
+            }
             sv_tot[tid] = sc;
         }
         __syncthreads();
@@ -555,8 +635,9 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
             }
             sv_pos[rank] = tid;
             out_score[b * W + rank] = sc;
-            fz.out_ctc[b * W + rank] = ctc;
-            fz.out_lm[b * W + rank] = lmv;
+            o_ctc[b * W + rank] = ctc;
+            o_lm[b * W + rank] = lmv;
+            if constexpr (BIAS) bz.out_bias[b * W + rank] = bv;
         }
         __syncthreads();
         for (size_t k = tid; k < (size_t)W * T; k += THREADS) {
@@ -576,8 +657,9 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
             } else {
                 out_len[b * W + tid] = 0;
                 out_score[b * W + tid] = -INFINITY;
-                fz.out_ctc[b * W + tid] = -INFINITY;
-                fz.out_lm[b * W + tid] = 0.f;
+                o_ctc[b * W + tid] = -INFINITY;
+                o_lm[b * W + tid] = 0.f;
+                if constexpr (BIAS) bz.out_bias[b * W + tid] = 0.f;
             }
         }
         return;
@@ -631,8 +713,8 @@ extern "C" int asr_ctc_beam_search(void* stream, const float* logits, const int3
     hipLaunchKernelGGL(cand_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, lengths, T, B, V,
                        blank, K, min_logp, ws);
     ASR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(beam_kernel<false>, dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V, beam_width, K,
-                       blank, ws, out_ids, out_len, out_score, Fuse<false>{});
+    hipLaunchKernelGGL((beam_kernel<false, false>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V,
+                       beam_width, K, blank, ws, out_ids, out_len, out_score, Fuse<false>{}, Bias<false>{});
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }
@@ -730,8 +812,124 @@ extern "C" int asr_ctc_beam_search_lm(void* stream, const float* logits, const i
     hipLaunchKernelGGL(cand_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, lengths, T, B, V,
                        blank, K, min_logp, ws);
     ASR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(beam_kernel<true>, dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V, beam_width, K,
-                       blank, ws, out_ids, out_len, out_score, fz);
+    hipLaunchKernelGGL((beam_kernel<true, false>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V,
+                       beam_width, K, blank, ws, out_ids, out_len, out_score, fz, Bias<false>{});
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- phrase biasing entries
+namespace asr {
+namespace beam {
+
+// one sequence per thread: a step's state comes from the step before it, so a sequence is walked in order; the sum is the
+// left-to-right f32 sum of the deltas
+__global__ __launch_bounds__(64) void ctx_score_kernel(ctx::Graph g, int V, const int32_t* __restrict__ ids,
+                                                       const int32_t* __restrict__ lengths, int N, int Lmax, int finalize,
+                                                       float* __restrict__ out_tok, float* __restrict__ out_sum) {
+    const int nseq = blockIdx.x * 64 + threadIdx.x;
+    if (nseq >= N) return;
+    const int32_t* row = ids + (size_t)nseq * Lmax;
+    float* tok = out_tok + (size_t)nseq * Lmax;
+    const int len = lengths ? min(max(lengths[nseq], 0), Lmax) : Lmax;
+    int s = 0;
+    float acc = 0.f;
+    for (int p = 0; p < len; ++p) {
+        const int c = row[p];
+        float d;
+        if (c < 0 || c >= V) {                          // not a token: NaN, and the match starts over
+            d = __int_as_float(0x7fc00000);
+            s = 0;
+        } else {
+            d = ctx::step(g, s, c, &s);
+        }
+        tok[p] = d;
+        acc += d;
+    }
+    for (int p = len; p < Lmax; ++p) tok[p] = 0.f;
+    if (finalize) acc += g.ret[s];
+    out_sum[nseq] = acc;
+}
+
+static int make_graph(const int32_t* keys, const int32_t* vals, int slots, int max_probe, const float* ret, int n_states,
+                      ctx::Graph* g) {
+    if (!ret || n_states < 1 || slots < 0) return ASR_ERR_BAD_ARG;
+    if (slots > 0 && ((slots & (slots - 1)) != 0 || max_probe <= 0 || !keys || !vals)) return ASR_ERR_BAD_ARG;
+    g->keys = slots > 0 ? (const int2*)keys : nullptr;
+    g->vals = (const int2*)vals;
+    g->ret = ret;
+    g->mask = slots > 0 ? (unsigned)slots - 1u : 0u;
+    g->max_probe = max_probe;
+    g->n_states = n_states;
+    return ASR_OK;
+}
+
+}  // namespace beam
+}  // namespace asr
+
+extern "C" int asr_ctx_score(void* stream, const int32_t* g_keys, const int32_t* g_vals, int g_slots, int g_max_probe,
+                             const float* g_ret, int g_n_states, int V, const int32_t* ids, const int32_t* lengths, int N,
+                             int Lmax, int finalize, float* out_tok, float* out_sum) {
+    if (!ids || !out_tok || !out_sum || N <= 0 || Lmax <= 0 || V <= 0) return ASR_ERR_BAD_ARG;
+    ctx::Graph g;
+    const int rc = make_graph(g_keys, g_vals, g_slots, g_max_probe, g_ret, g_n_states, &g);
+    if (rc != ASR_OK) return rc;
+    hipLaunchKernelGGL(ctx_score_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, (hipStream_t)stream, g, V, ids, lengths, N,
+                       Lmax, finalize, out_tok, out_sum);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+extern "C" size_t asr_ctc_beam_bias_workspace_bytes(int T, int B, int V, int beam_width, int top_k) {
+    return asr_ctc_beam_workspace_bytes(T, B, V, beam_width, top_k);
+}
+
+extern "C" int asr_ctc_beam_search_bias(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank,
+                                        int beam_width, int top_k, float min_logp, const float* uni, int vlm, const int32_t* keys,
+                                        const float* vals, int slots, int max_probe, int order, int bos, int eos, float alpha,
+                                        float beta, void* workspace, size_t workspace_bytes, int32_t* out_ids, int32_t* out_len,
+                                        float* out_score, float* out_ctc, float* out_lm, const int32_t* g_keys,
+                                        const int32_t* g_vals, int g_slots, int g_max_probe, const float* g_ret, int g_n_states,
+                                        float* out_bias) {
+    if (!logits || !workspace || !out_ids || !out_len || !out_score || !out_ctc || !out_lm || !out_bias || T <= 0 || B <= 0 ||
+        V <= 0 || blank < 0 || blank >= V || beam_width <= 0 || top_k <= 0)
+        return ASR_ERR_BAD_ARG;
+    const bool with_lm = uni != nullptr;
+    Fuse<true> fz;
+    if (with_lm) {
+        if (vlm < V || bos >= vlm || eos >= vlm) return ASR_ERR_BAD_ARG;
+        const int rc = make_lm(uni, vlm, keys, vals, slots, max_probe, order, &fz.lm);
+        if (rc != ASR_OK) return rc;
+    }
+    Bias<true> bz;
+    const int rc = make_graph(g_keys, g_vals, g_slots, g_max_probe, g_ret, g_n_states, &bz.g);
+    if (rc != ASR_OK) return rc;
+    if (beam_width > MAX_BEAM || top_k > MAX_TOPK || beam_width * top_k > MAX_EXT) return ASR_ERR_UNSUPPORTED;
+    if ((long long)T * beam_width > 0x7fffffffLL) return ASR_ERR_UNSUPPORTED;
+    const int K = min(top_k, V - 1);
+    Ws ws;
+    const size_t need = ws_layout(T, B, beam_width, K, (char*)workspace, &ws);
+    if (workspace_bytes < need) return ASR_ERR_WORKSPACE;
+    bz.out_ctc = out_ctc;
+    bz.out_lm = out_lm;
+    bz.out_bias = out_bias;
+    const long long rows = (long long)T * B;
+    hipLaunchKernelGGL(cand_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, lengths, T, B, V,
+                       blank, K, min_logp, ws);
+    ASR_LAUNCH_CHECK();
+    if (with_lm) {
+        fz.bos = bos < 0 ? -1 : bos;
+        fz.eos = eos < 0 ? -1 : eos;
+        fz.alpha = alpha;
+        fz.beta = beta;
+        fz.out_ctc = out_ctc;
+        fz.out_lm = out_lm;
+        hipLaunchKernelGGL((beam_kernel<true, true>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V,
+                           beam_width, K, blank, ws, out_ids, out_len, out_score, fz, bz);
+    } else {
+        hipLaunchKernelGGL((beam_kernel<false, true>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V,
+                           beam_width, K, blank, ws, out_ids, out_len, out_score, Fuse<false>{}, bz);
+    }
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }

@@ -252,6 +252,50 @@ int asr_ctc_beam_search_lm(void* stream, const float* logits, const int32_t* len
                            const float* vals, int slots, int max_probe, int order, int bos, int eos, float alpha, float beta,
                            void* workspace, size_t workspace_bytes, int32_t* out_ids, int32_t* out_len, float* out_score,
                            float* out_ctc, float* out_lm);
+/* Contextual phrase biasing (asr/bias.py builds and uploads the image): an Aho-Corasick automaton over a
+ * list of phrases (token-id sequences without the blank, each with a per-token weight w > 0) runs beside every hypothesis of the
+ * beam search, pays a bonus as a match grows and takes it back when the match is abandoned.  The reference has no biasing.
+ * Automaton: the trie of the phrases; the weight of the edge into node v is the largest w of the phrases through v; phi(s) the sum
+ * of the edge weights from the root to s; fail / goto as usual; out(s) the sum of w * length over every phrase that is a suffix of
+ * the string of s; adv(s) = phi(s) - phi(u), u the deepest of s and its trie ancestors at which a phrase ends (the root if none).
+ * A step from s on c: s' = goto(s, c), delta = out(s') + adv(s') - adv(s).  bias_open(h) is the left-to-right f32 sum of the deltas
+ * along h from the root, bias(h) = bias_open(h) - adv(state(h)): the sum of w * length over every occurrence of every phrase in h.
+ * Image (sparse, defaulting to the root):
+ *   keys (slots, 2) i32  (state, token) of a stored transition: (0, c) where goto(0, c) != 0, and (s, c), s != 0, where
+ *                        goto(s, c) != goto(0, c); an unused slot is -1 -1
+ *   vals (slots, 2) i32  (next state, the bit pattern of the f32 delta) of the transition in the same slot
+ *   ret  (n_states) f32  -adv(s);  n_states >= 1, state 0 is the root
+ *   slots is 0 (keys, vals NULL: no phrases) or a power of two; load <= 0.5; linear probing from the n-gram image's hash over the
+ *   key words (state, token, -1, -1); keys are compared in full; a probe sequence ends at a match, at an unused slot, or after
+ *   max_probe slots (the builder's longest displacement + 1), so no table content can make a kernel spin.
+ * Look-up of (s, c), in f32: a hit at (s, c) gives (next, delta); a miss there and a hit at (0, c) gives (next0, ret[s] + delta0);
+ * a miss at both gives (0, ret[s]).  A `next` outside [0, n_states) counts as 0, so no table content causes an out-of-range read.
+ * asr_ctx_score: ids (N, Lmax) i32 over [0, V), lengths (N) or NULL (all Lmax) -> out_tok (N, Lmax) f32 the delta of every token
+ * (0 past the length), out_sum (N) f32 their left-to-right sum, plus ret[state] when finalize != 0 (bias instead of bias_open).
+ * An id outside [0, V) gives NaN for that token and sends the state to the root.  Bitwise reproducible.
+ * asr_ctc_beam_search_bias: asr_ctc_beam_search_lm (uni != NULL) or asr_ctc_beam_search (uni == NULL: the other model arguments
+ * are ignored and out_lm is all 0) with every prefix carrying bias_open and its state, both fixed when the prefix enters the beam,
+ * and ranked, in every frame, by  (total + (alpha * lm + beta * len)) + bias_open  resp.  total + bias_open  in f32.  Merging,
+ * canonical positions and tie rules are the parents'; a merged entry keeps the stay's values; pb / pnb stay pure CTC quantities.
+ * After the last frame bias = bias_open + ret[state], the eos term goes into lm as in the parent, and the beam is sorted by
+ * out_score = (out_ctc + (alpha * out_lm + beta * len)) + out_bias  resp.  out_ctc + out_bias,  ties to the earlier slot.
+ *   out_ids, out_len, out_score, out_ctc, out_lm as asr_ctc_beam_search_lm       out_bias (B, beam_width) f32 bias(h), unused 0
+ *   workspace asr_ctc_beam_bias_workspace_bytes(T, B, V, beam_width, top_k) bytes
+ * Every element of every output is written on every call; an utterance without frames gives the empty hypothesis in slot 0.  With
+ * a graph without phrases (n_states 1, slots 0) the outputs equal the parent entry's bit for bit and out_bias is all 0.
+ * Limits and error codes of the parent entries; n_states < 1, ret == NULL, a g_slots that is neither 0 nor a power of two,
+ * g_max_probe <= 0 or NULL g_keys / g_vals with g_slots > 0 are ASR_ERR_BAD_ARG.  All checks run before the first launch.  Frames
+ * past lengths[b] are never read.  No host synchronisation.  Bitwise reproducible. */
+int asr_ctx_score(void* stream, const int32_t* g_keys, const int32_t* g_vals, int g_slots, int g_max_probe, const float* g_ret,
+                  int g_n_states, int V, const int32_t* ids, const int32_t* lengths, int N, int Lmax, int finalize, float* out_tok,
+                  float* out_sum);
+size_t asr_ctc_beam_bias_workspace_bytes(int T, int B, int V, int beam_width, int top_k);
+int asr_ctc_beam_search_bias(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank,
+                             int beam_width, int top_k, float min_logp, const float* uni, int vlm, const int32_t* keys,
+                             const float* vals, int slots, int max_probe, int order, int bos, int eos, float alpha, float beta,
+                             void* workspace, size_t workspace_bytes, int32_t* out_ids, int32_t* out_len, float* out_score,
+                             float* out_ctc, float* out_lm, const int32_t* g_keys, const int32_t* g_vals, int g_slots,
+                             int g_max_probe, const float* g_ret, int g_n_states, float* out_bias);
 /* Gram-CTC beam search over spelled strings: asr_ctc_beam_search for an inventory of a blank, unigrams and
  * bigrams spelled by two unigrams (the loss asr_ctc_forward computes with label_bigram).  The hypotheses are strings of unigrams; a
  * string carries the mass of its paths that end in blank, in the unigram token of its last character and in the bigram token of its
