@@ -878,6 +878,62 @@ def ctc_beam_search_bias(logits, lengths, blank, beam_width, top_k, graph, image
     return ids, out_len, scores, ctc, lm, bias
 
 
+_NO_LM = (None, 0, None, None, 0, 0, 0)
+_NO_GRAPH = (None, None, 0, 0, None, 0)
+
+
+def ctc_beam_stream_state_bytes(B, beam_width, max_frames, with_lm, with_bias):
+    """bytes of the device-resident state of a streaming beam search (asr_ctc_beam_stream_state_bytes; host only)"""
+    return _lib.lib().asr_ctc_beam_stream_state_bytes(int(B), int(beam_width), int(max_frames), int(bool(with_lm)), int(bool(with_bias)))
+
+
+def ctc_beam_stream_workspace_bytes(Tc, B, V, beam_width, top_k):
+    """bytes of the per-call scratch of ctc_beam_stream_advance for a chunk of Tc frames (host only)"""
+    return _lib.lib().asr_ctc_beam_stream_workspace_bytes(int(Tc), int(B), int(V), int(beam_width), int(top_k))
+
+
+def ctc_beam_stream_reset(state, B, beam_width, max_frames, with_lm, with_bias, bos=-1, mask=None):
+    """the root beam into `state` (uint8, ctc_beam_stream_state_bytes) for every utterance, or for those with mask[b] != 0
+    (mask (B) int32 on the device): asr_ctc_beam_stream_reset"""
+    rc = _lib.lib().asr_ctc_beam_stream_reset(stream(), ptr(state), state.numel(), int(B), int(beam_width), int(max_frames),
+                                              int(bool(with_lm)), int(bool(with_bias)), int(bos), None if mask is None else ptr(mask))
+    check(rc, "asr_ctc_beam_stream_reset")
+
+
+def ctc_beam_stream_advance(state, logits, lengths, blank, beam_width, top_k, frames_before, max_frames, image=None, graph=None,
+                            alpha=0.0, beta=0.0, min_logp=None):
+    """one chunk (Tc, B, V) f32 of logits into the beam kept in `state` (asr_ctc_beam_stream_advance); `lengths` (B) int32: the valid
+    frames of this chunk per utterance, or None; `image` / `graph`: the device images of an asr.lm.NGramLM / asr.bias.ContextGraph"""
+    Tc, B, V = logits.shape
+    nbytes = _lib.lib().asr_ctc_beam_stream_workspace_bytes(Tc, B, V, int(beam_width), int(top_k))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=logits.device)
+    rc = _lib.lib().asr_ctc_beam_stream_advance(stream(), ptr(logits), None if lengths is None else ptr(lengths), Tc, B, V, int(blank),
+                                                int(beam_width), int(top_k), float("-inf") if min_logp is None else float(min_logp),
+                                                *(_NO_LM if image is None else _lm_args(image)),
+                                                *(_NO_GRAPH if graph is None else _graph_args(graph)), float(alpha), float(beta),
+                                                int(frames_before), int(max_frames), ptr(state), state.numel(), ptr(ws), nbytes)
+    check(rc, "asr_ctc_beam_stream_advance")
+
+
+def ctc_beam_stream_result(state, B, beam_width, max_frames, blank, Lcap, image=None, graph=None, alpha=0.0, beta=0.0, eos=-1):
+    """the N-best of the beam kept in `state`, which stays as it is (asr_ctc_beam_stream_result) -> ((ids (B, beam_width, Lcap),
+    lengths, scores[, ctc_scores, lm_scores[, bias_scores]]) as the one-shot search of the same variant returns them,
+    frames (B) int32: the frames every utterance has consumed)"""
+    dev = state.device
+    ids = torch.empty((B, beam_width, Lcap), dtype=I32, device=dev)
+    out_len = torch.empty((B, beam_width), dtype=I32, device=dev)
+    frames = torch.empty((B,), dtype=I32, device=dev)
+    n = 1 if image is None and graph is None else (3 if graph is None else 4)
+    scores = tuple(torch.empty((B, beam_width), dtype=torch.float32, device=dev) for _ in range(n))
+    extra = [ptr(s) for s in scores[1:]] + [None] * (4 - n)
+    rc = _lib.lib().asr_ctc_beam_stream_result(stream(), *(_NO_LM if image is None else _lm_args(image)),
+                                               *(_NO_GRAPH if graph is None else _graph_args(graph)), float(alpha), float(beta),
+                                               int(eos), int(B), int(beam_width), int(max_frames), int(blank), int(Lcap), ptr(state),
+                                               state.numel(), ptr(ids), ptr(out_len), ptr(scores[0]), *extra, ptr(frames))
+    check(rc, "asr_ctc_beam_stream_result")
+    return (ids, out_len) + scores, frames
+
+
 def gram_ctc_beam_search_lm(logits, lengths, blank, beam_width, top_k, gram, image, alpha, beta, bos=-1, eos=-1, min_logp=None):
     """gram_ctc_beam_search ranked by ctc + alpha * lm + beta * len over the spelled characters (asr_gram_ctc_beam_search_lm) ->
     (ids (B, beam_width, 2T), lengths, scores, ctc_scores, lm_scores); `image`: the device image of an asr.lm.NGramLM over the

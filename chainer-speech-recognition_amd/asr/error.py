@@ -100,6 +100,86 @@ def beam_decode_biased(logits, graph, lm=None, lm_weight=0.0, length_bonus=0.0, 
                                      length_bonus, lm.bos_id, lm.eos_id if use_eos else -1, min_logp)
 
 
+class BeamStream:
+    """``beam_decode`` / ``beam_decode_lm`` (`lm`) / ``beam_decode_biased`` (`graph`, with or without `lm`) fed chunk by chunk:
+    the beam of `B` utterances lives on the device between the calls.  However the frames are cut into chunks, ``result()``
+    after a chunk is bit for bit what the one-shot function returns for the frames fed so far.
+
+        s = BeamStream(B, V, max_frames, beam_width=16, top_k=16, lm=lm, lm_weight=0.5, length_bonus=1.0)
+        for chunk in chunks:                    # (Tc, B, V) f32 logits on the device
+            s.advance(chunk)                    # lengths=(B) int32: the valid frames of this chunk per utterance
+            ids, lens, scores, ctc, lms = s.result()
+
+    ``reset()`` starts all utterances over; ``reset(mask)`` only those with mask[b] != 0, so a serving loop can put a new
+    utterance into a batch slot while the others go on.  The prefix table holds `max_frames` frames per utterance and is not
+    compacted: the frames fed are counted on the host from the last full reset, a partial reset does not lower that count, and
+    feeding beyond `max_frames` raises ValueError.  Nothing here synchronises with the host."""
+
+    def __init__(self, B, V, max_frames, beam_width=16, top_k=16, blank=0, min_logp=None, lm=None, lm_weight=0.0, length_bonus=0.0,
+                 graph=None, device=None):
+        if B <= 0 or V <= 0 or max_frames <= 0:
+            raise ValueError("B, V and max_frames must be positive")
+        if graph is not None and (graph.V != V or graph.blank != blank):
+            raise ValueError("the context graph was built for %d ids with blank %d, the stream has %d with blank %d"
+                             % (graph.V, graph.blank, V, blank))
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.B, self.V, self.max_frames, self.beam_width, self.top_k = int(B), int(V), int(max_frames), int(beam_width), int(top_k)
+        self.blank, self.min_logp = int(blank), min_logp
+        self.lm = None if lm is None else lm.to(self.device)
+        self.graph = None if graph is None else graph.to(self.device)
+        self.lm_weight, self.length_bonus = (float(lm_weight), float(length_bonus)) if lm is not None else (0.0, 0.0)
+        nbytes = _ops.ctc_beam_stream_state_bytes(B, beam_width, max_frames, lm is not None, graph is not None)
+        self.state = torch.zeros(max(nbytes, 1), dtype=torch.uint8, device=self.device)
+        self.fed = 0                              # frames fed since the last full reset: the capacity every slot has used
+        self.frames = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
+        self.reset()
+
+    def _images(self):
+        return (None if self.lm is None else self.lm.image), (None if self.graph is None else self.graph.image)
+
+    def reset(self, mask=None):
+        """start every utterance over, or those with mask[b] != 0 (`mask`: (B) integers, host or device)"""
+        if mask is not None:
+            mask = torch.as_tensor(mask).to(self.device, torch.int32).contiguous()
+            if tuple(mask.shape) != (self.B,):
+                raise ValueError("mask must have one entry per utterance (%d)" % self.B)
+        else:
+            self.fed = 0
+        _ops.ctc_beam_stream_reset(self.state, self.B, self.beam_width, self.max_frames, self.lm is not None, self.graph is not None,
+                                   -1 if self.lm is None else self.lm.bos_id, mask)
+
+    def advance(self, logits, lengths=None):
+        """consume a chunk (Tc, B, V) of f32 logits; `lengths` (B): the valid frames of this chunk per utterance (0: the
+        utterance is left as it is; frames past the length are never read), None: all Tc"""
+        if logits.dim() != 3 or logits.shape[1] != self.B or logits.shape[2] != self.V:
+            raise ValueError("the chunk must be (Tc, %d, %d), got %s" % (self.B, self.V, tuple(logits.shape)))
+        Tc = logits.shape[0]
+        if Tc == 0:
+            return
+        if self.fed + Tc > self.max_frames:
+            raise ValueError("%d frames fed since the last full reset, %d more exceed max_frames = %d"
+                             % (self.fed, Tc, self.max_frames))
+        if lengths is not None:
+            lengths = torch.as_tensor(lengths).to(self.device, torch.int32).contiguous()
+            if tuple(lengths.shape) != (self.B,):
+                raise ValueError("lengths must have one entry per utterance (%d)" % self.B)
+        image, graph = self._images()
+        _ops.ctc_beam_stream_advance(self.state, logits.to(self.device, torch.float32).contiguous(), lengths, self.blank,
+                                     self.beam_width, self.top_k, self.fed, self.max_frames, image, graph, self.lm_weight,
+                                     self.length_bonus, self.min_logp)
+        self.fed += Tc
+
+    def result(self, use_eos=True):
+        """the N-best of the frames fed so far: the tuple of ``beam_decode`` (3), ``beam_decode_lm`` (5) or ``beam_decode_biased``
+        (6) with ids of shape (B, beam_width, frames fed); the search goes on unchanged.  Sets ``frames`` (B) int32 on the
+        device: the frames every utterance has consumed."""
+        image, graph = self._images()
+        eos = self.lm.eos_id if self.lm is not None and use_eos else -1
+        out, self.frames = _ops.ctc_beam_stream_result(self.state, self.B, self.beam_width, self.max_frames, self.blank,
+                                                       max(self.fed, 1), image, graph, self.lm_weight, self.length_bonus, eos)
+        return (out[0][:, :, :self.fed],) + out[1:]
+
+
 def check_gram_table(gram, V, blank=0):
     """Raise ValueError unless `gram` (NumPy) is a (V, 2) integer table as ``asr.vocab.gram_table`` makes it: (-1, -1) for the
     blank, every other row (-1, -1), (u, -1) or (u1, u2) with ids in [0, V), and no two tokens with the same spelling."""

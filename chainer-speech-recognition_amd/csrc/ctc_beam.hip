@@ -291,11 +291,97 @@ struct BiasLds<true> {
     int state[2][MAX_BEAM];                                      // their automaton states
 };
 
-template <bool LM, bool BIAS>
+// The resumable search (asr_ctc_beam_stream_*): the beam between two chunks of frames lives in a State in
+// device memory.  beam_kernel<., ., ADVANCE> loads it instead of the root, runs the frame loop over the chunk and stores it back;
+// beam_kernel<., ., RESULT> loads it and runs the tail only (end terms, final order, backtrack) without storing anything;
+// beam_kernel<., ., ONESHOT> carries none of this and is the one-shot search as it was.
+constexpr int ONESHOT = 0, ADVANCE = 1, RESULT = 2;
+constexpr int STATE_MAGIC = 0x43424d53;
+constexpr int HDR_WORDS = 8;      // per utterance: magic, B, beam_width, max_frames, variant, m, frames consumed, 0
+constexpr int H_MAGIC = 0, H_B = 1, H_W = 2, H_F = 3, H_VARIANT = 4, H_M = 5, H_FRAMES = 6;
+
+struct State {
+    int* hdr;                                        // (B, HDR_WORDS)
+    float* pb;                                       // (B, W) each: the beam's fields as Beam keeps them, slot-major per utterance
+    float* pnb;
+    unsigned long long* hash;
+    unsigned long long* phash;
+    int* len;
+    int* last;
+    int* plast;
+    int* node;
+    float* lm;                                       // with a model: FuseLds' fields
+    int* c0;
+    int* c1;
+    int* c2;
+    float* open;                                     // with a graph: BiasLds' fields
+    int* state;
+    int2* table;                                     // (B, max_frames * W) prefix table
+};
+
+// F = max_frames; variant = with_lm | with_bias << 1
+__host__ __device__ inline size_t state_layout(int B, int W, int F, int variant, char* base, State* s) {
+    const size_t slots = (size_t)B * W;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return base + o; };
+    char* hdr = take((size_t)B * HDR_WORDS * 4);
+    char* pb = take(slots * 4);
+    char* pnb = take(slots * 4);
+    char* hash = take(slots * 8);
+    char* phash = take(slots * 8);
+    char* len = take(slots * 4);
+    char* last = take(slots * 4);
+    char* plast = take(slots * 4);
+    char* node = take(slots * 4);
+    char *lm = nullptr, *c0 = nullptr, *c1 = nullptr, *c2 = nullptr, *open = nullptr, *state = nullptr;
+    if (variant & 1) { lm = take(slots * 4); c0 = take(slots * 4); c1 = take(slots * 4); c2 = take(slots * 4); }
+    if (variant & 2) { open = take(slots * 4); state = take(slots * 4); }
+    char* table = take(slots * F * 8);
+    if (s) {
+        s->hdr = (int*)hdr;
+        s->pb = (float*)pb;
+        s->pnb = (float*)pnb;
+        s->hash = (unsigned long long*)hash;
+        s->phash = (unsigned long long*)phash;
+        s->len = (int*)len;
+        s->last = (int*)last;
+        s->plast = (int*)plast;
+        s->node = (int*)node;
+        s->lm = (float*)lm;
+        s->c0 = (int*)c0;
+        s->c1 = (int*)c1;
+        s->c2 = (int*)c2;
+        s->open = (float*)open;
+        s->state = (int*)state;
+        s->table = (int2*)table;
+    }
+    return off;
+}
+
+struct StrmArgs {
+    State s;
+    int max_frames, variant;
+    int32_t* out_frames;                             // RESULT only
+};
+
+template <int MODE>
+struct Strm : StrmArgs {};                           // kernel arguments
+
+template <>
+struct Strm<ONESHOT> {};
+
+// the header of utterance b was written for these dimensions and this variant
+__device__ inline bool state_matches(const int* h, int B, int W, int F, int variant) {
+    return h[H_MAGIC] == STATE_MAGIC && h[H_B] == B && h[H_W] == W && h[H_F] == F && h[H_VARIANT] == variant;
+}
+
+// ADVANCE: x, lengths and T are the chunk's (Tc frames, lengths[b] of them valid), ws holds the chunk's candidate rows and the
+// outputs are unused.  RESULT: x, lengths and ws are unused, T is the ids' row pitch (Lcap).
+template <bool LM, bool BIAS, int MODE>
 __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__ x, const int32_t* __restrict__ lengths, int T, int B,
                                                        int V, int W, int K, int blank, Ws ws, int32_t* __restrict__ out_ids,
                                                        int32_t* __restrict__ out_len, float* __restrict__ out_score, Fuse<LM> fz,
-                                                       Bias<BIAS> bz) {
+                                                       Bias<BIAS> bz, Strm<MODE> sz) {
     __shared__ Beam bm[2];
     __shared__ FuseLds<LM> fl;
     __shared__ BiasLds<BIAS> bl;
@@ -311,9 +397,51 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
     __shared__ int wsum[4];
     __shared__ int s_digit, s_need, s_all, s_done;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int len_b = lengths ? min(max(lengths[b], 0), T) : T;
-    int2* nodes = ws.node + (size_t)b * T * W;
-    if (tid == 0) {
+    int len_b = lengths ? min(max(lengths[b], 0), T) : T;
+    int2* nodes;
+    int cur = 0, m = 1, f0 = 0;                        // f0: the frames this utterance consumed before this call
+    if constexpr (MODE != ONESHOT) {
+        const int* h = sz.s.hdr + (size_t)b * HDR_WORDS;
+        const bool ok = state_matches(h, B, W, sz.max_frames, sz.variant);
+        nodes = sz.s.table + (size_t)b * sz.max_frames * W;
+        m = ok ? min(max(h[H_M], 0), W) : 0;
+        f0 = ok ? min(max(h[H_FRAMES], 0), sz.max_frames) : 0;
+        if constexpr (MODE == ADVANCE) {
+            len_b = ok ? min(len_b, sz.max_frames - f0) : 0;       // no node beyond the table, whatever the host says
+            if (len_b <= 0) return;                                  // nothing to consume: the state is not touched
+        } else {
+            len_b = 0;
+            if (tid == 0) sz.out_frames[b] = ok ? f0 : -1;
+        }
+        if (tid < m) {
+            const size_t i = (size_t)b * W + tid;
+            const int last = sz.s.last[i], len = sz.s.len[i];
+            bm[0].pb[tid] = sz.s.pb[i];
+            bm[0].pnb[tid] = sz.s.pnb[i];
+            bm[0].hash[tid] = sz.s.hash[i];
+            bm[0].phash[tid] = sz.s.phash[i];
+            bm[0].len[tid] = len;
+            bm[0].last[tid] = last;
+            bm[0].plast[tid] = sz.s.plast[i];
+            bm[0].node[tid] = sz.s.node[i];
+            if constexpr (LM) {
+                fl.lm[0][tid] = sz.s.lm[i];
+                fl.c0[0][tid] = sz.s.c0[i];
+                fl.c1[0][tid] = sz.s.c1[i];
+                fl.c2[0][tid] = sz.s.c2[i];
+            }
+            if constexpr (BIAS) {
+                bl.open[0][tid] = sz.s.open[i];
+                bl.state[0][tid] = sz.s.state[i];
+            }
+            // the logit of the prefix's last token in the chunk's first frame: the value the one-shot loop loads one frame ahead
+            if constexpr (MODE == ADVANCE)
+                bm[0].xl[tid] = len > 0 && (unsigned)last < (unsigned)V ? x[(size_t)b * V + last] : 0.f;
+        }
+    } else {
+        nodes = ws.node + (size_t)b * T * W;
+    }
+    if (MODE == ONESHOT && tid == 0) {
         bm[0].pb[0] = 0.f;
         bm[0].pnb[0] = -INFINITY;
         bm[0].hash[0] = ROOT_HASH;
@@ -333,7 +461,6 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
             bl.state[0][0] = 0;
         }
     }
-    int cur = 0, m = 1;
     // a frame's candidate row, loaded one frame ahead so that its latency stays off the serial path
     int q_n = 0, q_id = 0;
     float q_lse = 0.f, q_lpb = 0.f, q_lp = 0.f;
@@ -349,7 +476,7 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
     };
     if (len_b > 0) load_row(0);
     __syncthreads();
-    for (int t = 0; t < len_b; ++t) {
+    for (int t = 0; MODE != RESULT && t < len_b; ++t) {
         const Beam& o = bm[cur];
         Beam& nx = bm[cur ^ 1];
         const int n = min(q_n, K);
@@ -567,7 +694,7 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
                 }
             } else {
                 const int q2 = e - m, j = q2 / n, r = q2 - j * n, c = cid[r];
-                const int id = t * W + rank;
+                const int id = (MODE == ADVANCE ? f0 + t : t) * W + rank;
                 nx.pb[rank] = -INFINITY;
                 if constexpr (LM) {
                     // f is the ranking score here; the CTC score is phase B's sum again, bit for bit
@@ -603,6 +730,40 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
     __threadfence();
     __syncthreads();
     const Beam& o = bm[cur];
+    if constexpr (MODE == ADVANCE) {
+        // the beam goes back where it came from; slots past m keep what they held
+        if (tid < m) {
+            const size_t i = (size_t)b * W + tid;
+            sz.s.pb[i] = o.pb[tid];
+            sz.s.pnb[i] = o.pnb[tid];
+            sz.s.hash[i] = o.hash[tid];
+            sz.s.phash[i] = o.phash[tid];
+            sz.s.len[i] = o.len[tid];
+            sz.s.last[i] = o.last[tid];
+            sz.s.plast[i] = o.plast[tid];
+            sz.s.node[i] = o.node[tid];
+            if constexpr (LM) {
+                sz.s.lm[i] = fl.lm[cur][tid];
+                sz.s.c0[i] = fl.c0[cur][tid];
+                sz.s.c1[i] = fl.c1[cur][tid];
+                sz.s.c2[i] = fl.c2[cur][tid];
+            }
+            if constexpr (BIAS) {
+                sz.s.open[i] = bl.open[cur][tid];
+                sz.s.state[i] = bl.state[cur][tid];
+            }
+        }
+        if (tid == 0) {
+            int* h = sz.s.hdr + (size_t)b * HDR_WORDS;
+            h[H_M] = m;
+            h[H_FRAMES] = f0 + len_b;
+        }
+        return;
+    }
+    // RESULT: a hypothesis longer than the row pitch is cut (its length is reported in full), and a chain that leaves the table
+    // (a state that other code wrote into) ends there
+    int table_n = 0;
+    if constexpr (MODE == RESULT) table_n = sz.max_frames * W;
     // the N-best, sorted by score: ids padded with blank, then each hypothesis walks its prefix table chain back to the root
     int32_t* ids = out_ids + (size_t)b * W * T;
     if constexpr (LM || BIAS) {
@@ -650,8 +811,9 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
                 out_len[b * W + tid] = L;
                 int nd = o.node[h];
                 for (int p = L - 1; p >= 0; --p) {
+                    if (MODE == RESULT && (unsigned)nd >= (unsigned)table_n) break;
                     const int2 e = nodes[nd];
-                    ids[(size_t)tid * T + p] = e.y;
+                    if (MODE != RESULT || p < T) ids[(size_t)tid * T + p] = e.y;
                     nd = e.x;
                 }
             } else {
@@ -675,8 +837,9 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
             out_score[b * W + tid] = lae(o.pb[tid], o.pnb[tid]);
             int nd = o.node[tid];
             for (int p = L - 1; p >= 0; --p) {
+                if (MODE == RESULT && (unsigned)nd >= (unsigned)table_n) break;
                 const int2 e = nodes[nd];
-                ids[(size_t)tid * T + p] = e.y;
+                if (MODE != RESULT || p < T) ids[(size_t)tid * T + p] = e.y;
                 nd = e.x;
             }
         } else {
@@ -713,8 +876,8 @@ extern "C" int asr_ctc_beam_search(void* stream, const float* logits, const int3
     hipLaunchKernelGGL(cand_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, lengths, T, B, V,
                        blank, K, min_logp, ws);
     ASR_LAUNCH_CHECK();
-    hipLaunchKernelGGL((beam_kernel<false, false>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V,
-                       beam_width, K, blank, ws, out_ids, out_len, out_score, Fuse<false>{}, Bias<false>{});
+    hipLaunchKernelGGL((beam_kernel<false, false, ONESHOT>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V,
+                       beam_width, K, blank, ws, out_ids, out_len, out_score, Fuse<false>{}, Bias<false>{}, Strm<ONESHOT>{});
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }
@@ -812,8 +975,8 @@ extern "C" int asr_ctc_beam_search_lm(void* stream, const float* logits, const i
     hipLaunchKernelGGL(cand_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, lengths, T, B, V,
                        blank, K, min_logp, ws);
     ASR_LAUNCH_CHECK();
-    hipLaunchKernelGGL((beam_kernel<true, false>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V,
-                       beam_width, K, blank, ws, out_ids, out_len, out_score, fz, Bias<false>{});
+    hipLaunchKernelGGL((beam_kernel<true, false, ONESHOT>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V,
+                       beam_width, K, blank, ws, out_ids, out_len, out_score, fz, Bias<false>{}, Strm<ONESHOT>{});
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }
@@ -924,12 +1087,191 @@ extern "C" int asr_ctc_beam_search_bias(void* stream, const float* logits, const
         fz.beta = beta;
         fz.out_ctc = out_ctc;
         fz.out_lm = out_lm;
-        hipLaunchKernelGGL((beam_kernel<true, true>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V,
-                           beam_width, K, blank, ws, out_ids, out_len, out_score, fz, bz);
+        hipLaunchKernelGGL((beam_kernel<true, true, ONESHOT>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V,
+                           beam_width, K, blank, ws, out_ids, out_len, out_score, fz, bz, Strm<ONESHOT>{});
     } else {
-        hipLaunchKernelGGL((beam_kernel<false, true>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V,
-                           beam_width, K, blank, ws, out_ids, out_len, out_score, Fuse<false>{}, bz);
+        hipLaunchKernelGGL((beam_kernel<false, true, ONESHOT>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V,
+                           beam_width, K, blank, ws, out_ids, out_len, out_score, Fuse<false>{}, bz, Strm<ONESHOT>{});
     }
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- streaming entries
+namespace asr {
+namespace beam {
+
+// the header and the root beam (what beam_kernel<., ., ONESHOT> starts from) of every utterance, or of those with mask[b] != 0
+__global__ __launch_bounds__(256) void stream_reset_kernel(State s, int B, int W, int F, int variant, int bos,
+                                                           const int32_t* __restrict__ mask) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B || (mask && mask[b] == 0)) return;
+    int* h = s.hdr + (size_t)b * HDR_WORDS;
+    h[H_MAGIC] = STATE_MAGIC;
+    h[H_B] = B;
+    h[H_W] = W;
+    h[H_F] = F;
+    h[H_VARIANT] = variant;
+    h[H_M] = 1;
+    h[H_FRAMES] = 0;
+    h[HDR_WORDS - 1] = 0;
+    const size_t i = (size_t)b * W;
+    s.pb[i] = 0.f;
+    s.pnb[i] = -INFINITY;
+    s.hash[i] = ROOT_HASH;
+    s.phash[i] = 0;
+    s.len[i] = 0;
+    s.last[i] = -1;
+    s.plast[i] = -2;
+    s.node[i] = -1;
+    if (variant & 1) {
+        s.lm[i] = 0.f;
+        s.c0[i] = bos;
+        s.c1[i] = -1;
+        s.c2[i] = -1;
+    }
+    if (variant & 2) {
+        s.open[i] = 0.f;
+        s.state[i] = 0;
+    }
+}
+
+template <bool LM, bool BIAS, int MODE>
+static void launch_stream(hipStream_t st, const float* x, const int32_t* lengths, int T, int B, int V, int W, int K, int blank,
+                          const Ws& ws, int32_t* out_ids, int32_t* out_len, float* out_score, const Fuse<true>& fz,
+                          const Bias<true>& bz, const Strm<MODE>& sz) {
+    Fuse<LM> f;
+    Bias<BIAS> g;
+    if constexpr (LM) f = fz;
+    if constexpr (BIAS) g = bz;
+    hipLaunchKernelGGL((beam_kernel<LM, BIAS, MODE>), dim3(B), dim3(THREADS), 0, st, x, lengths, T, B, V, W, K, blank, ws, out_ids,
+                       out_len, out_score, f, g, sz);
+}
+
+template <int MODE>
+static void launch_stream_variant(int variant, hipStream_t st, const float* x, const int32_t* lengths, int T, int B, int V, int W,
+                                  int K, int blank, const Ws& ws, int32_t* out_ids, int32_t* out_len, float* out_score,
+                                  const Fuse<true>& fz, const Bias<true>& bz, const Strm<MODE>& sz) {
+    switch (variant) {
+        case 0: launch_stream<false, false, MODE>(st, x, lengths, T, B, V, W, K, blank, ws, out_ids, out_len, out_score, fz, bz, sz); break;
+        case 1: launch_stream<true, false, MODE>(st, x, lengths, T, B, V, W, K, blank, ws, out_ids, out_len, out_score, fz, bz, sz); break;
+        case 2: launch_stream<false, true, MODE>(st, x, lengths, T, B, V, W, K, blank, ws, out_ids, out_len, out_score, fz, bz, sz); break;
+        default: launch_stream<true, true, MODE>(st, x, lengths, T, B, V, W, K, blank, ws, out_ids, out_len, out_score, fz, bz, sz);
+    }
+}
+
+// the checks on dimensions, state size and the model / graph arguments that advance and result share; fills fz.lm, bz.g, sz->s
+static int stream_open(int B, int W, int F, const float* uni, int vlm, const int32_t* keys, const float* vals, int slots,
+                       int max_probe, int order, const int32_t* g_keys, const int32_t* g_vals, int g_slots, int g_max_probe,
+                       const float* g_ret, int g_n_states, void* state, size_t state_bytes, Fuse<true>* fz, Bias<true>* bz,
+                       StrmArgs* sz) {
+    if (!state || B <= 0 || W <= 0 || F <= 0) return ASR_ERR_BAD_ARG;
+    const bool with_lm = uni != nullptr, with_bias = g_ret != nullptr;
+    if (with_lm) {
+        const int rc = make_lm(uni, vlm, keys, vals, slots, max_probe, order, &fz->lm);
+        if (rc != ASR_OK) return rc;
+    }
+    if (with_bias) {
+        const int rc = make_graph(g_keys, g_vals, g_slots, g_max_probe, g_ret, g_n_states, &bz->g);
+        if (rc != ASR_OK) return rc;
+    } else if (g_keys || g_vals || g_slots != 0 || g_n_states != 0) {
+        return ASR_ERR_BAD_ARG;                      // a graph without its ret: section 22's check, not "no graph"
+    }
+    if (W > MAX_BEAM) return ASR_ERR_UNSUPPORTED;
+    if ((long long)F * W > 0x7fffffffLL) return ASR_ERR_UNSUPPORTED;      // prefix table node ids are int32
+    sz->max_frames = F;
+    sz->variant = (with_lm ? 1 : 0) | (with_bias ? 2 : 0);
+    sz->out_frames = nullptr;
+    if (state_bytes < state_layout(B, W, F, sz->variant, (char*)state, &sz->s)) return ASR_ERR_WORKSPACE;
+    return ASR_OK;
+}
+
+}  // namespace beam
+}  // namespace asr
+
+extern "C" size_t asr_ctc_beam_stream_state_bytes(int B, int beam_width, int max_frames, int with_lm, int with_bias) {
+    if (B <= 0 || beam_width <= 0 || max_frames <= 0) return 0;
+    return state_layout(B, beam_width, max_frames, (with_lm ? 1 : 0) | (with_bias ? 2 : 0), nullptr, nullptr);
+}
+
+extern "C" size_t asr_ctc_beam_stream_workspace_bytes(int Tc, int B, int V, int beam_width, int top_k) {
+    if (Tc <= 0 || B <= 0 || V <= 0 || beam_width <= 0 || top_k <= 0) return 0;
+    return ws_layout(Tc, B, 0, min(top_k, V - 1), nullptr, nullptr);          // the candidate rows; the prefix table is the state's
+}
+
+extern "C" int asr_ctc_beam_stream_reset(void* stream, void* state, size_t state_bytes, int B, int beam_width, int max_frames,
+                                         int with_lm, int with_bias, int bos, const int32_t* mask) {
+    if (!state || B <= 0 || beam_width <= 0 || max_frames <= 0) return ASR_ERR_BAD_ARG;
+    if (beam_width > MAX_BEAM || (long long)max_frames * beam_width > 0x7fffffffLL) return ASR_ERR_UNSUPPORTED;
+    const int variant = (with_lm ? 1 : 0) | (with_bias ? 2 : 0);
+    State s;
+    if (state_bytes < state_layout(B, beam_width, max_frames, variant, (char*)state, &s)) return ASR_ERR_WORKSPACE;
+    hipLaunchKernelGGL(stream_reset_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, s, B, beam_width,
+                       max_frames, variant, bos < 0 ? -1 : bos, mask);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+extern "C" int asr_ctc_beam_stream_advance(void* stream, const float* logits, const int32_t* lengths, int Tc, int B, int V,
+                                           int blank, int beam_width, int top_k, float min_logp, const float* uni, int vlm,
+                                           const int32_t* keys, const float* vals, int slots, int max_probe, int order,
+                                           const int32_t* g_keys, const int32_t* g_vals, int g_slots, int g_max_probe,
+                                           const float* g_ret, int g_n_states, float alpha, float beta, int frames_before,
+                                           int max_frames, void* state, size_t state_bytes, void* workspace,
+                                           size_t workspace_bytes) {
+    if (!logits || !workspace || Tc <= 0 || V <= 0 || blank < 0 || blank >= V || top_k <= 0 || frames_before < 0)
+        return ASR_ERR_BAD_ARG;
+    if (uni && vlm < V) return ASR_ERR_BAD_ARG;
+    Fuse<true> fz{};
+    Bias<true> bz{};
+    Strm<ADVANCE> sz{};
+    const int rc = stream_open(B, beam_width, max_frames, uni, vlm, keys, vals, slots, max_probe, order, g_keys, g_vals, g_slots,
+                               g_max_probe, g_ret, g_n_states, state, state_bytes, &fz, &bz, &sz);
+    if (rc != ASR_OK) return rc;
+    if (top_k > MAX_TOPK || beam_width * top_k > MAX_EXT) return ASR_ERR_UNSUPPORTED;
+    if ((long long)frames_before + Tc > max_frames) return ASR_ERR_UNSUPPORTED;
+    const int K = min(top_k, V - 1);
+    Ws ws;
+    if (workspace_bytes < ws_layout(Tc, B, 0, K, (char*)workspace, &ws)) return ASR_ERR_WORKSPACE;
+    fz.bos = fz.eos = -1;                            // the contexts start in reset and end in result
+    fz.alpha = alpha;
+    fz.beta = beta;
+    const long long rows = (long long)Tc * B;
+    hipLaunchKernelGGL(cand_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, lengths, Tc, B, V,
+                       blank, K, min_logp, ws);
+    ASR_LAUNCH_CHECK();
+    launch_stream_variant<ADVANCE>(sz.variant, (hipStream_t)stream, logits, lengths, Tc, B, V, beam_width, K, blank, ws, nullptr,
+                                   nullptr, nullptr, fz, bz, sz);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+extern "C" int asr_ctc_beam_stream_result(void* stream, const float* uni, int vlm, const int32_t* keys, const float* vals, int slots,
+                                          int max_probe, int order, const int32_t* g_keys, const int32_t* g_vals, int g_slots,
+                                          int g_max_probe, const float* g_ret, int g_n_states, float alpha, float beta, int eos,
+                                          int B, int beam_width, int max_frames, int blank, int Lcap, const void* state,
+                                          size_t state_bytes, int32_t* out_ids, int32_t* out_len, float* out_score, float* out_ctc,
+                                          float* out_lm, float* out_bias, int32_t* out_frames) {
+    if (!out_ids || !out_len || !out_score || !out_frames || Lcap <= 0 || blank < 0) return ASR_ERR_BAD_ARG;
+    if ((uni || g_ret) && (!out_ctc || !out_lm)) return ASR_ERR_BAD_ARG;
+    if (g_ret && !out_bias) return ASR_ERR_BAD_ARG;
+    if (uni && eos >= vlm) return ASR_ERR_BAD_ARG;
+    Fuse<true> fz{};
+    Bias<true> bz{};
+    Strm<RESULT> sz{};
+    const int rc = stream_open(B, beam_width, max_frames, uni, vlm, keys, vals, slots, max_probe, order, g_keys, g_vals, g_slots,
+                               g_max_probe, g_ret, g_n_states, const_cast<void*>(state), state_bytes, &fz, &bz, &sz);
+    if (rc != ASR_OK) return rc;
+    sz.out_frames = out_frames;
+    fz.bos = -1;
+    fz.eos = eos < 0 ? -1 : eos;
+    fz.alpha = alpha;
+    fz.beta = beta;
+    fz.out_ctc = bz.out_ctc = out_ctc;
+    fz.out_lm = bz.out_lm = out_lm;
+    bz.out_bias = out_bias;
+    launch_stream_variant<RESULT>(sz.variant, (hipStream_t)stream, nullptr, nullptr, Lcap, B, 0, beam_width, 0, blank, Ws{}, out_ids,
+                                  out_len, out_score, fz, bz, sz);
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }

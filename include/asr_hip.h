@@ -296,6 +296,55 @@ int asr_ctc_beam_search_bias(void* stream, const float* logits, const int32_t* l
                              void* workspace, size_t workspace_bytes, int32_t* out_ids, int32_t* out_len, float* out_score,
                              float* out_ctc, float* out_lm, const int32_t* g_keys, const int32_t* g_vals, int g_slots,
                              int g_max_probe, const float* g_ret, int g_n_states, float* out_bias);
+/* Streaming CTC beam search: asr_ctc_beam_search, asr_ctc_beam_search_lm or asr_ctc_beam_search_bias fed
+ * chunk by chunk, the beam carried between the calls in a device-resident state.  For every cutting of the frames into chunks,
+ * result after the last chunk is bit for bit the output of the one-shot entry on the concatenated frames (its first min(T, Lcap)
+ * id columns), and after every earlier chunk that of the frames so far.  The variant is fixed by what is passed: uni == NULL: no
+ * model (the other model arguments are ignored); g_ret == NULL: no graph (the other graph arguments must then be NULL / 0).  The
+ * same variant, B, beam_width and max_frames go to every call on one state.
+ *   state     asr_ctc_beam_stream_state_bytes(B, beam_width, max_frames, with_lm, with_bias) bytes, 256-byte aligned.  Per utterance
+ *             a header (a magic word, B, beam_width, max_frames, the variant, the beam's occupancy, the frames consumed), the
+ *             beam's per-prefix fields as arrays of beam_width entries (pb, pnb, hash, parent hash, len, last, parent's last,
+ *             node; with a model lm and three context tokens; with a graph bias_open and the automaton state), and the prefix
+ *             table of max_frames * beam_width (parent node, token) pairs.  Opaque to the caller; copying the bytes copies the search.
+ *   workspace asr_ctc_beam_stream_workspace_bytes(Tc, B, V, beam_width, top_k) bytes: the candidate rows of one chunk, per call
+ * reset:   writes the header and the root beam (with a model, its context is (bos); bos < 0: none) of every utterance, or, with
+ *          mask (B) int32, of the utterances with mask[b] != 0: a batch slot starts a new utterance while the others go on.
+ * advance: consumes logits (Tc, B, V) f32; lengths (B) int32 or NULL (all Tc) is the number of valid frames of this chunk per
+ *          utterance: 0 leaves that utterance untouched, frames past it are never read.  frames_before is the sum of Tc over the
+ *          advance calls since the last reset of all utterances, the host's upper bound on every utterance's consumed frames;
+ *          frames_before + Tc > max_frames is ASR_ERR_UNSUPPORTED.  On the device an utterance never consumes frames beyond
+ *          max_frames, whatever it is told, and no node is written outside the table.  blank, top_k, min_logp, alpha and beta as
+ *          in the one-shot entries; they should not change within an utterance.
+ * result:  the end terms (with a model and eos >= 0, lm += log P(eos | h); with a graph, bias = bias_open + ret[state]), the final
+ *          order and the backtrack of the one-shot entry, applied to the saved beam; the state is not changed, so it can be called
+ *          after any chunk.  out_ids (B, beam_width, Lcap) padded with blank; out_len, out_score (B, beam_width); out_ctc, out_lm
+ *          with a model or a graph, out_bias with a graph (NULL otherwise), as the one-shot entries write them; out_frames (B)
+ *          int32 the frames the utterance has consumed.  A hypothesis is never longer than the frames consumed; with a smaller
+ *          Lcap the ids are cut at Lcap, out_len is the full length, and nothing is written out of range.
+ * Every kernel that opens the state compares the utterance's header with its arguments (B, beam_width, max_frames, variant): on a
+ * mismatch advance leaves that utterance's state alone, and result writes the unused-slot values in every slot and out_frames -1.
+ * All accesses stay inside the state_bytes that the arguments name, which are checked against the state_bytes passed.
+ * NULL or non-positive arguments: ASR_ERR_BAD_ARG; the limits of asr_ctc_beam_search and max_frames * beam_width beyond int32:
+ * ASR_ERR_UNSUPPORTED; a short state or workspace: ASR_ERR_WORKSPACE; the model and graph argument checks of
+ * asr_ctc_beam_search_lm and asr_ctc_beam_search_bias.  All checks run before the first launch.  No entry allocates, synchronises
+ * or copies to the host: reset, advance and result can be enqueued back to back on one stream.  Bitwise reproducible. */
+size_t asr_ctc_beam_stream_state_bytes(int B, int beam_width, int max_frames, int with_lm, int with_bias);
+size_t asr_ctc_beam_stream_workspace_bytes(int Tc, int B, int V, int beam_width, int top_k);
+int asr_ctc_beam_stream_reset(void* stream, void* state, size_t state_bytes, int B, int beam_width, int max_frames, int with_lm,
+                              int with_bias, int bos, const int32_t* mask);
+int asr_ctc_beam_stream_advance(void* stream, const float* logits, const int32_t* lengths, int Tc, int B, int V, int blank,
+                                int beam_width, int top_k, float min_logp, const float* uni, int vlm, const int32_t* keys,
+                                const float* vals, int slots, int max_probe, int order, const int32_t* g_keys, const int32_t* g_vals,
+                                int g_slots, int g_max_probe, const float* g_ret, int g_n_states, float alpha, float beta,
+                                int frames_before, int max_frames, void* state, size_t state_bytes, void* workspace,
+                                size_t workspace_bytes);
+int asr_ctc_beam_stream_result(void* stream, const float* uni, int vlm, const int32_t* keys, const float* vals, int slots,
+                               int max_probe, int order, const int32_t* g_keys, const int32_t* g_vals, int g_slots, int g_max_probe,
+                               const float* g_ret, int g_n_states, float alpha, float beta, int eos, int B, int beam_width,
+                               int max_frames, int blank, int Lcap, const void* state, size_t state_bytes, int32_t* out_ids,
+                               int32_t* out_len, float* out_score, float* out_ctc, float* out_lm, float* out_bias,
+                               int32_t* out_frames);
 /* Gram-CTC beam search over spelled strings: asr_ctc_beam_search for an inventory of a blank, unigrams and
  * bigrams spelled by two unigrams (the loss asr_ctc_forward computes with label_bigram).  The hypotheses are strings of unigrams; a
  * string carries the mass of its paths that end in blank, in the unigram token of its last character and in the bigram token of its
