@@ -43,6 +43,18 @@ def log_softmax(x, axis=-1):
     return e - np.log(np.exp(e).sum(axis=axis, keepdims=True))
 
 
+def log_softmax_f32(x, axis=-1):
+    """log softmax with the float32 roundings of the device (csrc/ctc.hip rows_kernel): the row's log-sum-exp is held in
+    float32 and ``x - lse`` is formed and stored in float32.  The sums themselves stay float64, so the distance to
+    ``log_softmax`` is the price of the number format alone (in the spirit of oracle/bf16.py)."""
+    x = np.asarray(x, dtype=np.float32)
+    x64 = x.astype(np.float64)
+    m = x64.max(axis=axis, keepdims=True)
+    with np.errstate(invalid="ignore"):
+        lse = (m + np.log(np.exp(x64 - m).sum(axis=axis, keepdims=True))).astype(np.float32)
+    return (x - lse).astype(np.float64)
+
+
 def _lse0(c):
     """logsumexp over axis 0 that maps an all -inf column to -inf."""
     m = c.max(axis=0)
@@ -113,7 +125,8 @@ def ctc_lattice(labels_b, length, blank=0):
     skip = np.zeros(S, dtype=bool)
     ok = np.ones(L, dtype=bool)
     ok[1:] = u[1:] != u[:-1]
-    ok[0] = False          # no node at s - 2 for the first label
+    if L:
+        ok[0] = False      # no node at s - 2 for the first label
     skip[1::2] = ok
     allowed[2] = skip
     final = np.zeros(S, dtype=bool)
@@ -155,10 +168,10 @@ def _alpha_beta(logy_path, allowed, final, ks):
     return alpha, beta
 
 
-def _loss_grad(xs, lattices, ks, input_length, reduce, gy, infeasible_loss=1e10):
+def _loss_grad(xs, lattices, ks, input_length, reduce, gy, infeasible_loss=1e10, f32_logits=False):
     xs = np.asarray(xs)
     T, B, V = xs.shape
-    logy = log_softmax(xs, axis=2)
+    logy = log_softmax_f32(xs, axis=2) if f32_logits else log_softmax(xs, axis=2)
     y = np.exp(logy)
     losses = np.zeros(B)
     grad = np.zeros((T, B, V))
@@ -168,6 +181,9 @@ def _loss_grad(xs, lattices, ks, input_length, reduce, gy, infeasible_loss=1e10)
     for b in range(B):
         labels, alive, allowed, final = lattices[b]
         xl = int(input_length[b])
+        if xl <= 0:             # no frame at all: no path, and no gradient row to fill (grad is zero for t >= input_length)
+            losses[b] = infeasible_loss
+            continue
         lab = np.where(alive, labels, 0)
         lp = logy[:xl, b][:, lab]
         lp = np.where(alive[None, :], lp, NEG)
@@ -191,7 +207,7 @@ def _loss_grad(xs, lattices, ks, input_length, reduce, gy, infeasible_loss=1e10)
     return loss, grad
 
 
-def ctc_loss_grad(xs, labels, blank=0, input_length=None, label_length=None, reduce="mean", gy=None):
+def ctc_loss_grad(xs, labels, blank=0, input_length=None, label_length=None, reduce="mean", gy=None, f32_logits=False):
     """Chainer-convention CTC.  xs (T, B, V) pre-softmax activations; returns (loss, d loss / d xs)."""
     xs = np.asarray(xs)
     B = xs.shape[1]
@@ -199,11 +215,11 @@ def ctc_loss_grad(xs, labels, blank=0, input_length=None, label_length=None, red
     if label_length is None:
         label_length = np.full(B, labels.shape[1])
     lat = [ctc_lattice(labels[b], label_length[b], blank) for b in range(B)]
-    return _loss_grad(xs, lat, CTC_KS, input_length, reduce, gy)
+    return _loss_grad(xs, lat, CTC_KS, input_length, reduce, gy, f32_logits=f32_logits)
 
 
 def gram_ctc_loss_grad(xs, label_unigram, label_bigram, blank=0, input_length=None, length_unigram=None,
-                       reduce="mean", gy=None):
+                       reduce="mean", gy=None, f32_logits=False):
     """Reference-convention Gram-CTC (asr/loss/gram_ctc.py:300-315)."""
     xs = np.asarray(xs)
     B = xs.shape[1]
@@ -212,7 +228,7 @@ def gram_ctc_loss_grad(xs, label_unigram, label_bigram, blank=0, input_length=No
     if length_unigram is None:
         length_unigram = np.full(B, label_unigram.shape[1])
     lat = [gram_lattice(label_unigram[b], label_bigram[b], length_unigram[b], blank) for b in range(B)]
-    return _loss_grad(xs, lat, GRAM_KS, input_length, reduce, gy)
+    return _loss_grad(xs, lat, GRAM_KS, input_length, reduce, gy, f32_logits=f32_logits)
 
 
 def gram_connection_matrix(uni, big, length, max_nodes, blank=0, zero_padding=-1e10):

@@ -4,8 +4,8 @@ helper, not collected.  It is the oracle of tests/test_ctc_nbest_cpu.py and test
 log p(h_n | x_b) per slot, by case:
   * hyp_len < 0 (unused) and hypotheses without a path (x_len < len + number of adjacent repeats, decided HERE, explicitly):
     -inf, zero gradient.  oracle.ctc does not handle them (it returns 1e10 for an infeasible path);
-  * hyp_len == 0: the closed form sum_{t < x_len} log softmax(x[t])[blank], gradient onehot(blank) - softmax (oracle.ctc raises
-    on an empty labelling);
+  * hyp_len == 0: the closed form sum_{t < x_len} log softmax(x[t])[blank], gradient onehot(blank) - softmax (kept as a statement
+    of its own beside oracle.ctc's empty labelling);
   * everything else: oracle.ctc.ctc_loss_grad on that utterance's logits, reduce="no": logp = -loss, d logp = -d loss.
 """
 import numpy as np
