@@ -35,6 +35,7 @@ def debug_flag(key, default):
     return default
 
 c_void_p, c_int, c_float, c_size_t = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
+c_double = ctypes.c_double
 c_longlong = ctypes.c_longlong
 
 # name -> (restype, argtypes).  Mirrors include/asr_hip.h one to one; tests/test_abi.py checks both ways.
@@ -55,11 +56,11 @@ SIGNATURES = {
     "asr_gram_ctc_nbest_workspace_bytes": (c_size_t, [c_int] * 5),
     "asr_gram_ctc_nbest_forward": (c_int, [c_void_p] * 6 + [c_int] * 6 + [c_void_p, c_void_p, c_size_t]),
     "asr_gram_ctc_nbest_backward": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 3 + [c_size_t]),
-    "asr_specgram": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_longlong] + [c_int] * 4 + [c_float, c_void_p, c_void_p, c_int,
+    "asr_specgram": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_longlong] + [c_int] * 4 + [c_double, c_void_p, c_void_p, c_int,
                                c_void_p, c_void_p, c_int, c_void_p]),
     "asr_mel_bands_bytes": (c_size_t, []),
     "asr_mel_bands": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t]),
-    "asr_specgram_bands": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_longlong] + [c_int] * 4 + [c_float, c_void_p, c_void_p, c_int,
+    "asr_specgram_bands": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_longlong] + [c_int] * 4 + [c_double, c_void_p, c_void_p, c_int,
                                      c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "asr_logmel": (c_int, [c_void_p] * 3 + [c_longlong, c_int, c_int, c_void_p]),
     "asr_deltas": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_void_p] * 3),

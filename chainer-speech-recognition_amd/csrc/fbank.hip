@@ -31,10 +31,38 @@ constexpr float kPi = 3.14159265358979323846f;
 
 __device__ __forceinline__ int bitrev(int x, int bits) { return (int)(__brev((unsigned)x) >> (32 - bits)); }
 
+// the logarithm of a positive float to float64 precision, rounded once to float32: at log-mel 16 .. 19 float32 is spaced 1.9e-6, so the
+// stored value alone is worth up to 9.5e-7 of the energy it stands for, and logf's own ulp on top of that doubled it
+// (tests/test_fbank_edges_gpu.py reads energies back through exp).  v = m 2^e with m in [1/sqrt 2, sqrt 2), s = (m - 1) / (m + 1):
+// log m = 2 s (1 + s^2 / 3 + ... + s^10 / 11), the next term below 2e-11 at |s| <= 0.1716; 1 / (m + 1) from the float32 reciprocal and
+// one Newton step.  Against long double on 25 million floats: the correctly rounded float32 except in 1 of 100,000 (within 1e-4 ulp of
+// a tie).  A third of the instructions of the library's float64 log; one call per frame and mel filter.
+__device__ __forceinline__ float log_rounded_once(float v) {
+    int e;
+    float m = frexpf(v, &e);
+    if (m < 0.70710678f) { m *= 2.0f; --e; }
+    const double md = (double)m, den = md + 1.0;
+    double r = (double)__builtin_amdgcn_rcpf((float)den);
+    r = r * (2.0 - den * r);
+    const double s = (md - 1.0) * r, z = s * s;
+    double p = 2.0 / 11;
+    p = fma(p, z, 2.0 / 9); p = fma(p, z, 2.0 / 7); p = fma(p, z, 2.0 / 5); p = fma(p, z, 2.0 / 3);
+    return (float)fma((double)e, 0.6931471805599453, fma(s * z, p, 2.0 * s));
+}
+
+// y[n] = x[n] - c x[n - 1] with the coefficient to float64 precision, as its float32 head and tail in two fused multiply-adds: on a slowly
+// varying signal the difference is a small fraction of its terms (1/32 of them on a constant), and the rounding of 0.97 to float32 (3e-8)
+// alone then put 1e-6 on every sample -- 2e-6 on the power spectrum of a constant, fifty times what float32 arithmetic costs there
+// (tests/test_fbank_edges_gpu.py: dc)
+__device__ __forceinline__ float preemphasised(float x, float prev, double c) {
+    const float hi = (float)c, lo = (float)(c - (double)hi);
+    return fmaf(-lo, prev, fmaf(-hi, prev, x));
+}
+
 template <typename SigT>
 __global__ __launch_bounds__(256) void specgram_kernel(const SigT* __restrict__ signals, const int* __restrict__ lengths,
                                                        long long sig_pitch, int frame_len, int frame_step, int nfft,
-                                                       int logn, float preemph, const float* __restrict__ window,
+                                                       int logn, double preemph, const float* __restrict__ window,
                                                        const int* __restrict__ nframes, int Fmax,
                                                        float* __restrict__ pspec_out,        // (B, Fmax, nfft/2+1) or null
                                                        const float* __restrict__ fbank, int nfilt,
@@ -52,7 +80,7 @@ __global__ __launch_bounds__(256) void specgram_kernel(const SigT* __restrict__ 
             const int n = start + i;
             if (n < N) {
                 const float x = (float)sig[n];
-                v = n == 0 ? x : x - preemph * (float)sig[n - 1];
+                v = n == 0 ? x : preemphasised(x, (float)sig[n - 1], preemph);
                 v *= window[i];
             }
         }
@@ -89,7 +117,7 @@ __global__ __launch_bounds__(256) void specgram_kernel(const SigT* __restrict__ 
             float acc = 0.f;
             for (int k = 0; k < nbins; ++k) acc += ps[k] * w[k];
             if (acc == 0.f) acc = 2.220446049250313e-16f;          // np.finfo(float).eps (asr/fft.py:64)
-            logmel_out[frame * nfilt + m] = logf(acc);
+            logmel_out[frame * nfilt + m] = log_rounded_once(acc);
         }
     }
 }
@@ -190,7 +218,7 @@ __global__ __launch_bounds__(256) void mel_bands_kernel(const float* __restrict_
 
 template <typename SigT>
 __global__ __launch_bounds__(256) void specgram512_kernel(const SigT* __restrict__ signals, const int* __restrict__ lengths,
-                                                          long long sig_pitch, int frame_len, int frame_step, float preemph,
+                                                          long long sig_pitch, int frame_len, int frame_step, double preemph,
                                                           const float* __restrict__ window, const int* __restrict__ nframes,
                                                           int Fmax, int B, int groups_per_utt, float* __restrict__ pspec_out,
                                                           const float* __restrict__ fbank, int nfilt, float* __restrict__ logmel_out,
@@ -277,10 +305,10 @@ __global__ __launch_bounds__(256) void specgram512_kernel(const SigT* __restrict
         if (4 * tid < span) {
             const float x0 = (float)cur.x, x1 = (float)cur.y, x2 = (float)cur.z, x3 = (float)cur.w;
             float4 v;
-            v.x = n < N ? x0 - (n > 0 ? preemph * (float)prv : 0.f) : 0.f;
-            v.y = n + 1 < N ? x1 - preemph * x0 : 0.f;
-            v.z = n + 2 < N ? x2 - preemph * x1 : 0.f;
-            v.w = n + 3 < N ? x3 - preemph * x2 : 0.f;
+            v.x = n < N ? (n > 0 ? preemphasised(x0, (float)prv, preemph) : x0) : 0.f;
+            v.y = n + 1 < N ? preemphasised(x1, x0, preemph) : 0.f;
+            v.z = n + 2 < N ? preemphasised(x2, x1, preemph) : 0.f;
+            v.w = n + 3 < N ? preemphasised(x3, x2, preemph) : 0.f;
             *reinterpret_cast<float4*>(st + 4 * tid) = v;
         }
         __syncthreads();                // (the other buffer is still being read by slower waves: two buffers, one barrier)
@@ -379,7 +407,7 @@ __global__ __launch_bounds__(256) void specgram512_kernel(const SigT* __restrict
                     for (int k = 0; k < nbins; ++k) acc += psw[k] * w[k];
                 }
                 if (acc == 0.f) acc = 2.220446049250313e-16f;          // np.finfo(float).eps (asr/fft.py:64)
-                logmel_out[frame * nfilt + m] = logf(acc);
+                logmel_out[frame * nfilt + m] = log_rounded_once(acc);
             }
             wave_exchange_fence();      // (the next frame's split pass writes ps again)
         }
@@ -399,7 +427,7 @@ __global__ void logmel_kernel(const float* __restrict__ pspec, const float* __re
         float acc = 0.f;
         for (int k = 0; k < nbins; ++k) acc += p[k] * w[k];
         if (acc == 0.f) acc = 2.220446049250313e-16f;
-        out[i] = logf(acc);
+        out[i] = log_rounded_once(acc);
     }
 }
 
@@ -608,7 +636,7 @@ using namespace asr;
 using namespace asr::fbank;
 
 static int specgram_launch(void* stream, const void* signals, int sig_is_f32, const int32_t* lengths, long long sig_pitch,
-                           int B, int frame_len, int frame_step, int nfft, float preemph, const float* window,
+                           int B, int frame_len, int frame_step, int nfft, double preemph, const float* window,
                            const int32_t* nframes, int Fmax, float* pspec_out, const float* fbank, int nfilt,
                            float* logmel_out, const void* bands) {
     if (!signals || !lengths || !window || !nframes || B <= 0 || Fmax <= 0 || frame_step <= 0) return ASR_ERR_BAD_ARG;
@@ -649,7 +677,7 @@ static int specgram_launch(void* stream, const void* signals, int sig_is_f32, co
 }
 
 extern "C" int asr_specgram(void* stream, const void* signals, int sig_is_f32, const int32_t* lengths, long long sig_pitch,
-                            int B, int frame_len, int frame_step, int nfft, float preemph, const float* window,
+                            int B, int frame_len, int frame_step, int nfft, double preemph, const float* window,
                             const int32_t* nframes, int Fmax, float* pspec_out, const float* fbank, int nfilt,
                             float* logmel_out) {
     return specgram_launch(stream, signals, sig_is_f32, lengths, sig_pitch, B, frame_len, frame_step, nfft, preemph, window, nframes, Fmax,
@@ -657,7 +685,7 @@ extern "C" int asr_specgram(void* stream, const void* signals, int sig_is_f32, c
 }
 
 extern "C" int asr_specgram_bands(void* stream, const void* signals, int sig_is_f32, const int32_t* lengths, long long sig_pitch,
-                                  int B, int frame_len, int frame_step, int nfft, float preemph, const float* window,
+                                  int B, int frame_len, int frame_step, int nfft, double preemph, const float* window,
                                   const int32_t* nframes, int Fmax, float* pspec_out, const float* fbank, int nfilt,
                                   float* logmel_out, const void* bands) {
     return specgram_launch(stream, signals, sig_is_f32, lengths, sig_pitch, B, frame_len, frame_step, nfft, preemph, window, nframes, Fmax,

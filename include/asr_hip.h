@@ -129,7 +129,7 @@ int asr_gram_ctc_nbest_backward(void* stream, const float* xs, const int32_t* x_
  *                 T_b = nframes[b] - 2 frames, zero beyond; mean/std (3, nfilt) optional
  */
 int asr_specgram(void* stream, const void* signals, int sig_is_f32, const int32_t* lengths, long long sig_pitch, int B,
-                 int frame_len, int frame_step, int nfft, float preemph, const float* window, const int32_t* nframes,
+                 int frame_len, int frame_step, int nfft, double preemph, const float* window, const int32_t* nframes,
                  int Fmax, float* pspec_out, const float* fbank, int nfilt, float* logmel_out);
 /*   asr_mel_bands       the sparse form of a mel matrix fbank (nfilt, nbins) (asr/fft.py:68-82 builds triangles: 454 of 10280 entries are
  *                       non-zero at 40 x 257): per filter the first non-zero bin, the band length padded to a multiple of 8, the offset of its
@@ -139,7 +139,7 @@ int asr_specgram(void* stream, const void* signals, int sig_is_f32, const int32_
 size_t asr_mel_bands_bytes(void);
 int asr_mel_bands(void* stream, const float* fbank, int nfilt, int nbins, void* table, size_t table_bytes);
 int asr_specgram_bands(void* stream, const void* signals, int sig_is_f32, const int32_t* lengths, long long sig_pitch, int B,
-                       int frame_len, int frame_step, int nfft, float preemph, const float* window, const int32_t* nframes,
+                       int frame_len, int frame_step, int nfft, double preemph, const float* window, const int32_t* nframes,
                        int Fmax, float* pspec_out, const float* fbank, int nfilt, float* logmel_out, const void* bands);
 int asr_logmel(void* stream, const float* pspec, const float* fbank, long long F, int nbins, int nfilt, float* out);
 int asr_deltas(void* stream, const float* logmel, const int32_t* nframes, int B, int Fmax, int nfilt, int Tmax,

@@ -33,33 +33,40 @@ def get_filterbanks(nfilt=20, nfft=512, samplerate=16000, lowfreq=0, highfreq=No
     return fbank
 
 
-def preemphasis(signal, coeff=0.97):
-    signal = np.asarray(signal, dtype=np.float64)
-    return np.append(signal[0], signal[1:] - coeff * signal[:-1])
+# dtype=np.float32 below: every step in float32 -- what float32 arithmetic alone costs against the float64 default (the yardstick of the
+# tolerances in tests/test_fbank_edges_gpu.py).  The default, float64, is the reference's arithmetic and is what the goldens pin.
+def preemphasis(signal, coeff=0.97, dtype=np.float64):
+    signal = np.asarray(signal, dtype=dtype)
+    return np.append(signal[0], signal[1:] - dtype(coeff) * signal[:-1])
 
 
-def framesig(sig, frame_len, frame_step, winfunc=lambda n: np.ones((n,))):
+def framesig(sig, frame_len, frame_step, winfunc=lambda n: np.ones((n,)), dtype=np.float64):
     slen = len(sig)
     frame_len, frame_step = int(round(frame_len)), int(round(frame_step))
     numframes = 1 if slen <= frame_len else 1 + int(math.ceil((1.0 * slen - frame_len) / frame_step))
     padlen = int((numframes - 1) * frame_step + frame_len)
-    padsignal = np.concatenate((sig, np.zeros((padlen - slen,))))
+    padsignal = np.concatenate((sig, np.zeros((padlen - slen,), dtype=dtype)))
     idx = np.arange(frame_len)[None, :] + (np.arange(numframes) * frame_step)[:, None]
-    return padsignal[idx] * winfunc(frame_len)[None, :]
+    return padsignal[idx] * np.asarray(winfunc(frame_len), dtype=dtype)[None, :]
 
 
-def powspec(frames, nfft):
+def powspec(frames, nfft, dtype=np.float64):
+    if dtype == np.float32:         # torch's transform of a float32 tensor stays in float32 (numpy.fft widens to float64)
+        import torch
+        spec = torch.view_as_real(torch.fft.rfft(torch.from_numpy(np.ascontiguousarray(frames, dtype=np.float32)), nfft)).numpy()
+        return (np.square(spec[..., 0]) + np.square(spec[..., 1])) / np.float32(nfft)
     return 1.0 / nfft * np.square(np.absolute(np.fft.rfft(frames, nfft)))
 
 
-def get_specgram(signal, samplerate=16000, winlen=0.025, winstep=0.01, nfft=512, preemph=0.97, winfunc=lambda n: np.ones((n,))):
+def get_specgram(signal, samplerate=16000, winlen=0.025, winstep=0.01, nfft=512, preemph=0.97, winfunc=lambda n: np.ones((n,)),
+                 dtype=np.float64):
     """asr/fft.py:52-56"""
-    return powspec(framesig(preemphasis(signal, preemph), winlen * samplerate, winstep * samplerate, winfunc), nfft)
+    return powspec(framesig(preemphasis(signal, preemph, dtype), winlen * samplerate, winstep * samplerate, winfunc, dtype), nfft, dtype)
 
 
-def compute_logmel(pspec, fbank):
-    feat = np.dot(pspec, fbank.T)
-    feat = np.where(feat == 0, np.finfo(float).eps, feat)
+def compute_logmel(pspec, fbank, dtype=np.float64):
+    feat = np.dot(np.asarray(pspec, dtype=dtype), np.asarray(fbank, dtype=dtype).T)
+    feat = np.where(feat == 0, dtype(np.finfo(float).eps), feat)
     return np.log(feat)
 
 
@@ -78,13 +85,14 @@ def compute_deltas(logmel):
     return logmel[:-2], delta[:-2], delta_delta[:-2]
 
 
-def logfbank_minibatch(signals, frame_len=512, frame_step=160, nfft=512, nfilt=40, samplerate=16000, mean=None, std=None):
+def logfbank_minibatch(signals, frame_len=512, frame_step=160, nfft=512, nfilt=40, samplerate=16000, mean=None, std=None,
+                       dtype=np.float64):
     """Processor.extract_batch_features + features_to_minibatch (asr/data/processing.py:67-173), Hann window."""
     fbank = get_filterbanks(nfilt, nfft, samplerate)
     feats = []
     for s in signals:
-        ps = powspec(framesig(preemphasis(s), frame_len, frame_step, np.hanning), nfft)
-        feats.append([f.T for f in compute_deltas(compute_logmel(ps, fbank))])
+        ps = powspec(framesig(preemphasis(s, dtype=dtype), frame_len, frame_step, np.hanning, dtype), nfft, dtype)
+        feats.append([f.T for f in compute_deltas(compute_logmel(ps, fbank, dtype))])
     Tmax = max(f[0].shape[1] for f in feats)
     x = np.zeros((len(signals), 3, nfilt, Tmax), dtype=np.float32)
     lens = []
