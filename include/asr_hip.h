@@ -643,6 +643,13 @@ int asr_batchnorm_bwd(void* stream, const void* x_bf16, const void* gy_bf16, con
  * then written by a storer wave and needs no sentinel fill); 9 = ask for that kernel, 10 = the same with a forged split placement
  * (its write-through stores).  Other values: ASR_ERR_BAD_ARG (3, 5 and 6 named kernel forms that no shape selected; removed).
  * Modes >= 2 return ASR_ERR_UNSUPPORTED instead of falling back to mode 1.
+ * Widths: H % 32 == 0.  asr_gru_fwd (and asr_gru_fwd_state) serve H <= 1024; asr_gru_bwd (and asr_gru_bwd_state) stop at H <= 512
+ * and return ASR_ERR_UNSUPPORTED above (the per-step backward kernel holds at most 12 K steps of 3H / 32 per wave, and no persistent
+ * backward form is wider).  Persistent forms need a grid that fits the device's CUs (8 recurrences x H / 16 workgroups forward: H <= 512
+ * on 256 CUs); the wide backward kernel needs H >= 64, the partial-sum one H in {128, 256, 384, 512}: modes 0 / 1 fall back to one launch
+ * per time step where no persistent form serves (forward 512 < H <= 1024, backward H = 32), modes >= 2 refuse.  A refused call launches
+ * no recurrence kernel; what it may have written by then is helper output only: with x_len the pinned update-gate columns of gi / the
+ * masked copy of dy, and -- a refusal inside the forward launch helper -- cleared control words of sync_ws (never the abort word).
  * After a synchronisation ((int*)sync_ws)[1023] != 0 reports a timed-out in-launch wait (results invalid).  That word
  * is sticky: the calls zero every other control word but never this one, so a caller that reuses one sync_ws (zeroed
  * once) can look at it whenever convenient; once set, later launches give up immediately.

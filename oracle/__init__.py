@@ -19,5 +19,8 @@ What pins each restatement (see DESIGN.md section "Oracle"):
                    forward (the reference's own test strategy, ``asr/nn/test_layernorm.py:70-74``).
                    conv / max-pool / maxout / GRU / Adam are Chainer's (absent) -> PARITY UNPINNED,
                    torch-CPU fp32 is the stated stand-in.
+* ``oracle.gru_step`` one GRU step in float64, teacher-forced from a device run's saved inputs, with a derived
+                   cap per element; pinned by tests/test_oracle_gru.py against torch's
+                   float64 GRU, pack_padded_sequence and ``oracle.bf16.GRUMatched``.
 * ``oracle.text``  tokeniser / greedy decode / CER: pinned by tests/golden/text.json.
 """
