@@ -99,6 +99,13 @@ SIGNATURES = {
     "asr_gram_ctc_beam_lm_workspace_bytes": (c_size_t, [c_int] * 5),
     "asr_gram_ctc_beam_search_lm": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
                                     + [c_int] * 5 + [c_float, c_float, c_void_p, c_size_t] + [c_void_p] * 5),
+    "asr_gram_ctc_beam_stream_state_bytes": (c_size_t, [c_int] * 4),
+    "asr_gram_ctc_beam_stream_workspace_bytes": (c_size_t, [c_int] * 5),
+    "asr_gram_ctc_beam_stream_reset": (c_int, [c_void_p] * 2 + [c_size_t] + [c_int] * 4 + [c_void_p]),
+    "asr_gram_ctc_beam_stream_advance": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
+                                         + [c_int] * 4 + [c_float, c_float, c_int, c_int] + [c_void_p, c_size_t] * 2),
+    "asr_gram_ctc_beam_stream_result": (c_int, [c_void_p] * 2 + [c_int, c_void_p, c_void_p] + [c_int] * 5 + [c_float, c_float]
+                                        + [c_int] * 5 + [c_void_p, c_size_t] + [c_void_p] * 6),
     "asr_ctc_align_workspace_bytes": (c_size_t, [c_int] * 5),
     "asr_ctc_align": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p] * 9 + [c_size_t]),
     "asr_gemm_nt": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p] + [c_int] * 4),

@@ -956,6 +956,62 @@ def gram_ctc_beam_search_lm(logits, lengths, blank, beam_width, top_k, gram, ima
     return ids, out_len, scores, ctc, lm
 
 
+def gram_ctc_beam_stream_state_bytes(B, beam_width, max_frames, with_lm):
+    """bytes of the device-resident state of a streaming Gram-CTC beam search (asr_gram_ctc_beam_stream_state_bytes; host only)"""
+    return _lib.lib().asr_gram_ctc_beam_stream_state_bytes(int(B), int(beam_width), int(max_frames), int(bool(with_lm)))
+
+
+def gram_ctc_beam_stream_workspace_bytes(Tc, B, V, beam_width, top_k):
+    """bytes of the per-call scratch of gram_ctc_beam_stream_advance for a chunk of Tc frames (host only)"""
+    return _lib.lib().asr_gram_ctc_beam_stream_workspace_bytes(int(Tc), int(B), int(V), int(beam_width), int(top_k))
+
+
+def gram_ctc_beam_stream_reset(state, B, beam_width, max_frames, with_lm, mask=None):
+    """the root beam into `state` (uint8, gram_ctc_beam_stream_state_bytes) for every utterance, or for those with mask[b] != 0
+    (mask (B) int32 on the device): asr_gram_ctc_beam_stream_reset"""
+    rc = _lib.lib().asr_gram_ctc_beam_stream_reset(stream(), ptr(state), state.numel(), int(B), int(beam_width), int(max_frames),
+                                                   int(bool(with_lm)), None if mask is None else ptr(mask))
+    check(rc, "asr_gram_ctc_beam_stream_reset")
+
+
+def gram_ctc_beam_stream_advance(state, logits, lengths, blank, beam_width, top_k, gram, frames_before, max_frames, image=None,
+                                 alpha=0.0, beta=0.0, bos=-1, min_logp=None):
+    """one chunk (Tc, B, V) f32 of logits into the beam of strings kept in `state` (asr_gram_ctc_beam_stream_advance); gram (V, 2)
+    int32 on the same device (not checked here); `lengths` (B) int32: the valid frames of this chunk per utterance, or None;
+    `image`: the device image of an asr.lm.NGramLM over the unigram ids of `gram`"""
+    Tc, B, V = logits.shape
+    if gram.dtype != I32 or tuple(gram.shape) != (V, 2) or gram.device != logits.device or not gram.is_contiguous():
+        raise ValueError("gram must be a contiguous (V, 2) int32 tensor on the logits' device")
+    nbytes = _lib.lib().asr_gram_ctc_beam_stream_workspace_bytes(Tc, B, V, int(beam_width), int(top_k))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=logits.device)
+    rc = _lib.lib().asr_gram_ctc_beam_stream_advance(stream(), ptr(logits), None if lengths is None else ptr(lengths), Tc, B, V,
+                                                     int(blank), int(beam_width), int(top_k),
+                                                     float("-inf") if min_logp is None else float(min_logp), ptr(gram),
+                                                     *(_NO_LM if image is None else _lm_args(image)), int(bos), float(alpha),
+                                                     float(beta), int(frames_before), int(max_frames), ptr(state), state.numel(),
+                                                     ptr(ws), nbytes)
+    check(rc, "asr_gram_ctc_beam_stream_advance")
+
+
+def gram_ctc_beam_stream_result(state, B, beam_width, max_frames, blank, Lcap, image=None, alpha=0.0, beta=0.0, bos=-1, eos=-1):
+    """the N-best strings of the beam kept in `state`, which stays as it is (asr_gram_ctc_beam_stream_result) -> ((ids (B, beam_width,
+    Lcap), lengths, scores[, ctc_scores, lm_scores]) as the one-shot search of the same variant returns them, frames (B) int32:
+    the frames every utterance has consumed)"""
+    dev = state.device
+    ids = torch.empty((B, beam_width, Lcap), dtype=I32, device=dev)
+    out_len = torch.empty((B, beam_width), dtype=I32, device=dev)
+    frames = torch.empty((B,), dtype=I32, device=dev)
+    n = 1 if image is None else 3
+    scores = tuple(torch.empty((B, beam_width), dtype=torch.float32, device=dev) for _ in range(n))
+    extra = [ptr(s) for s in scores[1:]] + [None] * (3 - n)
+    rc = _lib.lib().asr_gram_ctc_beam_stream_result(stream(), *(_NO_LM if image is None else _lm_args(image)), int(bos), int(eos),
+                                                    float(alpha), float(beta), int(B), int(beam_width), int(max_frames), int(blank),
+                                                    int(Lcap), ptr(state), state.numel(), ptr(ids), ptr(out_len), ptr(scores[0]),
+                                                    *extra, ptr(frames))
+    check(rc, "asr_gram_ctc_beam_stream_result")
+    return (ids, out_len) + scores, frames
+
+
 def ctc_align(xs, label_unigram, label_bigram, x_len, l_len, blank):
     """(T, B, V) f32 logits + labels (B, Lmax) int32 (label_bigram None: CTC, else Gram-CTC) -> the forced alignment
     (frame_ids (B, T), tok_ids, tok_pos, tok_start, tok_end (B, Lmax) int32, tok_logp (B, Lmax) f32, n_tok (B) int32,

@@ -244,6 +244,86 @@ def gram_beam_decode_lm(logits, gram, lm, lm_weight, length_bonus, beam_width=16
                                         length_bonus, lm.bos_id, lm.eos_id if use_eos else -1, min_logp)
 
 
+class GramBeamStream:
+    """``gram_beam_decode`` / ``gram_beam_decode_lm`` (`lm`) fed chunk by chunk: the beam of strings of `B` utterances lives on the
+    device between the calls.  However the frames are cut into chunks, ``result()`` after a chunk is bit for bit what the one-shot
+    function returns for the frames fed so far.
+
+        s = GramBeamStream(B, V, max_frames, gram, beam_width=16, top_k=16, lm=lm, lm_weight=0.5, length_bonus=1.0)
+        for chunk in chunks:                    # (Tc, B, V) f32 logits on the device
+            s.advance(chunk)                    # lengths=(B) int32: the valid frames of this chunk per utterance
+            ids, lens, scores, ctc, lms = s.result()
+
+    `gram` is validated once, here, as ``gram_beam_decode`` validates it; `lm` as in ``gram_beam_decode_lm`` (``lm.vlm < V`` raises
+    ValueError).  ``reset``, partial resets, the frame count and `max_frames` behave as in ``BeamStream``; the prefix table holds
+    two characters per frame.  Nothing here synchronises with the host."""
+
+    def __init__(self, B, V, max_frames, gram, beam_width=16, top_k=16, blank=0, min_logp=None, lm=None, lm_weight=0.0,
+                 length_bonus=0.0, device=None):
+        if B <= 0 or V <= 0 or max_frames <= 0:
+            raise ValueError("B, V and max_frames must be positive")
+        if lm is not None and lm.vlm < V:
+            raise ValueError("the language model covers %d ids, fewer than the %d of the logits" % (lm.vlm, V))
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.B, self.V, self.max_frames, self.beam_width, self.top_k = int(B), int(V), int(max_frames), int(beam_width), int(top_k)
+        self.blank, self.min_logp = int(blank), min_logp
+        if isinstance(gram, torch.Tensor):
+            check_gram_table(gram.cpu().numpy(), self.V, self.blank)
+            self.gram = gram.to(self.device, torch.int32).contiguous()
+        else:
+            check_gram_table(gram, self.V, self.blank)
+            self.gram = torch.from_numpy(np.ascontiguousarray(gram, np.int32)).to(self.device)
+        self.lm = None if lm is None else lm.to(self.device)
+        self.lm_weight, self.length_bonus = (float(lm_weight), float(length_bonus)) if lm is not None else (0.0, 0.0)
+        nbytes = _ops.gram_ctc_beam_stream_state_bytes(B, beam_width, max_frames, lm is not None)
+        self.state = torch.zeros(max(nbytes, 1), dtype=torch.uint8, device=self.device)
+        self.fed = 0                              # frames fed since the last full reset: the capacity every slot has used
+        self.frames = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
+        self.reset()
+
+    def reset(self, mask=None):
+        """start every utterance over, or those with mask[b] != 0 (`mask`: (B) integers, host or device)"""
+        if mask is not None:
+            mask = torch.as_tensor(mask).to(self.device, torch.int32).contiguous()
+            if tuple(mask.shape) != (self.B,):
+                raise ValueError("mask must have one entry per utterance (%d)" % self.B)
+        else:
+            self.fed = 0
+        _ops.gram_ctc_beam_stream_reset(self.state, self.B, self.beam_width, self.max_frames, self.lm is not None, mask)
+
+    def advance(self, logits, lengths=None):
+        """consume a chunk (Tc, B, V) of f32 logits; `lengths` (B): the valid frames of this chunk per utterance (0: the
+        utterance is left as it is; frames past the length are never read), None: all Tc"""
+        if logits.dim() != 3 or logits.shape[1] != self.B or logits.shape[2] != self.V:
+            raise ValueError("the chunk must be (Tc, %d, %d), got %s" % (self.B, self.V, tuple(logits.shape)))
+        Tc = logits.shape[0]
+        if Tc == 0:
+            return
+        if self.fed + Tc > self.max_frames:
+            raise ValueError("%d frames fed since the last full reset, %d more exceed max_frames = %d"
+                             % (self.fed, Tc, self.max_frames))
+        if lengths is not None:
+            lengths = torch.as_tensor(lengths).to(self.device, torch.int32).contiguous()
+            if tuple(lengths.shape) != (self.B,):
+                raise ValueError("lengths must have one entry per utterance (%d)" % self.B)
+        _ops.gram_ctc_beam_stream_advance(self.state, logits.to(self.device, torch.float32).contiguous(), lengths, self.blank,
+                                          self.beam_width, self.top_k, self.gram, self.fed, self.max_frames,
+                                          None if self.lm is None else self.lm.image, self.lm_weight, self.length_bonus,
+                                          -1 if self.lm is None else self.lm.bos_id, self.min_logp)
+        self.fed += Tc
+
+    def result(self, use_eos=True):
+        """the N-best strings of the frames fed so far: the tuple of ``gram_beam_decode`` (3) or ``gram_beam_decode_lm`` (5) with
+        ids of shape (B, beam_width, 2 x frames fed); the search goes on unchanged.  Sets ``frames`` (B) int32 on the device: the
+        frames every utterance has consumed."""
+        eos = self.lm.eos_id if self.lm is not None and use_eos else -1
+        out, self.frames = _ops.gram_ctc_beam_stream_result(self.state, self.B, self.beam_width, self.max_frames, self.blank,
+                                                            max(2 * self.fed, 1), None if self.lm is None else self.lm.image,
+                                                            self.lm_weight, self.length_bonus,
+                                                            -1 if self.lm is None else self.lm.bos_id, eos)
+        return (out[0][:, :, :2 * self.fed],) + out[1:]
+
+
 def _error_rate(pred, pred_len, true, true_len, BLANK, vocab_token_to_id, vocab_id_to_token, print_sequences):
     """mean over the batch of Levenshtein(pred, true) / len(true) for collapsed id rows on the GPU (asr/error.py:49-68)"""
     dev = pred.device

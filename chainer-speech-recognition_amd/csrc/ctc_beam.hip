@@ -18,6 +18,7 @@
 //               beam_kernel<LM, BIAS>: with a language model (section 17) and / or contextual phrase biasing (section 22) in the
 //               ranking; beam_kernel<false, false> is the search described here.
 // gram_beam_kernel : the same frame loop for the Gram-CTC inventory, over spelled strings (the end of this file).
+//               gram_beam_kernel<LM, MODE>: with a character language model (section 20); resumable like beam_kernel (section 26).
 // Integer atomics only, on LDS histograms: the same inputs give bitwise the same outputs on every launch.
 #include "common.hpp"
 #include "ngram.hpp"
@@ -1329,12 +1330,92 @@ __device__ inline int lm_ctx(const GBeam& g, int j, int k, int bos) {
     return k == 0 ? g.c1[j] : (k == 1 ? g.c2[j] : g.c3[j]);
 }
 
-template <bool LM>
+// The resumable string search (asr_gram_ctc_beam_stream_*): section 23's scheme for GBeam.  The header has
+// the CTC stream's place and words, and its variant word carries GRAM_VARIANT, so that neither family reads the other's state:
+// state_matches compares the whole word, and the CTC variants are 0 .. 3.
+constexpr int GRAM_VARIANT = 4;
+
+struct GState {
+    int* hdr;                                        // (B, HDR_WORDS), as State's
+    float* pb;                                       // (B, W) each: the beam's fields as GBeam keeps them, slot-major per utterance
+    float* pu;
+    float* pg;
+    unsigned long long* h0;
+    unsigned long long* h1;
+    unsigned long long* h2;
+    int* len;
+    int* c1;
+    int* c2;
+    int* c3;
+    int* utok;
+    int* gtok;
+    int* node;
+    float* lm;                                       // with a model: GFuseLds' lm
+    int2* table;                                     // (B, 2 * max_frames * W) prefix table
+};
+
+// F = max_frames; variant = GRAM_VARIANT | with_lm
+__host__ __device__ inline size_t gram_state_layout(int B, int W, int F, int variant, char* base, GState* s) {
+    const size_t slots = (size_t)B * W;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return base + o; };
+    char* hdr = take((size_t)B * HDR_WORDS * 4);
+    char* pb = take(slots * 4);
+    char* pu = take(slots * 4);
+    char* pg = take(slots * 4);
+    char* h0 = take(slots * 8);
+    char* h1 = take(slots * 8);
+    char* h2 = take(slots * 8);
+    char* len = take(slots * 4);
+    char* c1 = take(slots * 4);
+    char* c2 = take(slots * 4);
+    char* c3 = take(slots * 4);
+    char* utok = take(slots * 4);
+    char* gtok = take(slots * 4);
+    char* node = take(slots * 4);
+    char* lm = (variant & 1) ? take(slots * 4) : nullptr;
+    char* table = take(slots * F * 16);
+    if (s) {
+        s->hdr = (int*)hdr;
+        s->pb = (float*)pb;
+        s->pu = (float*)pu;
+        s->pg = (float*)pg;
+        s->h0 = (unsigned long long*)h0;
+        s->h1 = (unsigned long long*)h1;
+        s->h2 = (unsigned long long*)h2;
+        s->len = (int*)len;
+        s->c1 = (int*)c1;
+        s->c2 = (int*)c2;
+        s->c3 = (int*)c3;
+        s->utok = (int*)utok;
+        s->gtok = (int*)gtok;
+        s->node = (int*)node;
+        s->lm = (float*)lm;
+        s->table = (int2*)table;
+    }
+    return off;
+}
+
+struct GStrmArgs {
+    GState s;
+    int max_frames, variant;
+    int32_t* out_frames;                             // RESULT only
+};
+
+template <int MODE>
+struct GStrm : GStrmArgs {};                         // kernel arguments
+
+template <>
+struct GStrm<ONESHOT> {};
+
+// ADVANCE: x, lengths and T are the chunk's (Tc frames, lengths[b] of them valid), ws and cgr hold the chunk's candidate rows and
+// their spellings and the outputs are unused.  RESULT: x, lengths, ws and cgr are unused, T is the ids' row pitch (Lcap).
+template <bool LM, int MODE>
 __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restrict__ x, const int32_t* __restrict__ lengths, int T,
                                                             int B, int V, int W, int K, int blank, Ws ws,
                                                             const int2* __restrict__ cgr, int32_t* __restrict__ out_ids,
                                                             int32_t* __restrict__ out_len, float* __restrict__ out_score,
-                                                            Fuse<LM> fz) {
+                                                            Fuse<LM> fz, GStrm<MODE> sz) {
     __shared__ GBeam bm[2];
     __shared__ GFuseLds<LM> fl;
     __shared__ float tot[MAX_ENTRIES];                 // scores of the frame's entries in canonical order
@@ -1352,10 +1433,52 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
     __shared__ int wsum[4];
     __shared__ int s_digit, s_need, s_all, s_done;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int len_b = lengths ? min(max(lengths[b], 0), T) : T;
-    const int T2 = 2 * T;
-    int2* nodes = ws.node + (size_t)b * T2 * W;
-    if (tid == 0) {
+    int len_b = lengths ? min(max(lengths[b], 0), T) : T;
+    const int T2 = MODE == RESULT ? T : 2 * T;        // the ids' row pitch
+    int2* nodes;
+    int cur = 0, m = 1, f0 = 0;                        // f0: the frames this utterance consumed before this call
+    if constexpr (MODE != ONESHOT) {
+        const int* h = sz.s.hdr + (size_t)b * HDR_WORDS;
+        const bool ok = state_matches(h, B, W, sz.max_frames, sz.variant);
+        nodes = sz.s.table + (size_t)b * 2 * sz.max_frames * W;
+        m = ok ? min(max(h[H_M], 0), W) : 0;
+        f0 = ok ? min(max(h[H_FRAMES], 0), sz.max_frames) : 0;
+        if constexpr (MODE == ADVANCE) {
+            len_b = ok ? min(len_b, sz.max_frames - f0) : 0;       // no node beyond the table, whatever the host says
+            if (len_b <= 0) return;                                  // nothing to consume: the state is not touched
+        } else {
+            len_b = 0;
+            if (tid == 0) sz.out_frames[b] = ok ? f0 : -1;
+        }
+        if (tid < m) {
+            const size_t i = (size_t)b * W + tid;
+            const int utok = sz.s.utok[i], gtok = sz.s.gtok[i];
+            GBeam& r = bm[0];
+            r.pb[tid] = sz.s.pb[i];
+            r.pu[tid] = sz.s.pu[i];
+            r.pg[tid] = sz.s.pg[i];
+            r.h0[tid] = sz.s.h0[i];
+            r.h1[tid] = sz.s.h1[i];
+            r.h2[tid] = sz.s.h2[i];
+            r.len[tid] = sz.s.len[i];
+            r.c1[tid] = sz.s.c1[i];
+            r.c2[tid] = sz.s.c2[i];
+            r.c3[tid] = sz.s.c3[i];
+            r.utok[tid] = utok;
+            r.gtok[tid] = gtok;
+            r.node[tid] = sz.s.node[i];
+            if constexpr (LM) fl.lm[0][tid] = sz.s.lm[i];
+            // the logits of the tokens behind pu and pg in the chunk's first frame: the values the one-shot loop loads one frame
+            // ahead.  Behind a token of -1 that loop holds 0.f (the root's is never written) and never reads it (section 26).
+            if constexpr (MODE == ADVANCE) {
+                r.xu[tid] = (unsigned)utok < (unsigned)V ? x[(size_t)b * V + utok] : 0.f;
+                r.xg[tid] = (unsigned)gtok < (unsigned)V ? x[(size_t)b * V + gtok] : 0.f;
+            }
+        }
+    } else {
+        nodes = ws.node + (size_t)b * T2 * W;
+    }
+    if (MODE == ONESHOT && tid == 0) {
         GBeam& r = bm[0];
         r.pb[0] = 0.f;
         r.pu[0] = r.pg[0] = -INFINITY;
@@ -1367,7 +1490,6 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
         r.node[0] = -1;
         if constexpr (LM) fl.lm[0][0] = 0.f;
     }
-    int cur = 0, m = 1;
     int q_n = 0, q_id = 0;
     int2 q_g = make_int2(-1, -1);
     float q_lse = 0.f, q_lpb = 0.f, q_lp = 0.f;
@@ -1384,7 +1506,7 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
     };
     if (len_b > 0) load_row(0);
     __syncthreads();
-    for (int t = 0; t < len_b; ++t) {
+    for (int t = 0; MODE != RESULT && t < len_b; ++t) {
         const GBeam& o = bm[cur];
         GBeam& nx = bm[cur ^ 1];
         const int n = min(q_n, K);
@@ -1639,7 +1761,7 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
                 // (with the language model f is the ranking score, and the own part is phase B's sum again as well)
                 const float own = !LM && jm < 0 ? f : ext_val(j, r);
                 const float oth = jm < 0 ? -INFINITY : ext_val(jm, rm);
-                const int id = 2 * (t * W + rank);
+                const int id = 2 * ((f0 + t) * W + rank);
                 nx.pb[rank] = -INFINITY;
                 if constexpr (LM) fl.lm[cur ^ 1][rank] = fl.elm[q2];
                 if (b2 < 0) {                           // s + a
@@ -1686,6 +1808,36 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
     __threadfence();
     __syncthreads();
     const GBeam& o = bm[cur];
+    if constexpr (MODE == ADVANCE) {
+        // the beam goes back where it came from; slots past m keep what they held
+        if (tid < m) {
+            const size_t i = (size_t)b * W + tid;
+            sz.s.pb[i] = o.pb[tid];
+            sz.s.pu[i] = o.pu[tid];
+            sz.s.pg[i] = o.pg[tid];
+            sz.s.h0[i] = o.h0[tid];
+            sz.s.h1[i] = o.h1[tid];
+            sz.s.h2[i] = o.h2[tid];
+            sz.s.len[i] = o.len[tid];
+            sz.s.c1[i] = o.c1[tid];
+            sz.s.c2[i] = o.c2[tid];
+            sz.s.c3[i] = o.c3[tid];
+            sz.s.utok[i] = o.utok[tid];
+            sz.s.gtok[i] = o.gtok[tid];
+            sz.s.node[i] = o.node[tid];
+            if constexpr (LM) sz.s.lm[i] = fl.lm[cur][tid];
+        }
+        if (tid == 0) {
+            int* h = sz.s.hdr + (size_t)b * HDR_WORDS;
+            h[H_M] = m;
+            h[H_FRAMES] = f0 + len_b;
+        }
+        return;
+    }
+    // RESULT: a string longer than the row pitch is cut (its length is reported in full), and a chain that leaves the table (a
+    // state that other code wrote into) ends there
+    int table_n = 0;
+    if constexpr (MODE == RESULT) table_n = 2 * sz.max_frames * W;
     // the N-best strings, sorted by score: ids padded with blank, then each walks its prefix table chain back to the root
     int32_t* ids = out_ids + (size_t)b * W * T2;
     if constexpr (LM) {
@@ -1722,8 +1874,9 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
                 out_len[b * W + tid] = L;
                 int nd = o.node[h];
                 for (int p = L - 1; p >= 0; --p) {
+                    if (MODE == RESULT && (unsigned)nd >= (unsigned)table_n) break;
                     const int2 e = nodes[nd];
-                    ids[(size_t)tid * T2 + p] = e.y;
+                    if (MODE != RESULT || p < T2) ids[(size_t)tid * T2 + p] = e.y;
                     nd = e.x;
                 }
             } else {
@@ -1746,8 +1899,9 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
             out_score[b * W + tid] = lae3(o.pb[tid], o.pu[tid], o.pg[tid]);
             int nd = o.node[tid];
             for (int p = L - 1; p >= 0; --p) {
+                if (MODE == RESULT && (unsigned)nd >= (unsigned)table_n) break;
                 const int2 e = nodes[nd];
-                ids[(size_t)tid * T2 + p] = e.y;
+                if (MODE != RESULT || p < T2) ids[(size_t)tid * T2 + p] = e.y;
                 nd = e.x;
             }
         } else {
@@ -1797,8 +1951,8 @@ extern "C" int asr_gram_ctc_beam_search(void* stream, const float* logits, const
                            B, K, ws, (const int2*)gram, cgr);
         ASR_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(gram_beam_kernel<false>, dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V, beam_width,
-                       K, blank, ws, (const int2*)cgr, out_ids, out_len, out_score, Fuse<false>{});
+    hipLaunchKernelGGL((gram_beam_kernel<false, ONESHOT>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V,
+                       beam_width, K, blank, ws, (const int2*)cgr, out_ids, out_len, out_score, Fuse<false>{}, GStrm<ONESHOT>{});
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }
@@ -1841,8 +1995,160 @@ extern "C" int asr_gram_ctc_beam_search_lm(void* stream, const float* logits, co
                            B, K, ws, (const int2*)gram, cgr);
         ASR_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(gram_beam_kernel<true>, dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V, beam_width,
-                       K, blank, ws, (const int2*)cgr, out_ids, out_len, out_score, fz);
+    hipLaunchKernelGGL((gram_beam_kernel<true, ONESHOT>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V,
+                       beam_width, K, blank, ws, (const int2*)cgr, out_ids, out_len, out_score, fz, GStrm<ONESHOT>{});
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- Gram-CTC streaming entries
+namespace asr {
+namespace beam {
+
+// the header and the root beam (what gram_beam_kernel<., ONESHOT> starts from) of every utterance, or of those with mask[b] != 0
+__global__ __launch_bounds__(256) void gram_stream_reset_kernel(GState s, int B, int W, int F, int variant,
+                                                                const int32_t* __restrict__ mask) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B || (mask && mask[b] == 0)) return;
+    int* h = s.hdr + (size_t)b * HDR_WORDS;
+    h[H_MAGIC] = STATE_MAGIC;
+    h[H_B] = B;
+    h[H_W] = W;
+    h[H_F] = F;
+    h[H_VARIANT] = variant;
+    h[H_M] = 1;
+    h[H_FRAMES] = 0;
+    h[HDR_WORDS - 1] = 0;
+    const size_t i = (size_t)b * W;
+    s.pb[i] = 0.f;
+    s.pu[i] = s.pg[i] = -INFINITY;
+    s.h0[i] = ROOT_HASH;
+    s.h1[i] = s.h2[i] = 0;
+    s.len[i] = 0;
+    s.c1[i] = s.c2[i] = s.c3[i] = -1;
+    s.utok[i] = s.gtok[i] = -1;
+    s.node[i] = -1;
+    if (variant & 1) s.lm[i] = 0.f;
+}
+
+template <int MODE>
+static void launch_gram_stream(hipStream_t st, const float* x, const int32_t* lengths, int T, int B, int V, int W, int K, int blank,
+                               const Ws& ws, const int2* cgr, int32_t* out_ids, int32_t* out_len, float* out_score,
+                               const Fuse<true>& fz, const GStrm<MODE>& sz) {
+    if (sz.variant & 1)
+        hipLaunchKernelGGL((gram_beam_kernel<true, MODE>), dim3(B), dim3(THREADS), 0, st, x, lengths, T, B, V, W, K, blank, ws, cgr,
+                           out_ids, out_len, out_score, fz, sz);
+    else
+        hipLaunchKernelGGL((gram_beam_kernel<false, MODE>), dim3(B), dim3(THREADS), 0, st, x, lengths, T, B, V, W, K, blank, ws, cgr,
+                           out_ids, out_len, out_score, Fuse<false>{}, sz);
+}
+
+// the checks on dimensions, state size and the model arguments that advance and result share; fills fz->lm and sz->s
+static int gram_stream_open(int B, int W, int F, const float* uni, int vlm, const int32_t* keys, const float* vals, int slots,
+                            int max_probe, int order, int bos, void* state, size_t state_bytes, Fuse<true>* fz, GStrmArgs* sz) {
+    if (!state || B <= 0 || W <= 0 || F <= 0) return ASR_ERR_BAD_ARG;
+    const bool with_lm = uni != nullptr;
+    if (with_lm) {
+        if (bos >= vlm) return ASR_ERR_BAD_ARG;
+        const int rc = make_lm(uni, vlm, keys, vals, slots, max_probe, order, &fz->lm);
+        if (rc != ASR_OK) return rc;
+    }
+    if (W > MAX_BEAM) return ASR_ERR_UNSUPPORTED;
+    if (2LL * F * W > 0x7fffffffLL) return ASR_ERR_UNSUPPORTED;           // prefix table node ids are int32
+    sz->max_frames = F;
+    sz->variant = GRAM_VARIANT | (with_lm ? 1 : 0);
+    sz->out_frames = nullptr;
+    if (state_bytes < gram_state_layout(B, W, F, sz->variant, (char*)state, &sz->s)) return ASR_ERR_WORKSPACE;
+    return ASR_OK;
+}
+
+}  // namespace beam
+}  // namespace asr
+
+extern "C" size_t asr_gram_ctc_beam_stream_state_bytes(int B, int beam_width, int max_frames, int with_lm) {
+    if (B <= 0 || beam_width <= 0 || max_frames <= 0) return 0;
+    return gram_state_layout(B, beam_width, max_frames, GRAM_VARIANT | (with_lm ? 1 : 0), nullptr, nullptr);
+}
+
+extern "C" size_t asr_gram_ctc_beam_stream_workspace_bytes(int Tc, int B, int V, int beam_width, int top_k) {
+    if (Tc <= 0 || B <= 0 || V <= 0 || beam_width <= 0 || top_k <= 0) return 0;
+    return gram_ws_layout(Tc, B, 0, min(top_k, V - 1), nullptr, nullptr, nullptr);    // candidate rows and spellings; no table
+}
+
+extern "C" int asr_gram_ctc_beam_stream_reset(void* stream, void* state, size_t state_bytes, int B, int beam_width, int max_frames,
+                                              int with_lm, const int32_t* mask) {
+    if (!state || B <= 0 || beam_width <= 0 || max_frames <= 0) return ASR_ERR_BAD_ARG;
+    if (beam_width > MAX_BEAM || 2LL * max_frames * beam_width > 0x7fffffffLL) return ASR_ERR_UNSUPPORTED;
+    const int variant = GRAM_VARIANT | (with_lm ? 1 : 0);
+    GState s;
+    if (state_bytes < gram_state_layout(B, beam_width, max_frames, variant, (char*)state, &s)) return ASR_ERR_WORKSPACE;
+    hipLaunchKernelGGL(gram_stream_reset_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, s, B,
+                       beam_width, max_frames, variant, mask);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+extern "C" int asr_gram_ctc_beam_stream_advance(void* stream, const float* logits, const int32_t* lengths, int Tc, int B, int V,
+                                                int blank, int beam_width, int top_k, float min_logp, const int32_t* gram,
+                                                const float* uni, int vlm, const int32_t* keys, const float* vals, int slots,
+                                                int max_probe, int order, int bos, float alpha, float beta, int frames_before,
+                                                int max_frames, void* state, size_t state_bytes, void* workspace,
+                                                size_t workspace_bytes) {
+    if (!logits || !workspace || Tc <= 0 || V <= 0 || blank < 0 || blank >= V || top_k <= 0 || frames_before < 0)
+        return ASR_ERR_BAD_ARG;
+    if (uni && vlm < V) return ASR_ERR_BAD_ARG;
+    Fuse<true> fz{};
+    GStrm<ADVANCE> sz{};
+    const int rc = gram_stream_open(B, beam_width, max_frames, uni, vlm, keys, vals, slots, max_probe, order, bos, state,
+                                    state_bytes, &fz, &sz);
+    if (rc != ASR_OK) return rc;
+    if (!gram) return ASR_ERR_UNSUPPORTED;
+    if (top_k > MAX_TOPK || beam_width * top_k > MAX_EXT) return ASR_ERR_UNSUPPORTED;
+    if ((long long)frames_before + Tc > max_frames) return ASR_ERR_UNSUPPORTED;
+    const int K = min(top_k, V - 1);
+    Ws ws;
+    int2* cgr;
+    if (workspace_bytes < gram_ws_layout(Tc, B, 0, K, (char*)workspace, &ws, &cgr)) return ASR_ERR_WORKSPACE;
+    fz.bos = bos < 0 ? -1 : bos;
+    fz.eos = -1;                                     // the strings end in result
+    fz.alpha = alpha;
+    fz.beta = beta;
+    const long long rows = (long long)Tc * B;
+    hipLaunchKernelGGL(cand_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, lengths, Tc, B, V,
+                       blank, K, min_logp, ws);
+    ASR_LAUNCH_CHECK();
+    if (K > 0) {
+        hipLaunchKernelGGL(gram_rows_kernel, dim3((unsigned)((rows * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, lengths, Tc,
+                           B, K, ws, (const int2*)gram, cgr);
+        ASR_LAUNCH_CHECK();
+    }
+    launch_gram_stream<ADVANCE>((hipStream_t)stream, logits, lengths, Tc, B, V, beam_width, K, blank, ws, (const int2*)cgr, nullptr,
+                                nullptr, nullptr, fz, sz);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+extern "C" int asr_gram_ctc_beam_stream_result(void* stream, const float* uni, int vlm, const int32_t* keys, const float* vals,
+                                               int slots, int max_probe, int order, int bos, int eos, float alpha, float beta, int B,
+                                               int beam_width, int max_frames, int blank, int Lcap, const void* state,
+                                               size_t state_bytes, int32_t* out_ids, int32_t* out_len, float* out_score,
+                                               float* out_ctc, float* out_lm, int32_t* out_frames) {
+    if (!out_ids || !out_len || !out_score || !out_frames || Lcap <= 0 || blank < 0) return ASR_ERR_BAD_ARG;
+    if (uni && (!out_ctc || !out_lm || eos >= vlm)) return ASR_ERR_BAD_ARG;
+    Fuse<true> fz{};
+    GStrm<RESULT> sz{};
+    const int rc = gram_stream_open(B, beam_width, max_frames, uni, vlm, keys, vals, slots, max_probe, order, bos,
+                                    const_cast<void*>(state), state_bytes, &fz, &sz);
+    if (rc != ASR_OK) return rc;
+    sz.out_frames = out_frames;
+    fz.bos = bos < 0 ? -1 : bos;
+    fz.eos = eos < 0 ? -1 : eos;
+    fz.alpha = alpha;
+    fz.beta = beta;
+    fz.out_ctc = out_ctc;
+    fz.out_lm = out_lm;
+    launch_gram_stream<RESULT>((hipStream_t)stream, nullptr, nullptr, Lcap, B, 0, beam_width, 0, blank, Ws{}, nullptr, out_ids,
+                               out_len, out_score, fz, sz);
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }

@@ -395,6 +395,48 @@ int asr_gram_ctc_beam_search_lm(void* stream, const float* logits, const int32_t
                                 const int32_t* keys, const float* vals, int slots, int max_probe, int order, int bos, int eos,
                                 float alpha, float beta, void* workspace, size_t workspace_bytes, int32_t* out_ids,
                                 int32_t* out_len, float* out_score, float* out_ctc, float* out_lm);
+/* Streaming Gram-CTC beam search: asr_gram_ctc_beam_search or asr_gram_ctc_beam_search_lm fed chunk by
+ * chunk, the beam of strings carried between the calls in a device-resident state: the contract of the asr_ctc_beam_stream_*
+ * block above.  For every cutting of the frames into chunks, result after a chunk is bit for bit the output of the one-shot entry
+ * on the frames so far (its first min(2T, Lcap) id columns).  uni == NULL: no model (the other model arguments are ignored).  The
+ * same variant, B, beam_width and max_frames go to every call on one state.
+ *   state     asr_gram_ctc_beam_stream_state_bytes(B, beam_width, max_frames, with_lm) bytes, 256-byte aligned.  Per utterance the
+ *             header of the CTC stream's state, in the same place, with a Gram bit in its variant word; the beam's per-string
+ *             fields as arrays of beam_width entries (pb, pu, pg, the hashes of s, s[:-1], s[:-2], len, the last three
+ *             characters, the tokens behind pu and pg, node; with a model lm); and the prefix table of 2 * max_frames * beam_width
+ *             (parent node, character) pairs.  Opaque to the caller; copying the bytes copies the search.
+ *   workspace asr_gram_ctc_beam_stream_workspace_bytes(Tc, B, V, beam_width, top_k) bytes: the candidate rows of one chunk and
+ *             their spellings, per call; it does not depend on beam_width
+ * reset:   writes the header and the root beam (the empty string) of every utterance, or, with mask (B) int32, of the utterances
+ *          with mask[b] != 0.  It takes no bos: a string's model context is its last characters with (bos) before them, which
+ *          advance and result form from the bos they are given; the same bos goes to both.
+ * advance: consumes logits (Tc, B, V) f32 with gram (V, 2) as in the one-shot entry; lengths, frames_before, max_frames and the
+ *          device-side clamp as in asr_ctc_beam_stream_advance.
+ * result:  the end term (with a model and eos >= 0, lm += step(ctx(S), eos)), the final order and the backtrack of the one-shot
+ *          entry, applied to the saved beam; the state is not changed.  out_ids (B, beam_width, Lcap) padded with blank; out_len,
+ *          out_score (B, beam_width); out_ctc, out_lm with a model (NULL otherwise); out_frames (B) int32 the frames the utterance
+ *          has consumed.  A string is never longer than twice the frames consumed; with a smaller Lcap the ids are cut at Lcap,
+ *          out_len is the full length, and nothing is written out of range.
+ * A header mismatch (B, beam_width, max_frames, variant) is handled as in the CTC stream: advance leaves that utterance's state
+ * alone, result writes the unused-slot values in every slot and out_frames -1.  The two families refuse each other's states the
+ * same way: a state reset by asr_ctc_beam_stream_reset is a mismatch here, and one reset here is a mismatch there.
+ * NULL or non-positive arguments: ASR_ERR_BAD_ARG; gram == NULL, the limits of asr_gram_ctc_beam_search, frames_before + Tc >
+ * max_frames and 2 * max_frames * beam_width beyond int32: ASR_ERR_UNSUPPORTED; a short state or workspace: ASR_ERR_WORKSPACE; the
+ * model argument checks of asr_gram_ctc_beam_search_lm.  All checks run before the first launch.  No entry allocates, synchronises
+ * or copies to the host.  Bitwise reproducible. */
+size_t asr_gram_ctc_beam_stream_state_bytes(int B, int beam_width, int max_frames, int with_lm);
+size_t asr_gram_ctc_beam_stream_workspace_bytes(int Tc, int B, int V, int beam_width, int top_k);
+int asr_gram_ctc_beam_stream_reset(void* stream, void* state, size_t state_bytes, int B, int beam_width, int max_frames, int with_lm,
+                                   const int32_t* mask);
+int asr_gram_ctc_beam_stream_advance(void* stream, const float* logits, const int32_t* lengths, int Tc, int B, int V, int blank,
+                                     int beam_width, int top_k, float min_logp, const int32_t* gram, const float* uni, int vlm,
+                                     const int32_t* keys, const float* vals, int slots, int max_probe, int order, int bos,
+                                     float alpha, float beta, int frames_before, int max_frames, void* state, size_t state_bytes,
+                                     void* workspace, size_t workspace_bytes);
+int asr_gram_ctc_beam_stream_result(void* stream, const float* uni, int vlm, const int32_t* keys, const float* vals, int slots,
+                                    int max_probe, int order, int bos, int eos, float alpha, float beta, int B, int beam_width,
+                                    int max_frames, int blank, int Lcap, const void* state, size_t state_bytes, int32_t* out_ids,
+                                    int32_t* out_len, float* out_score, float* out_ctc, float* out_lm, int32_t* out_frames);
 
 /* ---------------------------------------------------------------------------------------- dense projections
  * bf16 MFMA GEMMs (f32 accumulate).  Replace the BLAS/cuDNN calls behind chainer.links.Linear, the 1x1
