@@ -757,6 +757,24 @@ def edit_distance(ref, ref_len, hyp, hyp_len):
     return dist
 
 
+def _min_logp(min_logp):
+    """the candidate threshold as the C entries take it: None is no threshold"""
+    return float("-inf") if min_logp is None else float(min_logp)
+
+
+def _nbest_out(B, beam_width, L, dev, n_scores=1):
+    """uninitialised outputs of a beam search: ids (B, beam_width, L) int32, lengths (B, beam_width) int32 and a tuple of
+    `n_scores` (B, beam_width) f32 tensors"""
+    ids = torch.empty((B, beam_width, L), dtype=I32, device=dev)
+    out_len = torch.empty((B, beam_width), dtype=I32, device=dev)
+    return ids, out_len, tuple(torch.empty((B, beam_width), dtype=torch.float32, device=dev) for _ in range(n_scores))
+
+
+def _check_gram(gram, V, dev):
+    if gram.dtype != I32 or tuple(gram.shape) != (V, 2) or gram.device != dev or not gram.is_contiguous():
+        raise ValueError("gram must be a contiguous (V, 2) int32 tensor on the logits' device")
+
+
 def ctc_beam_search(logits, lengths, blank, beam_width, top_k, min_logp=None):
     """(T, B, V) f32 logits -> (ids (B, beam_width, T) int32 padded with blank, lengths (B, beam_width) int32,
     scores (B, beam_width) f32): the N-best of the CTC prefix beam search, best first; unused slots have length 0 and
@@ -765,12 +783,9 @@ def ctc_beam_search(logits, lengths, blank, beam_width, top_k, min_logp=None):
     dev = logits.device
     nbytes = _lib.lib().asr_ctc_beam_workspace_bytes(T, B, V, int(beam_width), int(top_k))
     ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    ids = torch.empty((B, beam_width, T), dtype=I32, device=dev)
-    out_len = torch.empty((B, beam_width), dtype=I32, device=dev)
-    scores = torch.empty((B, beam_width), dtype=torch.float32, device=dev)
-    rc = _lib.lib().asr_ctc_beam_search(stream(), ptr(logits), None if lengths is None else ptr(lengths), T, B, V, int(blank),
-                                        int(beam_width), int(top_k), float("-inf") if min_logp is None else float(min_logp),
-                                        ptr(ws), nbytes, ptr(ids), ptr(out_len), ptr(scores))
+    ids, out_len, (scores,) = _nbest_out(B, beam_width, T, dev)
+    rc = _lib.lib().asr_ctc_beam_search(stream(), ptr(logits), ptr(lengths), T, B, V, int(blank), int(beam_width), int(top_k),
+                                        _min_logp(min_logp), ptr(ws), nbytes, ptr(ids), ptr(out_len), ptr(scores))
     check(rc, "asr_ctc_beam_search")
     return ids, out_len, scores
 
@@ -782,16 +797,12 @@ def gram_ctc_beam_search(logits, lengths, blank, beam_width, top_k, gram, min_lo
     (asr.error.gram_beam_decode does)."""
     T, B, V = logits.shape
     dev = logits.device
-    if gram.dtype != I32 or tuple(gram.shape) != (V, 2) or gram.device != dev or not gram.is_contiguous():
-        raise ValueError("gram must be a contiguous (V, 2) int32 tensor on the logits' device")
+    _check_gram(gram, V, dev)
     nbytes = _lib.lib().asr_gram_ctc_beam_workspace_bytes(T, B, V, int(beam_width), int(top_k))
     ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    ids = torch.empty((B, beam_width, 2 * T), dtype=I32, device=dev)
-    out_len = torch.empty((B, beam_width), dtype=I32, device=dev)
-    scores = torch.empty((B, beam_width), dtype=torch.float32, device=dev)
-    rc = _lib.lib().asr_gram_ctc_beam_search(stream(), ptr(logits), None if lengths is None else ptr(lengths), T, B, V, int(blank),
-                                             int(beam_width), int(top_k), float("-inf") if min_logp is None else float(min_logp),
-                                             ptr(gram), ptr(ws), nbytes, ptr(ids), ptr(out_len), ptr(scores))
+    ids, out_len, (scores,) = _nbest_out(B, beam_width, 2 * T, dev)
+    rc = _lib.lib().asr_gram_ctc_beam_search(stream(), ptr(logits), ptr(lengths), T, B, V, int(blank), int(beam_width), int(top_k),
+                                             _min_logp(min_logp), ptr(gram), ptr(ws), nbytes, ptr(ids), ptr(out_len), ptr(scores))
     check(rc, "asr_gram_ctc_beam_search")
     return ids, out_len, scores
 
@@ -824,13 +835,10 @@ def ctc_beam_search_lm(logits, lengths, blank, beam_width, top_k, image, alpha, 
     dev = logits.device
     nbytes = _lib.lib().asr_ctc_beam_lm_workspace_bytes(T, B, V, int(beam_width), int(top_k))
     ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    ids = torch.empty((B, beam_width, T), dtype=I32, device=dev)
-    out_len = torch.empty((B, beam_width), dtype=I32, device=dev)
-    scores, ctc, lm = (torch.empty((B, beam_width), dtype=torch.float32, device=dev) for _ in range(3))
-    rc = _lib.lib().asr_ctc_beam_search_lm(stream(), ptr(logits), None if lengths is None else ptr(lengths), T, B, V, int(blank),
-                                           int(beam_width), int(top_k), float("-inf") if min_logp is None else float(min_logp),
-                                           *_lm_args(image), int(bos), int(eos), float(alpha), float(beta), ptr(ws), nbytes,
-                                           ptr(ids), ptr(out_len), ptr(scores), ptr(ctc), ptr(lm))
+    ids, out_len, (scores, ctc, lm) = _nbest_out(B, beam_width, T, dev, 3)
+    rc = _lib.lib().asr_ctc_beam_search_lm(stream(), ptr(logits), ptr(lengths), T, B, V, int(blank), int(beam_width), int(top_k),
+                                           _min_logp(min_logp), *_lm_args(image), int(bos), int(eos), float(alpha), float(beta),
+                                           ptr(ws), nbytes, ptr(ids), ptr(out_len), ptr(scores), ptr(ctc), ptr(lm))
     check(rc, "asr_ctc_beam_search_lm")
     return ids, out_len, scores, ctc, lm
 
@@ -866,14 +874,12 @@ def ctc_beam_search_bias(logits, lengths, blank, beam_width, top_k, graph, image
     dev = logits.device
     nbytes = _lib.lib().asr_ctc_beam_bias_workspace_bytes(T, B, V, int(beam_width), int(top_k))
     ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    ids = torch.empty((B, beam_width, T), dtype=I32, device=dev)
-    out_len = torch.empty((B, beam_width), dtype=I32, device=dev)
-    scores, ctc, lm, bias = (torch.empty((B, beam_width), dtype=torch.float32, device=dev) for _ in range(4))
-    lm_args = (None, 0, None, None, 0, 0, 0) if image is None else _lm_args(image)
-    rc = _lib.lib().asr_ctc_beam_search_bias(stream(), ptr(logits), None if lengths is None else ptr(lengths), T, B, V, int(blank),
-                                             int(beam_width), int(top_k), float("-inf") if min_logp is None else float(min_logp),
-                                             *lm_args, int(bos), int(eos), float(alpha), float(beta), ptr(ws), nbytes, ptr(ids),
-                                             ptr(out_len), ptr(scores), ptr(ctc), ptr(lm), *_graph_args(graph), ptr(bias))
+    ids, out_len, (scores, ctc, lm, bias) = _nbest_out(B, beam_width, T, dev, 4)
+    lm_args = _NO_LM if image is None else _lm_args(image)
+    rc = _lib.lib().asr_ctc_beam_search_bias(stream(), ptr(logits), ptr(lengths), T, B, V, int(blank), int(beam_width), int(top_k),
+                                             _min_logp(min_logp), *lm_args, int(bos), int(eos), float(alpha), float(beta), ptr(ws),
+                                             nbytes, ptr(ids), ptr(out_len), ptr(scores), ptr(ctc), ptr(lm), *_graph_args(graph),
+                                             ptr(bias))
     check(rc, "asr_ctc_beam_search_bias")
     return ids, out_len, scores, ctc, lm, bias
 
@@ -896,7 +902,7 @@ def ctc_beam_stream_reset(state, B, beam_width, max_frames, with_lm, with_bias, 
     """the root beam into `state` (uint8, ctc_beam_stream_state_bytes) for every utterance, or for those with mask[b] != 0
     (mask (B) int32 on the device): asr_ctc_beam_stream_reset"""
     rc = _lib.lib().asr_ctc_beam_stream_reset(stream(), ptr(state), state.numel(), int(B), int(beam_width), int(max_frames),
-                                              int(bool(with_lm)), int(bool(with_bias)), int(bos), None if mask is None else ptr(mask))
+                                              int(bool(with_lm)), int(bool(with_bias)), int(bos), ptr(mask))
     check(rc, "asr_ctc_beam_stream_reset")
 
 
@@ -907,9 +913,8 @@ def ctc_beam_stream_advance(state, logits, lengths, blank, beam_width, top_k, fr
     Tc, B, V = logits.shape
     nbytes = _lib.lib().asr_ctc_beam_stream_workspace_bytes(Tc, B, V, int(beam_width), int(top_k))
     ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=logits.device)
-    rc = _lib.lib().asr_ctc_beam_stream_advance(stream(), ptr(logits), None if lengths is None else ptr(lengths), Tc, B, V, int(blank),
-                                                int(beam_width), int(top_k), float("-inf") if min_logp is None else float(min_logp),
-                                                *(_NO_LM if image is None else _lm_args(image)),
+    rc = _lib.lib().asr_ctc_beam_stream_advance(stream(), ptr(logits), ptr(lengths), Tc, B, V, int(blank), int(beam_width),
+                                                int(top_k), _min_logp(min_logp), *(_NO_LM if image is None else _lm_args(image)),
                                                 *(_NO_GRAPH if graph is None else _graph_args(graph)), float(alpha), float(beta),
                                                 int(frames_before), int(max_frames), ptr(state), state.numel(), ptr(ws), nbytes)
     check(rc, "asr_ctc_beam_stream_advance")
@@ -920,16 +925,15 @@ def ctc_beam_stream_result(state, B, beam_width, max_frames, blank, Lcap, image=
     lengths, scores[, ctc_scores, lm_scores[, bias_scores]]) as the one-shot search of the same variant returns them,
     frames (B) int32: the frames every utterance has consumed)"""
     dev = state.device
-    ids = torch.empty((B, beam_width, Lcap), dtype=I32, device=dev)
-    out_len = torch.empty((B, beam_width), dtype=I32, device=dev)
-    frames = torch.empty((B,), dtype=I32, device=dev)
     n = 1 if image is None and graph is None else (3 if graph is None else 4)
-    scores = tuple(torch.empty((B, beam_width), dtype=torch.float32, device=dev) for _ in range(n))
+    ids, out_len, scores = _nbest_out(B, beam_width, Lcap, dev, n)
+    frames = torch.empty((B,), dtype=I32, device=dev)
     extra = [ptr(s) for s in scores[1:]] + [None] * (4 - n)
     rc = _lib.lib().asr_ctc_beam_stream_result(stream(), *(_NO_LM if image is None else _lm_args(image)),
                                                *(_NO_GRAPH if graph is None else _graph_args(graph)), float(alpha), float(beta),
-                                               int(eos), int(B), int(beam_width), int(max_frames), int(blank), int(Lcap), ptr(state),
-                                               state.numel(), ptr(ids), ptr(out_len), ptr(scores[0]), *extra, ptr(frames))
+                                               int(eos), int(B), int(beam_width), int(max_frames), int(blank), int(Lcap),
+                                               ptr(state), state.numel(), ptr(ids), ptr(out_len), ptr(scores[0]), *extra,
+                                               ptr(frames))
     check(rc, "asr_ctc_beam_stream_result")
     return (ids, out_len) + scores, frames
 
@@ -940,18 +944,14 @@ def gram_ctc_beam_search_lm(logits, lengths, blank, beam_width, top_k, gram, ima
     unigram ids of `gram`.  The table is not checked here (asr.error.gram_beam_decode_lm does)."""
     T, B, V = logits.shape
     dev = logits.device
-    if gram.dtype != I32 or tuple(gram.shape) != (V, 2) or gram.device != dev or not gram.is_contiguous():
-        raise ValueError("gram must be a contiguous (V, 2) int32 tensor on the logits' device")
+    _check_gram(gram, V, dev)
     nbytes = _lib.lib().asr_gram_ctc_beam_lm_workspace_bytes(T, B, V, int(beam_width), int(top_k))
     ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    ids = torch.empty((B, beam_width, 2 * T), dtype=I32, device=dev)
-    out_len = torch.empty((B, beam_width), dtype=I32, device=dev)
-    scores, ctc, lm = (torch.empty((B, beam_width), dtype=torch.float32, device=dev) for _ in range(3))
-    rc = _lib.lib().asr_gram_ctc_beam_search_lm(stream(), ptr(logits), None if lengths is None else ptr(lengths), T, B, V,
-                                                int(blank), int(beam_width), int(top_k),
-                                                float("-inf") if min_logp is None else float(min_logp), ptr(gram),
-                                                *_lm_args(image), int(bos), int(eos), float(alpha), float(beta), ptr(ws), nbytes,
-                                                ptr(ids), ptr(out_len), ptr(scores), ptr(ctc), ptr(lm))
+    ids, out_len, (scores, ctc, lm) = _nbest_out(B, beam_width, 2 * T, dev, 3)
+    rc = _lib.lib().asr_gram_ctc_beam_search_lm(stream(), ptr(logits), ptr(lengths), T, B, V, int(blank), int(beam_width),
+                                                int(top_k), _min_logp(min_logp), ptr(gram), *_lm_args(image), int(bos), int(eos),
+                                                float(alpha), float(beta), ptr(ws), nbytes, ptr(ids), ptr(out_len), ptr(scores),
+                                                ptr(ctc), ptr(lm))
     check(rc, "asr_gram_ctc_beam_search_lm")
     return ids, out_len, scores, ctc, lm
 
@@ -970,7 +970,7 @@ def gram_ctc_beam_stream_reset(state, B, beam_width, max_frames, with_lm, mask=N
     """the root beam into `state` (uint8, gram_ctc_beam_stream_state_bytes) for every utterance, or for those with mask[b] != 0
     (mask (B) int32 on the device): asr_gram_ctc_beam_stream_reset"""
     rc = _lib.lib().asr_gram_ctc_beam_stream_reset(stream(), ptr(state), state.numel(), int(B), int(beam_width), int(max_frames),
-                                                   int(bool(with_lm)), None if mask is None else ptr(mask))
+                                                   int(bool(with_lm)), ptr(mask))
     check(rc, "asr_gram_ctc_beam_stream_reset")
 
 
@@ -980,13 +980,11 @@ def gram_ctc_beam_stream_advance(state, logits, lengths, blank, beam_width, top_
     int32 on the same device (not checked here); `lengths` (B) int32: the valid frames of this chunk per utterance, or None;
     `image`: the device image of an asr.lm.NGramLM over the unigram ids of `gram`"""
     Tc, B, V = logits.shape
-    if gram.dtype != I32 or tuple(gram.shape) != (V, 2) or gram.device != logits.device or not gram.is_contiguous():
-        raise ValueError("gram must be a contiguous (V, 2) int32 tensor on the logits' device")
+    _check_gram(gram, V, logits.device)
     nbytes = _lib.lib().asr_gram_ctc_beam_stream_workspace_bytes(Tc, B, V, int(beam_width), int(top_k))
     ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=logits.device)
-    rc = _lib.lib().asr_gram_ctc_beam_stream_advance(stream(), ptr(logits), None if lengths is None else ptr(lengths), Tc, B, V,
-                                                     int(blank), int(beam_width), int(top_k),
-                                                     float("-inf") if min_logp is None else float(min_logp), ptr(gram),
+    rc = _lib.lib().asr_gram_ctc_beam_stream_advance(stream(), ptr(logits), ptr(lengths), Tc, B, V, int(blank), int(beam_width),
+                                                     int(top_k), _min_logp(min_logp), ptr(gram),
                                                      *(_NO_LM if image is None else _lm_args(image)), int(bos), float(alpha),
                                                      float(beta), int(frames_before), int(max_frames), ptr(state), state.numel(),
                                                      ptr(ws), nbytes)
@@ -998,16 +996,14 @@ def gram_ctc_beam_stream_result(state, B, beam_width, max_frames, blank, Lcap, i
     Lcap), lengths, scores[, ctc_scores, lm_scores]) as the one-shot search of the same variant returns them, frames (B) int32:
     the frames every utterance has consumed)"""
     dev = state.device
-    ids = torch.empty((B, beam_width, Lcap), dtype=I32, device=dev)
-    out_len = torch.empty((B, beam_width), dtype=I32, device=dev)
-    frames = torch.empty((B,), dtype=I32, device=dev)
     n = 1 if image is None else 3
-    scores = tuple(torch.empty((B, beam_width), dtype=torch.float32, device=dev) for _ in range(n))
+    ids, out_len, scores = _nbest_out(B, beam_width, Lcap, dev, n)
+    frames = torch.empty((B,), dtype=I32, device=dev)
     extra = [ptr(s) for s in scores[1:]] + [None] * (3 - n)
     rc = _lib.lib().asr_gram_ctc_beam_stream_result(stream(), *(_NO_LM if image is None else _lm_args(image)), int(bos), int(eos),
-                                                    float(alpha), float(beta), int(B), int(beam_width), int(max_frames), int(blank),
-                                                    int(Lcap), ptr(state), state.numel(), ptr(ids), ptr(out_len), ptr(scores[0]),
-                                                    *extra, ptr(frames))
+                                                    float(alpha), float(beta), int(B), int(beam_width), int(max_frames),
+                                                    int(blank), int(Lcap), ptr(state), state.numel(), ptr(ids), ptr(out_len),
+                                                    ptr(scores[0]), *extra, ptr(frames))
     check(rc, "asr_gram_ctc_beam_stream_result")
     return (ids, out_len) + scores, frames
 

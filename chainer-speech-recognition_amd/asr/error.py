@@ -100,7 +100,51 @@ def beam_decode_biased(logits, graph, lm=None, lm_weight=0.0, length_bonus=0.0, 
                                      length_bonus, lm.bos_id, lm.eos_id if use_eos else -1, min_logp)
 
 
-class BeamStream:
+class _Stream:
+    """What ``BeamStream`` and ``GramBeamStream`` share: the dimensions and options, the device, the frame counts (`fed` on the
+    host, `frames` on the device) and the argument checks of ``reset`` and ``advance``."""
+
+    def __init__(self, B, V, max_frames, beam_width, top_k, blank, min_logp, lm, lm_weight, length_bonus, device):
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.B, self.V, self.max_frames, self.beam_width, self.top_k = int(B), int(V), int(max_frames), int(beam_width), int(top_k)
+        self.blank, self.min_logp = int(blank), min_logp
+        self.lm = None if lm is None else lm.to(self.device)
+        self.lm_weight, self.length_bonus = (float(lm_weight), float(length_bonus)) if lm is not None else (0.0, 0.0)
+        self.fed = 0                              # frames fed since the last full reset: the capacity every slot has used
+        self.frames = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
+
+    def _new_state(self, nbytes):
+        self.state = torch.zeros(max(nbytes, 1), dtype=torch.uint8, device=self.device)
+        self.reset()
+
+    def _reset_mask(self, mask):
+        """`mask` of ``reset`` as a (B) int32 device tensor; None (a full reset) also starts the frame count over"""
+        if mask is None:
+            self.fed = 0
+            return None
+        mask = torch.as_tensor(mask).to(self.device, torch.int32).contiguous()
+        if tuple(mask.shape) != (self.B,):
+            raise ValueError("mask must have one entry per utterance (%d)" % self.B)
+        return mask
+
+    def _chunk(self, logits, lengths):
+        """the arguments of ``advance``, checked -> (logits, lengths) on the device, or None for an empty chunk"""
+        if logits.dim() != 3 or logits.shape[1] != self.B or logits.shape[2] != self.V:
+            raise ValueError("the chunk must be (Tc, %d, %d), got %s" % (self.B, self.V, tuple(logits.shape)))
+        Tc = logits.shape[0]
+        if Tc == 0:
+            return None
+        if self.fed + Tc > self.max_frames:
+            raise ValueError("%d frames fed since the last full reset, %d more exceed max_frames = %d"
+                             % (self.fed, Tc, self.max_frames))
+        if lengths is not None:
+            lengths = torch.as_tensor(lengths).to(self.device, torch.int32).contiguous()
+            if tuple(lengths.shape) != (self.B,):
+                raise ValueError("lengths must have one entry per utterance (%d)" % self.B)
+        return logits.to(self.device, torch.float32).contiguous(), lengths
+
+
+class BeamStream(_Stream):
     """``beam_decode`` / ``beam_decode_lm`` (`lm`) / ``beam_decode_biased`` (`graph`, with or without `lm`) fed chunk by chunk:
     the beam of `B` utterances lives on the device between the calls.  However the frames are cut into chunks, ``result()``
     after a chunk is bit for bit what the one-shot function returns for the frames fed so far.
@@ -122,52 +166,28 @@ class BeamStream:
         if graph is not None and (graph.V != V or graph.blank != blank):
             raise ValueError("the context graph was built for %d ids with blank %d, the stream has %d with blank %d"
                              % (graph.V, graph.blank, V, blank))
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.B, self.V, self.max_frames, self.beam_width, self.top_k = int(B), int(V), int(max_frames), int(beam_width), int(top_k)
-        self.blank, self.min_logp = int(blank), min_logp
-        self.lm = None if lm is None else lm.to(self.device)
+        super().__init__(B, V, max_frames, beam_width, top_k, blank, min_logp, lm, lm_weight, length_bonus, device)
         self.graph = None if graph is None else graph.to(self.device)
-        self.lm_weight, self.length_bonus = (float(lm_weight), float(length_bonus)) if lm is not None else (0.0, 0.0)
-        nbytes = _ops.ctc_beam_stream_state_bytes(B, beam_width, max_frames, lm is not None, graph is not None)
-        self.state = torch.zeros(max(nbytes, 1), dtype=torch.uint8, device=self.device)
-        self.fed = 0                              # frames fed since the last full reset: the capacity every slot has used
-        self.frames = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
-        self.reset()
+        self._new_state(_ops.ctc_beam_stream_state_bytes(B, beam_width, max_frames, lm is not None, graph is not None))
 
     def _images(self):
         return (None if self.lm is None else self.lm.image), (None if self.graph is None else self.graph.image)
 
     def reset(self, mask=None):
         """start every utterance over, or those with mask[b] != 0 (`mask`: (B) integers, host or device)"""
-        if mask is not None:
-            mask = torch.as_tensor(mask).to(self.device, torch.int32).contiguous()
-            if tuple(mask.shape) != (self.B,):
-                raise ValueError("mask must have one entry per utterance (%d)" % self.B)
-        else:
-            self.fed = 0
         _ops.ctc_beam_stream_reset(self.state, self.B, self.beam_width, self.max_frames, self.lm is not None, self.graph is not None,
-                                   -1 if self.lm is None else self.lm.bos_id, mask)
+                                   -1 if self.lm is None else self.lm.bos_id, self._reset_mask(mask))
 
     def advance(self, logits, lengths=None):
         """consume a chunk (Tc, B, V) of f32 logits; `lengths` (B): the valid frames of this chunk per utterance (0: the
         utterance is left as it is; frames past the length are never read), None: all Tc"""
-        if logits.dim() != 3 or logits.shape[1] != self.B or logits.shape[2] != self.V:
-            raise ValueError("the chunk must be (Tc, %d, %d), got %s" % (self.B, self.V, tuple(logits.shape)))
-        Tc = logits.shape[0]
-        if Tc == 0:
+        chunk = self._chunk(logits, lengths)
+        if chunk is None:
             return
-        if self.fed + Tc > self.max_frames:
-            raise ValueError("%d frames fed since the last full reset, %d more exceed max_frames = %d"
-                             % (self.fed, Tc, self.max_frames))
-        if lengths is not None:
-            lengths = torch.as_tensor(lengths).to(self.device, torch.int32).contiguous()
-            if tuple(lengths.shape) != (self.B,):
-                raise ValueError("lengths must have one entry per utterance (%d)" % self.B)
         image, graph = self._images()
-        _ops.ctc_beam_stream_advance(self.state, logits.to(self.device, torch.float32).contiguous(), lengths, self.blank,
-                                     self.beam_width, self.top_k, self.fed, self.max_frames, image, graph, self.lm_weight,
-                                     self.length_bonus, self.min_logp)
-        self.fed += Tc
+        _ops.ctc_beam_stream_advance(self.state, chunk[0], chunk[1], self.blank, self.beam_width, self.top_k, self.fed,
+                                     self.max_frames, image, graph, self.lm_weight, self.length_bonus, self.min_logp)
+        self.fed += chunk[0].shape[0]
 
     def result(self, use_eos=True):
         """the N-best of the frames fed so far: the tuple of ``beam_decode`` (3), ``beam_decode_lm`` (5) or ``beam_decode_biased``
@@ -197,14 +217,13 @@ def check_gram_table(gram, V, blank=0):
         raise ValueError("two tokens of gram have the same spelling")
 
 
-def _gram_table_on(logits, gram, blank):
-    """`gram` (NumPy or a device tensor), checked, as a contiguous (V, 2) int32 tensor on the logits' device"""
-    V = logits.shape[2]
+def _gram_table(gram, V, blank, device):
+    """`gram` (NumPy or a device tensor), checked, as a contiguous (V, 2) int32 tensor on `device`"""
     if isinstance(gram, torch.Tensor):
         check_gram_table(gram.cpu().numpy(), V, blank)
-        return gram.to(logits.device, torch.int32).contiguous()
+        return gram.to(device, torch.int32).contiguous()
     check_gram_table(gram, V, blank)
-    return torch.from_numpy(np.ascontiguousarray(gram, np.int32)).to(logits.device)
+    return torch.from_numpy(np.ascontiguousarray(gram, np.int32)).to(device)
 
 
 def gram_beam_decode(logits, gram, beam_width=16, top_k=16, blank=0, lengths=None, min_logp=None):
@@ -217,7 +236,7 @@ def gram_beam_decode(logits, gram, beam_width=16, top_k=16, blank=0, lengths=Non
     ``compute_sequence_error(ids[:, k], lengths[:, k], t_batch, blank, None, None)`` with no retokenisation on the host.
     Candidates, `lengths` and `min_logp` as in ``beam_decode``.  ``gram_ctc_align`` on a decoded string gives its best cut.
     ``gram_beam_decode_lm`` is this search with a character n-gram language model in the ranking."""
-    table = _gram_table_on(logits, gram, blank)
+    table = _gram_table(gram, logits.shape[2], blank, logits.device)
     if lengths is not None:
         lengths = lengths.to(logits.device, torch.int32).contiguous()
     return _ops.gram_ctc_beam_search(logits.contiguous(), lengths, blank, beam_width, top_k, table, min_logp)
@@ -234,7 +253,7 @@ def gram_beam_decode_lm(logits, gram, lm, lm_weight, length_bonus, beam_width=16
     the last frame.  A bigram token adds the steps of its two characters, so log p_lm(s) does not depend on how s was cut.
     -> (ids (B, beam_width, 2T), lengths, scores (the combined score), ctc_scores, lm_scores), the last three (B, beam_width)
     f32.  Unused slots: length 0, scores and ctc_scores -inf, lm_scores 0."""
-    table = _gram_table_on(logits, gram, blank)
+    table = _gram_table(gram, logits.shape[2], blank, logits.device)
     if lm.vlm < logits.shape[2]:
         raise ValueError("the language model covers %d ids, fewer than the %d of the logits" % (lm.vlm, logits.shape[2]))
     if lengths is not None:
@@ -244,7 +263,7 @@ def gram_beam_decode_lm(logits, gram, lm, lm_weight, length_bonus, beam_width=16
                                         length_bonus, lm.bos_id, lm.eos_id if use_eos else -1, min_logp)
 
 
-class GramBeamStream:
+class GramBeamStream(_Stream):
     """``gram_beam_decode`` / ``gram_beam_decode_lm`` (`lm`) fed chunk by chunk: the beam of strings of `B` utterances lives on the
     device between the calls.  However the frames are cut into chunks, ``result()`` after a chunk is bit for bit what the one-shot
     function returns for the frames fed so far.
@@ -264,53 +283,25 @@ class GramBeamStream:
             raise ValueError("B, V and max_frames must be positive")
         if lm is not None and lm.vlm < V:
             raise ValueError("the language model covers %d ids, fewer than the %d of the logits" % (lm.vlm, V))
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.B, self.V, self.max_frames, self.beam_width, self.top_k = int(B), int(V), int(max_frames), int(beam_width), int(top_k)
-        self.blank, self.min_logp = int(blank), min_logp
-        if isinstance(gram, torch.Tensor):
-            check_gram_table(gram.cpu().numpy(), self.V, self.blank)
-            self.gram = gram.to(self.device, torch.int32).contiguous()
-        else:
-            check_gram_table(gram, self.V, self.blank)
-            self.gram = torch.from_numpy(np.ascontiguousarray(gram, np.int32)).to(self.device)
-        self.lm = None if lm is None else lm.to(self.device)
-        self.lm_weight, self.length_bonus = (float(lm_weight), float(length_bonus)) if lm is not None else (0.0, 0.0)
-        nbytes = _ops.gram_ctc_beam_stream_state_bytes(B, beam_width, max_frames, lm is not None)
-        self.state = torch.zeros(max(nbytes, 1), dtype=torch.uint8, device=self.device)
-        self.fed = 0                              # frames fed since the last full reset: the capacity every slot has used
-        self.frames = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
-        self.reset()
+        super().__init__(B, V, max_frames, beam_width, top_k, blank, min_logp, lm, lm_weight, length_bonus, device)
+        self.gram = _gram_table(gram, self.V, self.blank, self.device)
+        self._new_state(_ops.gram_ctc_beam_stream_state_bytes(B, beam_width, max_frames, lm is not None))
 
     def reset(self, mask=None):
         """start every utterance over, or those with mask[b] != 0 (`mask`: (B) integers, host or device)"""
-        if mask is not None:
-            mask = torch.as_tensor(mask).to(self.device, torch.int32).contiguous()
-            if tuple(mask.shape) != (self.B,):
-                raise ValueError("mask must have one entry per utterance (%d)" % self.B)
-        else:
-            self.fed = 0
-        _ops.gram_ctc_beam_stream_reset(self.state, self.B, self.beam_width, self.max_frames, self.lm is not None, mask)
+        _ops.gram_ctc_beam_stream_reset(self.state, self.B, self.beam_width, self.max_frames, self.lm is not None,
+                                        self._reset_mask(mask))
 
     def advance(self, logits, lengths=None):
         """consume a chunk (Tc, B, V) of f32 logits; `lengths` (B): the valid frames of this chunk per utterance (0: the
         utterance is left as it is; frames past the length are never read), None: all Tc"""
-        if logits.dim() != 3 or logits.shape[1] != self.B or logits.shape[2] != self.V:
-            raise ValueError("the chunk must be (Tc, %d, %d), got %s" % (self.B, self.V, tuple(logits.shape)))
-        Tc = logits.shape[0]
-        if Tc == 0:
+        chunk = self._chunk(logits, lengths)
+        if chunk is None:
             return
-        if self.fed + Tc > self.max_frames:
-            raise ValueError("%d frames fed since the last full reset, %d more exceed max_frames = %d"
-                             % (self.fed, Tc, self.max_frames))
-        if lengths is not None:
-            lengths = torch.as_tensor(lengths).to(self.device, torch.int32).contiguous()
-            if tuple(lengths.shape) != (self.B,):
-                raise ValueError("lengths must have one entry per utterance (%d)" % self.B)
-        _ops.gram_ctc_beam_stream_advance(self.state, logits.to(self.device, torch.float32).contiguous(), lengths, self.blank,
-                                          self.beam_width, self.top_k, self.gram, self.fed, self.max_frames,
-                                          None if self.lm is None else self.lm.image, self.lm_weight, self.length_bonus,
-                                          -1 if self.lm is None else self.lm.bos_id, self.min_logp)
-        self.fed += Tc
+        _ops.gram_ctc_beam_stream_advance(self.state, chunk[0], chunk[1], self.blank, self.beam_width, self.top_k, self.gram,
+                                          self.fed, self.max_frames, None if self.lm is None else self.lm.image, self.lm_weight,
+                                          self.length_bonus, -1 if self.lm is None else self.lm.bos_id, self.min_logp)
+        self.fed += chunk[0].shape[0]
 
     def result(self, use_eos=True):
         """the N-best strings of the frames fed so far: the tuple of ``gram_beam_decode`` (3) or ``gram_beam_decode_lm`` (5) with

@@ -88,11 +88,11 @@ def ctc_nbest_logp(x, hyps, hyp_lengths, blank_symbol, input_length=None):
 
 
 def _checked_gram_table(xs, gram, blank_symbol):
-    """`gram` through ``asr.error._gram_table_on`` (validated on the host, -> (V, 2) int32 on the logits' device) and one more
+    """`gram` through ``asr.error._gram_table`` (validated on the host, -> (V, 2) int32 on the logits' device) and one more
     check: every character a bigram row spells with has a unigram row.  A string over such a table never meets a character it
     cannot emit alone, which is the only lattice the kernels (and the float64 oracle) model."""
-    from ..error import _gram_table_on
-    table = _gram_table_on(xs, gram, blank_symbol)
+    from ..error import _gram_table
+    table = _gram_table(gram, xs.shape[2], blank_symbol, xs.device)
     g = gram.cpu().numpy() if isinstance(gram, torch.Tensor) else np.asarray(gram)
     unigrams = g[(g[:, 0] >= 0) & (g[:, 1] < 0), 0]
     spelled = g[g[:, 1] >= 0].reshape(-1)

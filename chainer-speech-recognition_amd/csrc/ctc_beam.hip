@@ -44,24 +44,25 @@ struct Ws {
 
 __host__ __device__ inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
-// K = min(top_k, V - 1): the candidates a row can have
+// the layout functions' step: `field` gets the next piece of `bytes` (rounded up to 256) at base + off
+template <class P>
+__host__ __device__ inline void take(P*& field, char* base, size_t& off, size_t bytes) {
+    field = (P*)(base + off);
+    off += align256(bytes);
+}
+
+// K = min(top_k, V - 1): the candidates a row can have.  -> the bytes; fills *ws if there is one
 __host__ __device__ inline size_t ws_layout(int T, int B, int W, int K, char* base, Ws* ws) {
+    Ws sizing;
+    Ws& w = ws ? *ws : sizing;
     const size_t rows = (size_t)T * B;
     size_t off = 0;
-    const size_t o_lse = off; off += align256(rows * 4);
-    const size_t o_lpb = off; off += align256(rows * 4);
-    const size_t o_n = off; off += align256(rows * 4);
-    const size_t o_cid = off; off += align256(rows * K * 4);
-    const size_t o_clp = off; off += align256(rows * K * 4);
-    const size_t o_node = off; off += align256(rows * W * 8);
-    if (ws) {
-        ws->lse = (float*)(base + o_lse);
-        ws->lpb = (float*)(base + o_lpb);
-        ws->n = (int*)(base + o_n);
-        ws->cid = (int*)(base + o_cid);
-        ws->clp = (float*)(base + o_clp);
-        ws->node = (int2*)(base + o_node);
-    }
+    take(w.lse, base, off, rows * 4);
+    take(w.lpb, base, off, rows * 4);
+    take(w.n, base, off, rows * 4);
+    take(w.cid, base, off, rows * K * 4);
+    take(w.clp, base, off, rows * K * 4);
+    take(w.node, base, off, rows * W * 8);
     return off;
 }
 
@@ -244,6 +245,16 @@ __device__ inline int block_excl_scan(int v, int* wsum, int* total) {
     return before_me + incl - v;
 }
 
+// the rank of entry tid among v[0, n): score descending, ties to the lower index
+__device__ inline int rank_of(const float* v, int n, float f, int tid) {
+    int rank = 0;
+    for (int u = 0; u < n; ++u) {
+        const float g2 = v[u];
+        rank += g2 > f || (g2 == f && u < tid);
+    }
+    return rank;
+}
+
 // The language-model side of the fused search (asr_ctc_beam_search_lm): beam_kernel<true, .> ranks by
 // total + (alpha * lm + beta * len); beam_kernel<false, .> carries none of this and is the unfused search as it was.
 template <bool LM>
@@ -322,40 +333,31 @@ struct State {
 
 // F = max_frames; variant = with_lm | with_bias << 1
 __host__ __device__ inline size_t state_layout(int B, int W, int F, int variant, char* base, State* s) {
+    State sizing;
+    State& w = s ? *s : sizing;
+    w = State{};                                     // the fields of a side the variant does not have stay null
     const size_t slots = (size_t)B * W;
     size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return base + o; };
-    char* hdr = take((size_t)B * HDR_WORDS * 4);
-    char* pb = take(slots * 4);
-    char* pnb = take(slots * 4);
-    char* hash = take(slots * 8);
-    char* phash = take(slots * 8);
-    char* len = take(slots * 4);
-    char* last = take(slots * 4);
-    char* plast = take(slots * 4);
-    char* node = take(slots * 4);
-    char *lm = nullptr, *c0 = nullptr, *c1 = nullptr, *c2 = nullptr, *open = nullptr, *state = nullptr;
-    if (variant & 1) { lm = take(slots * 4); c0 = take(slots * 4); c1 = take(slots * 4); c2 = take(slots * 4); }
-    if (variant & 2) { open = take(slots * 4); state = take(slots * 4); }
-    char* table = take(slots * F * 8);
-    if (s) {
-        s->hdr = (int*)hdr;
-        s->pb = (float*)pb;
-        s->pnb = (float*)pnb;
-        s->hash = (unsigned long long*)hash;
-        s->phash = (unsigned long long*)phash;
-        s->len = (int*)len;
-        s->last = (int*)last;
-        s->plast = (int*)plast;
-        s->node = (int*)node;
-        s->lm = (float*)lm;
-        s->c0 = (int*)c0;
-        s->c1 = (int*)c1;
-        s->c2 = (int*)c2;
-        s->open = (float*)open;
-        s->state = (int*)state;
-        s->table = (int2*)table;
+    take(w.hdr, base, off, (size_t)B * HDR_WORDS * 4);
+    take(w.pb, base, off, slots * 4);
+    take(w.pnb, base, off, slots * 4);
+    take(w.hash, base, off, slots * 8);
+    take(w.phash, base, off, slots * 8);
+    take(w.len, base, off, slots * 4);
+    take(w.last, base, off, slots * 4);
+    take(w.plast, base, off, slots * 4);
+    take(w.node, base, off, slots * 4);
+    if (variant & 1) {
+        take(w.lm, base, off, slots * 4);
+        take(w.c0, base, off, slots * 4);
+        take(w.c1, base, off, slots * 4);
+        take(w.c2, base, off, slots * 4);
     }
+    if (variant & 2) {
+        take(w.open, base, off, slots * 4);
+        take(w.state, base, off, slots * 4);
+    }
+    take(w.table, base, off, slots * F * 8);
     return off;
 }
 
@@ -374,6 +376,64 @@ struct Strm<ONESHOT> {};
 // the header of utterance b was written for these dimensions and this variant
 __device__ inline bool state_matches(const int* h, int B, int W, int F, int variant) {
     return h[H_MAGIC] == STATE_MAGIC && h[H_B] == B && h[H_W] == W && h[H_F] == F && h[H_VARIANT] == variant;
+}
+
+// What a streaming kernel reads from the header of utterance b (hdr: that utterance's words) before it loads the beam: the beam's
+// size m, the frames consumed so far f0 and the frames this call may consume len_b, all clamped so that a header other code
+// wrote into cannot lead outside the state; a header that does not match gives m = 0.  ADVANCE: len_b <= 0 means there is
+// nothing to consume, and the caller returns without touching the state.  RESULT: len_b = 0, and out_frames[b] = f0 or -1.
+// Returns the utterance's prefix table: `per_frame` nodes per frame and beam slot (1, Gram-CTC 2).
+struct StrmHead {
+    int2* nodes;
+    int m, f0, len_b;
+};
+
+template <int MODE>
+__device__ inline StrmHead stream_begin(const int* hdr, int2* table, int per_frame, int B, int W, int F, int variant,
+                                        int32_t* out_frames, int b, int len_b) {
+    const bool ok = state_matches(hdr, B, W, F, variant);
+    StrmHead r;
+    r.nodes = table + (size_t)b * per_frame * F * W;
+    r.m = ok ? min(max(hdr[H_M], 0), W) : 0;
+    r.f0 = ok ? min(max(hdr[H_FRAMES], 0), F) : 0;
+    if constexpr (MODE == ADVANCE) {
+        r.len_b = ok ? min(len_b, F - r.f0) : 0;            // no node beyond the table, whatever the host says
+    } else {
+        r.len_b = 0;
+        if (threadIdx.x == 0) out_frames[b] = ok ? r.f0 : -1;
+    }
+    return r;
+}
+
+// ADVANCE's last step: the beam's size and the frames consumed go back into the header
+__device__ inline void stream_end(int* hdr, int m, int frames) {
+    if (threadIdx.x == 0) {
+        hdr[H_M] = m;
+        hdr[H_FRAMES] = frames;
+    }
+}
+
+// The two halves of every N-best tail; the caller's own writes for the slot sit between them.
+// fill_blank: in the utterance's ids, rows of `pitch`, the positions from a hypothesis' length on get blank; row i < m is beam slot
+// order[i] (slot i with no order), the rows from m on are all blank.
+__device__ inline void fill_blank(int32_t* ids, int pitch, int W, int m, const int* len, const int* order, int blank) {
+    for (size_t k = threadIdx.x; k < (size_t)W * pitch; k += THREADS) {
+        const int i = (int)(k / pitch), p = (int)(k - (size_t)i * pitch);
+        if (p >= (i < m ? len[order ? order[i] : i] : 0)) ids[k] = blank;
+    }
+}
+
+// walk_chain: one hypothesis of length L walks its prefix table chain from node nd back to the root and writes its row of ids.
+// RESULT: a hypothesis longer than the row is cut (its length is reported in full), and a chain that leaves the table's table_n
+// nodes (a state that other code wrote into) ends there.
+template <int MODE>
+__device__ inline void walk_chain(int32_t* row, int pitch, int L, int nd, const int2* nodes, int table_n) {
+    for (int p = L - 1; p >= 0; --p) {
+        if (MODE == RESULT && (unsigned)nd >= (unsigned)table_n) break;
+        const int2 e = nodes[nd];
+        if (MODE != RESULT || p < pitch) row[p] = e.y;
+        nd = e.x;
+    }
 }
 
 // ADVANCE: x, lengths and T are the chunk's (Tc frames, lengths[b] of them valid), ws holds the chunk's candidate rows and the
@@ -402,18 +462,10 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
     int2* nodes;
     int cur = 0, m = 1, f0 = 0;                        // f0: the frames this utterance consumed before this call
     if constexpr (MODE != ONESHOT) {
-        const int* h = sz.s.hdr + (size_t)b * HDR_WORDS;
-        const bool ok = state_matches(h, B, W, sz.max_frames, sz.variant);
-        nodes = sz.s.table + (size_t)b * sz.max_frames * W;
-        m = ok ? min(max(h[H_M], 0), W) : 0;
-        f0 = ok ? min(max(h[H_FRAMES], 0), sz.max_frames) : 0;
-        if constexpr (MODE == ADVANCE) {
-            len_b = ok ? min(len_b, sz.max_frames - f0) : 0;       // no node beyond the table, whatever the host says
-            if (len_b <= 0) return;                                  // nothing to consume: the state is not touched
-        } else {
-            len_b = 0;
-            if (tid == 0) sz.out_frames[b] = ok ? f0 : -1;
-        }
+        const StrmHead hd = stream_begin<MODE>(sz.s.hdr + (size_t)b * HDR_WORDS, sz.s.table, 1, B, W, sz.max_frames, sz.variant,
+                                               sz.out_frames, b, len_b);
+        nodes = hd.nodes; m = hd.m; f0 = hd.f0; len_b = hd.len_b;
+        if (MODE == ADVANCE && len_b <= 0) return;     // nothing to consume: the state is not touched
         if (tid < m) {
             const size_t i = (size_t)b * W + tid;
             const int last = sz.s.last[i], len = sz.s.len[i];
@@ -580,6 +632,8 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
             if constexpr (BIAS) tot[i] += bl.open[cur][i];
         }
         __syncthreads();
+        // (D and E stand in both kernels, line for line the same: as one __device__ function the pass loop was laid out differently
+        // and every frame loop ran 0.5 - 1.7 % slower; a change to one copy belongs in the other too)
         // D: radix select of the W best valid entries, 8 bits of the key per pass from the top: key >> sh > tau >> sh, and the
         // first `need` (canonical order) with key >> sh == tau >> sh.  It stops early once the boundary digit's entries are all kept.
         const int chunk = (E + THREADS - 1) / THREADS, e0 = min(E, tid * chunk), e1 = min(E, e0 + chunk);
@@ -668,11 +722,7 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
                 // a surviving extension looks its step up again, for the delta and the next state; the loads fly during the count
                 if (e >= m) cs = ctx::step_issue(bz.g, bl.state[cur][(e - m) / n], cid[(e - m) % n]);
             }
-            int rank = 0;
-            for (int u = 0; u < M; ++u) {
-                const float g2 = sv_tot[u];
-                rank += g2 > f || (g2 == f && u < tid);
-            }
+            const int rank = rank_of(sv_tot, M, f, tid);
             if (e < m) {
                 nx.pb[rank] = spb[e];
                 nx.pnb[rank] = spnb[e];
@@ -754,18 +804,13 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
                 sz.s.state[i] = bl.state[cur][tid];
             }
         }
-        if (tid == 0) {
-            int* h = sz.s.hdr + (size_t)b * HDR_WORDS;
-            h[H_M] = m;
-            h[H_FRAMES] = f0 + len_b;
-        }
+        stream_end(sz.s.hdr + (size_t)b * HDR_WORDS, m, f0 + len_b);
         return;
     }
-    // RESULT: a hypothesis longer than the row pitch is cut (its length is reported in full), and a chain that leaves the table
-    // (a state that other code wrote into) ends there
+    // the N-best, sorted by score: the ids by fill_blank and walk_chain (RESULT: a hypothesis longer than the row pitch is cut there, and its
+    // length is reported in full)
     int table_n = 0;
     if constexpr (MODE == RESULT) table_n = sz.max_frames * W;
-    // the N-best, sorted by score: ids padded with blank, then each hypothesis walks its prefix table chain back to the root
     int32_t* ids = out_ids + (size_t)b * W * T;
     if constexpr (LM || BIAS) {
         // the end terms, then the final order: score descending, ties to the earlier slot
@@ -790,11 +835,7 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
         }
         __syncthreads();
         if (tid < m) {
-            int rank = 0;
-            for (int u = 0; u < m; ++u) {
-                const float g2 = sv_tot[u];
-                rank += g2 > sc || (g2 == sc && u < tid);
-            }
+            const int rank = rank_of(sv_tot, m, sc, tid);
             sv_pos[rank] = tid;
             out_score[b * W + rank] = sc;
             o_ctc[b * W + rank] = ctc;
@@ -802,21 +843,12 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
             if constexpr (BIAS) bz.out_bias[b * W + rank] = bv;
         }
         __syncthreads();
-        for (size_t k = tid; k < (size_t)W * T; k += THREADS) {
-            const int i = (int)(k / T), p = (int)(k - (size_t)i * T);
-            if (p >= (i < m ? o.len[sv_pos[i]] : 0)) ids[k] = blank;
-        }
+        fill_blank(ids, T, W, m, o.len, sv_pos, blank);
         if (tid < W) {
             if (tid < m) {
                 const int h = sv_pos[tid], L = o.len[h];
                 out_len[b * W + tid] = L;
-                int nd = o.node[h];
-                for (int p = L - 1; p >= 0; --p) {
-                    if (MODE == RESULT && (unsigned)nd >= (unsigned)table_n) break;
-                    const int2 e = nodes[nd];
-                    if (MODE != RESULT || p < T) ids[(size_t)tid * T + p] = e.y;
-                    nd = e.x;
-                }
+                walk_chain<MODE>(ids + (size_t)tid * T, T, L, o.node[h], nodes, table_n);
             } else {
                 out_len[b * W + tid] = 0;
                 out_score[b * W + tid] = -INFINITY;
@@ -827,27 +859,42 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
         }
         return;
     }
-    for (size_t k = tid; k < (size_t)W * T; k += THREADS) {
-        const int i = (int)(k / T), p = (int)(k - (size_t)i * T);
-        if (p >= (i < m ? o.len[i] : 0)) ids[k] = blank;
-    }
+    fill_blank(ids, T, W, m, o.len, nullptr, blank);
     if (tid < W) {
         if (tid < m) {
             const int L = o.len[tid];
             out_len[b * W + tid] = L;
             out_score[b * W + tid] = lae(o.pb[tid], o.pnb[tid]);
-            int nd = o.node[tid];
-            for (int p = L - 1; p >= 0; --p) {
-                if (MODE == RESULT && (unsigned)nd >= (unsigned)table_n) break;
-                const int2 e = nodes[nd];
-                if (MODE != RESULT || p < T) ids[(size_t)tid * T + p] = e.y;
-                nd = e.x;
-            }
+            walk_chain<MODE>(ids + (size_t)tid * T, T, L, o.node[tid], nodes, table_n);
         } else {
             out_len[b * W + tid] = 0;
             out_score[b * W + tid] = -INFINITY;
         }
     }
+}
+
+// ---------------------------------------------------------------------------------------------- what the entries share
+// The one-shot entries' common checks: BAD_ARG for a null pointer, a dimension or a blank out of range, else UNSUPPORTED beyond
+// the kernels' limits (`per_frame` prefix table nodes per frame and beam slot: 1, Gram-CTC 2), else OK.  An entry returns a
+// BAD_ARG at once, but an UNSUPPORTED only after its own argument checks and the model's and the graph's codes.
+static int oneshot_check(const float* logits, const void* workspace, const int32_t* out_ids, const int32_t* out_len,
+                         const float* out_score, int T, int B, int V, int blank, int beam_width, int top_k, int per_frame) {
+    if (!logits || !workspace || !out_ids || !out_len || !out_score || T <= 0 || B <= 0 || V <= 0 || blank < 0 || blank >= V ||
+        beam_width <= 0 || top_k <= 0)
+        return ASR_ERR_BAD_ARG;
+    if (beam_width > MAX_BEAM || top_k > MAX_TOPK || beam_width * top_k > MAX_EXT) return ASR_ERR_UNSUPPORTED;
+    if ((long long)per_frame * T * beam_width > 0x7fffffffLL) return ASR_ERR_UNSUPPORTED;    // prefix table node ids are int32
+    return ASR_OK;
+}
+
+// cand_kernel over the (T, B, V) logits into ws
+static int launch_cand(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank, int K,
+                       float min_logp, const Ws& ws) {
+    const long long rows = (long long)T * B;
+    hipLaunchKernelGGL(cand_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, lengths, T, B, V,
+                       blank, K, min_logp, ws);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
 }
 
 }  // namespace beam
@@ -864,19 +911,14 @@ extern "C" size_t asr_ctc_beam_workspace_bytes(int T, int B, int V, int beam_wid
 extern "C" int asr_ctc_beam_search(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank,
                                    int beam_width, int top_k, float min_logp, void* workspace, size_t workspace_bytes,
                                    int32_t* out_ids, int32_t* out_len, float* out_score) {
-    if (!logits || !workspace || !out_ids || !out_len || !out_score || T <= 0 || B <= 0 || V <= 0 || blank < 0 || blank >= V ||
-        beam_width <= 0 || top_k <= 0)
-        return ASR_ERR_BAD_ARG;
-    if (beam_width > MAX_BEAM || top_k > MAX_TOPK || beam_width * top_k > MAX_EXT) return ASR_ERR_UNSUPPORTED;
-    if ((long long)T * beam_width > 0x7fffffffLL) return ASR_ERR_UNSUPPORTED;     // prefix table node ids are int32
+    int rc = oneshot_check(logits, workspace, out_ids, out_len, out_score, T, B, V, blank, beam_width, top_k, 1);
+    if (rc != ASR_OK) return rc;
     const int K = min(top_k, V - 1);
     Ws ws;
     const size_t need = ws_layout(T, B, beam_width, K, (char*)workspace, &ws);
     if (workspace_bytes < need) return ASR_ERR_WORKSPACE;
-    const long long rows = (long long)T * B;
-    hipLaunchKernelGGL(cand_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, lengths, T, B, V,
-                       blank, K, min_logp, ws);
-    ASR_LAUNCH_CHECK();
+    rc = launch_cand(stream, logits, lengths, T, B, V, blank, K, min_logp, ws);
+    if (rc != ASR_OK) return rc;
     hipLaunchKernelGGL((beam_kernel<false, false, ONESHOT>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V,
                        beam_width, K, blank, ws, out_ids, out_len, out_score, Fuse<false>{}, Bias<false>{}, Strm<ONESHOT>{});
     ASR_LAUNCH_CHECK();
@@ -929,6 +971,16 @@ static int make_lm(const float* uni, int vlm, const int32_t* keys, const float* 
     return ASR_OK;
 }
 
+// the search's side of the model arguments (fz->lm is make_lm's); a negative bos / eos means none
+static void fill_fuse(Fuse<true>* fz, int bos, int eos, float alpha, float beta, float* out_ctc, float* out_lm) {
+    fz->bos = bos < 0 ? -1 : bos;
+    fz->eos = eos < 0 ? -1 : eos;
+    fz->alpha = alpha;
+    fz->beta = beta;
+    fz->out_ctc = out_ctc;
+    fz->out_lm = out_lm;
+}
+
 }  // namespace beam
 }  // namespace asr
 
@@ -954,28 +1006,19 @@ extern "C" int asr_ctc_beam_search_lm(void* stream, const float* logits, const i
                                       const float* vals, int slots, int max_probe, int order, int bos, int eos, float alpha,
                                       float beta, void* workspace, size_t workspace_bytes, int32_t* out_ids, int32_t* out_len,
                                       float* out_score, float* out_ctc, float* out_lm) {
-    if (!logits || !workspace || !out_ids || !out_len || !out_score || !out_ctc || !out_lm || T <= 0 || B <= 0 || V <= 0 ||
-        blank < 0 || blank >= V || beam_width <= 0 || top_k <= 0 || vlm < V || bos >= vlm || eos >= vlm)
-        return ASR_ERR_BAD_ARG;
+    const int lim = oneshot_check(logits, workspace, out_ids, out_len, out_score, T, B, V, blank, beam_width, top_k, 1);
+    if (lim == ASR_ERR_BAD_ARG || !out_ctc || !out_lm || vlm < V || bos >= vlm || eos >= vlm) return ASR_ERR_BAD_ARG;
     Fuse<true> fz;
-    const int rc = make_lm(uni, vlm, keys, vals, slots, max_probe, order, &fz.lm);
+    int rc = make_lm(uni, vlm, keys, vals, slots, max_probe, order, &fz.lm);
     if (rc != ASR_OK) return rc;
-    if (beam_width > MAX_BEAM || top_k > MAX_TOPK || beam_width * top_k > MAX_EXT) return ASR_ERR_UNSUPPORTED;
-    if ((long long)T * beam_width > 0x7fffffffLL) return ASR_ERR_UNSUPPORTED;
+    if (lim != ASR_OK) return lim;
     const int K = min(top_k, V - 1);
     Ws ws;
     const size_t need = ws_layout(T, B, beam_width, K, (char*)workspace, &ws);
     if (workspace_bytes < need) return ASR_ERR_WORKSPACE;
-    fz.bos = bos < 0 ? -1 : bos;
-    fz.eos = eos < 0 ? -1 : eos;
-    fz.alpha = alpha;
-    fz.beta = beta;
-    fz.out_ctc = out_ctc;
-    fz.out_lm = out_lm;
-    const long long rows = (long long)T * B;
-    hipLaunchKernelGGL(cand_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, lengths, T, B, V,
-                       blank, K, min_logp, ws);
-    ASR_LAUNCH_CHECK();
+    fill_fuse(&fz, bos, eos, alpha, beta, out_ctc, out_lm);
+    rc = launch_cand(stream, logits, lengths, T, B, V, blank, K, min_logp, ws);
+    if (rc != ASR_OK) return rc;
     hipLaunchKernelGGL((beam_kernel<true, false, ONESHOT>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V,
                        beam_width, K, blank, ws, out_ids, out_len, out_score, fz, Bias<false>{}, Strm<ONESHOT>{});
     ASR_LAUNCH_CHECK();
@@ -1055,21 +1098,20 @@ extern "C" int asr_ctc_beam_search_bias(void* stream, const float* logits, const
                                         float* out_score, float* out_ctc, float* out_lm, const int32_t* g_keys,
                                         const int32_t* g_vals, int g_slots, int g_max_probe, const float* g_ret, int g_n_states,
                                         float* out_bias) {
-    if (!logits || !workspace || !out_ids || !out_len || !out_score || !out_ctc || !out_lm || !out_bias || T <= 0 || B <= 0 ||
-        V <= 0 || blank < 0 || blank >= V || beam_width <= 0 || top_k <= 0)
-        return ASR_ERR_BAD_ARG;
+    const int lim = oneshot_check(logits, workspace, out_ids, out_len, out_score, T, B, V, blank, beam_width, top_k, 1);
+    if (lim == ASR_ERR_BAD_ARG || !out_ctc || !out_lm || !out_bias) return ASR_ERR_BAD_ARG;
     const bool with_lm = uni != nullptr;
     Fuse<true> fz;
+    int rc;
     if (with_lm) {
         if (vlm < V || bos >= vlm || eos >= vlm) return ASR_ERR_BAD_ARG;
-        const int rc = make_lm(uni, vlm, keys, vals, slots, max_probe, order, &fz.lm);
+        rc = make_lm(uni, vlm, keys, vals, slots, max_probe, order, &fz.lm);
         if (rc != ASR_OK) return rc;
     }
     Bias<true> bz;
-    const int rc = make_graph(g_keys, g_vals, g_slots, g_max_probe, g_ret, g_n_states, &bz.g);
+    rc = make_graph(g_keys, g_vals, g_slots, g_max_probe, g_ret, g_n_states, &bz.g);
     if (rc != ASR_OK) return rc;
-    if (beam_width > MAX_BEAM || top_k > MAX_TOPK || beam_width * top_k > MAX_EXT) return ASR_ERR_UNSUPPORTED;
-    if ((long long)T * beam_width > 0x7fffffffLL) return ASR_ERR_UNSUPPORTED;
+    if (lim != ASR_OK) return lim;
     const int K = min(top_k, V - 1);
     Ws ws;
     const size_t need = ws_layout(T, B, beam_width, K, (char*)workspace, &ws);
@@ -1077,17 +1119,10 @@ extern "C" int asr_ctc_beam_search_bias(void* stream, const float* logits, const
     bz.out_ctc = out_ctc;
     bz.out_lm = out_lm;
     bz.out_bias = out_bias;
-    const long long rows = (long long)T * B;
-    hipLaunchKernelGGL(cand_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, lengths, T, B, V,
-                       blank, K, min_logp, ws);
-    ASR_LAUNCH_CHECK();
+    rc = launch_cand(stream, logits, lengths, T, B, V, blank, K, min_logp, ws);
+    if (rc != ASR_OK) return rc;
     if (with_lm) {
-        fz.bos = bos < 0 ? -1 : bos;
-        fz.eos = eos < 0 ? -1 : eos;
-        fz.alpha = alpha;
-        fz.beta = beta;
-        fz.out_ctc = out_ctc;
-        fz.out_lm = out_lm;
+        fill_fuse(&fz, bos, eos, alpha, beta, out_ctc, out_lm);
         hipLaunchKernelGGL((beam_kernel<true, true, ONESHOT>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V,
                            beam_width, K, blank, ws, out_ids, out_len, out_score, fz, bz, Strm<ONESHOT>{});
     } else {
@@ -1161,12 +1196,26 @@ static void launch_stream_variant(int variant, hipStream_t st, const float* x, c
     }
 }
 
+// the CTC stream's variant word (State's header, state_layout)
+static int ctc_variant(bool with_lm, bool with_bias) { return (with_lm ? 1 : 0) | (with_bias ? 2 : 0); }
+
+// The dimension and limit part of every streaming entry of both searches: BAD_ARG without a state (`has_state`) or for a
+// dimension that is not positive, else UNSUPPORTED beyond the kernels' limits (`per_frame` prefix table nodes per frame and beam
+// slot: 1, Gram-CTC 2), else OK.  As with oneshot_check, an UNSUPPORTED waits for the model's and the graph's codes.
+static int stream_dims(bool has_state, int B, int W, int F, int per_frame) {
+    if (!has_state || B <= 0 || W <= 0 || F <= 0) return ASR_ERR_BAD_ARG;
+    if (W > MAX_BEAM) return ASR_ERR_UNSUPPORTED;
+    if ((long long)per_frame * F * W > 0x7fffffffLL) return ASR_ERR_UNSUPPORTED;      // prefix table node ids are int32
+    return ASR_OK;
+}
+
 // the checks on dimensions, state size and the model / graph arguments that advance and result share; fills fz.lm, bz.g, sz->s
 static int stream_open(int B, int W, int F, const float* uni, int vlm, const int32_t* keys, const float* vals, int slots,
                        int max_probe, int order, const int32_t* g_keys, const int32_t* g_vals, int g_slots, int g_max_probe,
                        const float* g_ret, int g_n_states, void* state, size_t state_bytes, Fuse<true>* fz, Bias<true>* bz,
                        StrmArgs* sz) {
-    if (!state || B <= 0 || W <= 0 || F <= 0) return ASR_ERR_BAD_ARG;
+    const int lim = stream_dims(state != nullptr, B, W, F, 1);
+    if (lim == ASR_ERR_BAD_ARG) return lim;
     const bool with_lm = uni != nullptr, with_bias = g_ret != nullptr;
     if (with_lm) {
         const int rc = make_lm(uni, vlm, keys, vals, slots, max_probe, order, &fz->lm);
@@ -1178,10 +1227,9 @@ static int stream_open(int B, int W, int F, const float* uni, int vlm, const int
     } else if (g_keys || g_vals || g_slots != 0 || g_n_states != 0) {
         return ASR_ERR_BAD_ARG;                      // a graph without its ret: section 22's check, not "no graph"
     }
-    if (W > MAX_BEAM) return ASR_ERR_UNSUPPORTED;
-    if ((long long)F * W > 0x7fffffffLL) return ASR_ERR_UNSUPPORTED;      // prefix table node ids are int32
+    if (lim != ASR_OK) return lim;
     sz->max_frames = F;
-    sz->variant = (with_lm ? 1 : 0) | (with_bias ? 2 : 0);
+    sz->variant = ctc_variant(with_lm, with_bias);
     sz->out_frames = nullptr;
     if (state_bytes < state_layout(B, W, F, sz->variant, (char*)state, &sz->s)) return ASR_ERR_WORKSPACE;
     return ASR_OK;
@@ -1191,8 +1239,8 @@ static int stream_open(int B, int W, int F, const float* uni, int vlm, const int
 }  // namespace asr
 
 extern "C" size_t asr_ctc_beam_stream_state_bytes(int B, int beam_width, int max_frames, int with_lm, int with_bias) {
-    if (B <= 0 || beam_width <= 0 || max_frames <= 0) return 0;
-    return state_layout(B, beam_width, max_frames, (with_lm ? 1 : 0) | (with_bias ? 2 : 0), nullptr, nullptr);
+    if (stream_dims(true, B, beam_width, max_frames, 1) == ASR_ERR_BAD_ARG) return 0;
+    return state_layout(B, beam_width, max_frames, ctc_variant(with_lm, with_bias), nullptr, nullptr);
 }
 
 extern "C" size_t asr_ctc_beam_stream_workspace_bytes(int Tc, int B, int V, int beam_width, int top_k) {
@@ -1202,9 +1250,9 @@ extern "C" size_t asr_ctc_beam_stream_workspace_bytes(int Tc, int B, int V, int 
 
 extern "C" int asr_ctc_beam_stream_reset(void* stream, void* state, size_t state_bytes, int B, int beam_width, int max_frames,
                                          int with_lm, int with_bias, int bos, const int32_t* mask) {
-    if (!state || B <= 0 || beam_width <= 0 || max_frames <= 0) return ASR_ERR_BAD_ARG;
-    if (beam_width > MAX_BEAM || (long long)max_frames * beam_width > 0x7fffffffLL) return ASR_ERR_UNSUPPORTED;
-    const int variant = (with_lm ? 1 : 0) | (with_bias ? 2 : 0);
+    const int rc = stream_dims(state != nullptr, B, beam_width, max_frames, 1);
+    if (rc != ASR_OK) return rc;
+    const int variant = ctc_variant(with_lm, with_bias);
     State s;
     if (state_bytes < state_layout(B, beam_width, max_frames, variant, (char*)state, &s)) return ASR_ERR_WORKSPACE;
     hipLaunchKernelGGL(stream_reset_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, s, B, beam_width,
@@ -1226,21 +1274,17 @@ extern "C" int asr_ctc_beam_stream_advance(void* stream, const float* logits, co
     Fuse<true> fz{};
     Bias<true> bz{};
     Strm<ADVANCE> sz{};
-    const int rc = stream_open(B, beam_width, max_frames, uni, vlm, keys, vals, slots, max_probe, order, g_keys, g_vals, g_slots,
-                               g_max_probe, g_ret, g_n_states, state, state_bytes, &fz, &bz, &sz);
+    int rc = stream_open(B, beam_width, max_frames, uni, vlm, keys, vals, slots, max_probe, order, g_keys, g_vals, g_slots,
+                         g_max_probe, g_ret, g_n_states, state, state_bytes, &fz, &bz, &sz);
     if (rc != ASR_OK) return rc;
     if (top_k > MAX_TOPK || beam_width * top_k > MAX_EXT) return ASR_ERR_UNSUPPORTED;
     if ((long long)frames_before + Tc > max_frames) return ASR_ERR_UNSUPPORTED;
     const int K = min(top_k, V - 1);
     Ws ws;
     if (workspace_bytes < ws_layout(Tc, B, 0, K, (char*)workspace, &ws)) return ASR_ERR_WORKSPACE;
-    fz.bos = fz.eos = -1;                            // the contexts start in reset and end in result
-    fz.alpha = alpha;
-    fz.beta = beta;
-    const long long rows = (long long)Tc * B;
-    hipLaunchKernelGGL(cand_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, lengths, Tc, B, V,
-                       blank, K, min_logp, ws);
-    ASR_LAUNCH_CHECK();
+    fill_fuse(&fz, -1, -1, alpha, beta, nullptr, nullptr);       // the contexts start in reset and end in result
+    rc = launch_cand(stream, logits, lengths, Tc, B, V, blank, K, min_logp, ws);
+    if (rc != ASR_OK) return rc;
     launch_stream_variant<ADVANCE>(sz.variant, (hipStream_t)stream, logits, lengths, Tc, B, V, beam_width, K, blank, ws, nullptr,
                                    nullptr, nullptr, fz, bz, sz);
     ASR_LAUNCH_CHECK();
@@ -1264,12 +1308,9 @@ extern "C" int asr_ctc_beam_stream_result(void* stream, const float* uni, int vl
                                g_max_probe, g_ret, g_n_states, const_cast<void*>(state), state_bytes, &fz, &bz, &sz);
     if (rc != ASR_OK) return rc;
     sz.out_frames = out_frames;
-    fz.bos = -1;
-    fz.eos = eos < 0 ? -1 : eos;
-    fz.alpha = alpha;
-    fz.beta = beta;
-    fz.out_ctc = bz.out_ctc = out_ctc;
-    fz.out_lm = bz.out_lm = out_lm;
+    fill_fuse(&fz, -1, eos, alpha, beta, out_ctc, out_lm);
+    bz.out_ctc = out_ctc;
+    bz.out_lm = out_lm;
     bz.out_bias = out_bias;
     launch_stream_variant<RESULT>(sz.variant, (hipStream_t)stream, nullptr, nullptr, Lcap, B, 0, beam_width, 0, blank, Ws{}, out_ids,
                                   out_len, out_score, fz, bz, sz);
@@ -1356,43 +1397,27 @@ struct GState {
 
 // F = max_frames; variant = GRAM_VARIANT | with_lm
 __host__ __device__ inline size_t gram_state_layout(int B, int W, int F, int variant, char* base, GState* s) {
+    GState sizing;
+    GState& w = s ? *s : sizing;
+    w = GState{};                                    // lm stays null without a model
     const size_t slots = (size_t)B * W;
     size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return base + o; };
-    char* hdr = take((size_t)B * HDR_WORDS * 4);
-    char* pb = take(slots * 4);
-    char* pu = take(slots * 4);
-    char* pg = take(slots * 4);
-    char* h0 = take(slots * 8);
-    char* h1 = take(slots * 8);
-    char* h2 = take(slots * 8);
-    char* len = take(slots * 4);
-    char* c1 = take(slots * 4);
-    char* c2 = take(slots * 4);
-    char* c3 = take(slots * 4);
-    char* utok = take(slots * 4);
-    char* gtok = take(slots * 4);
-    char* node = take(slots * 4);
-    char* lm = (variant & 1) ? take(slots * 4) : nullptr;
-    char* table = take(slots * F * 16);
-    if (s) {
-        s->hdr = (int*)hdr;
-        s->pb = (float*)pb;
-        s->pu = (float*)pu;
-        s->pg = (float*)pg;
-        s->h0 = (unsigned long long*)h0;
-        s->h1 = (unsigned long long*)h1;
-        s->h2 = (unsigned long long*)h2;
-        s->len = (int*)len;
-        s->c1 = (int*)c1;
-        s->c2 = (int*)c2;
-        s->c3 = (int*)c3;
-        s->utok = (int*)utok;
-        s->gtok = (int*)gtok;
-        s->node = (int*)node;
-        s->lm = (float*)lm;
-        s->table = (int2*)table;
-    }
+    take(w.hdr, base, off, (size_t)B * HDR_WORDS * 4);
+    take(w.pb, base, off, slots * 4);
+    take(w.pu, base, off, slots * 4);
+    take(w.pg, base, off, slots * 4);
+    take(w.h0, base, off, slots * 8);
+    take(w.h1, base, off, slots * 8);
+    take(w.h2, base, off, slots * 8);
+    take(w.len, base, off, slots * 4);
+    take(w.c1, base, off, slots * 4);
+    take(w.c2, base, off, slots * 4);
+    take(w.c3, base, off, slots * 4);
+    take(w.utok, base, off, slots * 4);
+    take(w.gtok, base, off, slots * 4);
+    take(w.node, base, off, slots * 4);
+    if (variant & 1) take(w.lm, base, off, slots * 4);
+    take(w.table, base, off, slots * F * 16);
     return off;
 }
 
@@ -1438,18 +1463,10 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
     int2* nodes;
     int cur = 0, m = 1, f0 = 0;                        // f0: the frames this utterance consumed before this call
     if constexpr (MODE != ONESHOT) {
-        const int* h = sz.s.hdr + (size_t)b * HDR_WORDS;
-        const bool ok = state_matches(h, B, W, sz.max_frames, sz.variant);
-        nodes = sz.s.table + (size_t)b * 2 * sz.max_frames * W;
-        m = ok ? min(max(h[H_M], 0), W) : 0;
-        f0 = ok ? min(max(h[H_FRAMES], 0), sz.max_frames) : 0;
-        if constexpr (MODE == ADVANCE) {
-            len_b = ok ? min(len_b, sz.max_frames - f0) : 0;       // no node beyond the table, whatever the host says
-            if (len_b <= 0) return;                                  // nothing to consume: the state is not touched
-        } else {
-            len_b = 0;
-            if (tid == 0) sz.out_frames[b] = ok ? f0 : -1;
-        }
+        const StrmHead hd = stream_begin<MODE>(sz.s.hdr + (size_t)b * HDR_WORDS, sz.s.table, 2, B, W, sz.max_frames,
+                                               sz.variant, sz.out_frames, b, len_b);
+        nodes = hd.nodes; m = hd.m; f0 = hd.f0; len_b = hd.len_b;
+        if (MODE == ADVANCE && len_b <= 0) return;     // nothing to consume: the state is not touched
         if (tid < m) {
             const size_t i = (size_t)b * W + tid;
             const int utok = sz.s.utok[i], gtok = sz.s.gtok[i];
@@ -1642,13 +1659,15 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
             else tot[i] = lae3(npb, npu, npg);
         }
         __syncthreads();
-        // D: radix select of the W best valid entries (as in beam_kernel)
+        // D, E: beam_kernel's, line for line (see the note there)
+        // D: radix select of the W best valid entries, 8 bits of the key per pass from the top: key >> sh > tau >> sh, and the
+        // first `need` (canonical order) with key >> sh == tau >> sh.  It stops early once the boundary digit's entries are all kept.
         const int chunk = (E + THREADS - 1) / THREADS, e0 = min(E, tid * chunk), e1 = min(E, e0 + chunk);
         unsigned prefix = 0;
         int need = W, all = 0, sh = 0;
         for (int shift = 24, pass = 0; shift >= 0; shift -= 8, ++pass) {
             unsigned* h = hist[pass & 1];
-            hist[(pass + 1) & 1][tid] = 0;
+            hist[(pass + 1) & 1][tid] = 0;           // the next pass's histogram; the last reader of it was the pass before
             for (int e = e0; e < e1; ++e) {
                 const float f = tot[e];
                 if (!valid(f)) continue;
@@ -1693,7 +1712,7 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
             prefix |= (unsigned)s_digit << shift;
             need = s_need;
             sh = shift;
-            if (s_done) break;
+            if (s_done) break;          // (s_digit / s_need / s_done are rewritten after the next pass's first barrier)
         }
         const unsigned tau = all ? 0u : prefix;
         const int need_eq = all ? 0 : need;
@@ -1728,11 +1747,7 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
         // F: rank the survivors (score descending, canonical position on ties) into the next beam
         if (tid < M) {
             const float f = sv_tot[tid];
-            int rank = 0;
-            for (int u = 0; u < M; ++u) {
-                const float g2 = sv_tot[u];
-                rank += g2 > f || (g2 == f && u < tid);
-            }
+            const int rank = rank_of(sv_tot, M, f, tid);
             const int e = sv_pos[tid];
             if (e < m) {
                 // a stay whose pu (pg) was empty so far learns the token from the candidate that spells s[-1] (s[-2:])
@@ -1827,18 +1842,13 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
             sz.s.node[i] = o.node[tid];
             if constexpr (LM) sz.s.lm[i] = fl.lm[cur][tid];
         }
-        if (tid == 0) {
-            int* h = sz.s.hdr + (size_t)b * HDR_WORDS;
-            h[H_M] = m;
-            h[H_FRAMES] = f0 + len_b;
-        }
+        stream_end(sz.s.hdr + (size_t)b * HDR_WORDS, m, f0 + len_b);
         return;
     }
-    // RESULT: a string longer than the row pitch is cut (its length is reported in full), and a chain that leaves the table (a
-    // state that other code wrote into) ends there
+    // the N-best strings, sorted by score: the ids by fill_blank and walk_chain (RESULT: a string longer than the row pitch is cut there, and its
+    // length is reported in full)
     int table_n = 0;
     if constexpr (MODE == RESULT) table_n = 2 * sz.max_frames * W;
-    // the N-best strings, sorted by score: ids padded with blank, then each walks its prefix table chain back to the root
     int32_t* ids = out_ids + (size_t)b * W * T2;
     if constexpr (LM) {
         // the end term, then the final order: score descending, ties to the earlier slot (as beam_kernel<true>)
@@ -1853,32 +1863,19 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
         }
         __syncthreads();
         if (tid < m) {
-            int rank = 0;
-            for (int u = 0; u < m; ++u) {
-                const float g2 = sv_tot[u];
-                rank += g2 > sc || (g2 == sc && u < tid);
-            }
+            const int rank = rank_of(sv_tot, m, sc, tid);
             sv_pos[rank] = tid;
             out_score[b * W + rank] = sc;
             fz.out_ctc[b * W + rank] = ctc;
             fz.out_lm[b * W + rank] = lmv;
         }
         __syncthreads();
-        for (size_t k = tid; k < (size_t)W * T2; k += THREADS) {
-            const int i = (int)(k / T2), p = (int)(k - (size_t)i * T2);
-            if (p >= (i < m ? o.len[sv_pos[i]] : 0)) ids[k] = blank;
-        }
+        fill_blank(ids, T2, W, m, o.len, sv_pos, blank);
         if (tid < W) {
             if (tid < m) {
                 const int h = sv_pos[tid], L = o.len[h];
                 out_len[b * W + tid] = L;
-                int nd = o.node[h];
-                for (int p = L - 1; p >= 0; --p) {
-                    if (MODE == RESULT && (unsigned)nd >= (unsigned)table_n) break;
-                    const int2 e = nodes[nd];
-                    if (MODE != RESULT || p < T2) ids[(size_t)tid * T2 + p] = e.y;
-                    nd = e.x;
-                }
+                walk_chain<MODE>(ids + (size_t)tid * T2, T2, L, o.node[h], nodes, table_n);
             } else {
                 out_len[b * W + tid] = 0;
                 out_score[b * W + tid] = -INFINITY;
@@ -1888,22 +1885,13 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
         }
         return;
     }
-    for (size_t k = tid; k < (size_t)W * T2; k += THREADS) {
-        const int i = (int)(k / T2), p = (int)(k - (size_t)i * T2);
-        if (p >= (i < m ? o.len[i] : 0)) ids[k] = blank;
-    }
+    fill_blank(ids, T2, W, m, o.len, nullptr, blank);
     if (tid < W) {
         if (tid < m) {
             const int L = o.len[tid];
             out_len[b * W + tid] = L;
             out_score[b * W + tid] = lae3(o.pb[tid], o.pu[tid], o.pg[tid]);
-            int nd = o.node[tid];
-            for (int p = L - 1; p >= 0; --p) {
-                if (MODE == RESULT && (unsigned)nd >= (unsigned)table_n) break;
-                const int2 e = nodes[nd];
-                if (MODE != RESULT || p < T2) ids[(size_t)tid * T2 + p] = e.y;
-                nd = e.x;
-            }
+            walk_chain<MODE>(ids + (size_t)tid * T2, T2, L, o.node[tid], nodes, table_n);
         } else {
             out_len[b * W + tid] = 0;
             out_score[b * W + tid] = -INFINITY;
@@ -1920,6 +1908,16 @@ static size_t gram_ws_layout(int T, int B, int W, int K, char* base, Ws* ws, int
     return off;
 }
 
+// gram_rows_kernel over the candidate rows that launch_cand left in ws; nothing to spell where a row can have no candidate
+static int launch_gram_rows(void* stream, const int32_t* lengths, int T, int B, int K, const Ws& ws, const int32_t* gram, int2* cgr) {
+    if (K <= 0) return ASR_OK;
+    const long long rows = (long long)T * B;
+    hipLaunchKernelGGL(gram_rows_kernel, dim3((unsigned)((rows * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, lengths, T, B,
+                       K, ws, (const int2*)gram, cgr);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
 }  // namespace beam
 }  // namespace asr
 
@@ -1931,26 +1929,18 @@ extern "C" size_t asr_gram_ctc_beam_workspace_bytes(int T, int B, int V, int bea
 extern "C" int asr_gram_ctc_beam_search(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank,
                                         int beam_width, int top_k, float min_logp, const int32_t* gram, void* workspace,
                                         size_t workspace_bytes, int32_t* out_ids, int32_t* out_len, float* out_score) {
-    if (!logits || !workspace || !out_ids || !out_len || !out_score || T <= 0 || B <= 0 || V <= 0 || blank < 0 || blank >= V ||
-        beam_width <= 0 || top_k <= 0)
-        return ASR_ERR_BAD_ARG;
-    if (!gram) return ASR_ERR_UNSUPPORTED;
-    if (beam_width > MAX_BEAM || top_k > MAX_TOPK || beam_width * top_k > MAX_EXT) return ASR_ERR_UNSUPPORTED;
-    if (2LL * T * beam_width > 0x7fffffffLL) return ASR_ERR_UNSUPPORTED;         // prefix table node ids are int32
+    int rc = oneshot_check(logits, workspace, out_ids, out_len, out_score, T, B, V, blank, beam_width, top_k, 2);
+    if (rc == ASR_OK && !gram) rc = ASR_ERR_UNSUPPORTED;
+    if (rc != ASR_OK) return rc;
     const int K = min(top_k, V - 1);
     Ws ws;
     int2* cgr;
     const size_t need = gram_ws_layout(T, B, beam_width, K, (char*)workspace, &ws, &cgr);
     if (workspace_bytes < need) return ASR_ERR_WORKSPACE;
-    const long long rows = (long long)T * B;
-    hipLaunchKernelGGL(cand_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, lengths, T, B, V,
-                       blank, K, min_logp, ws);
-    ASR_LAUNCH_CHECK();
-    if (K > 0) {
-        hipLaunchKernelGGL(gram_rows_kernel, dim3((unsigned)((rows * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, lengths, T,
-                           B, K, ws, (const int2*)gram, cgr);
-        ASR_LAUNCH_CHECK();
-    }
+    rc = launch_cand(stream, logits, lengths, T, B, V, blank, K, min_logp, ws);
+    if (rc != ASR_OK) return rc;
+    rc = launch_gram_rows(stream, lengths, T, B, K, ws, gram, cgr);
+    if (rc != ASR_OK) return rc;
     hipLaunchKernelGGL((gram_beam_kernel<false, ONESHOT>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V,
                        beam_width, K, blank, ws, (const int2*)cgr, out_ids, out_len, out_score, Fuse<false>{}, GStrm<ONESHOT>{});
     ASR_LAUNCH_CHECK();
@@ -1966,35 +1956,23 @@ extern "C" int asr_gram_ctc_beam_search_lm(void* stream, const float* logits, co
                                            const int32_t* keys, const float* vals, int slots, int max_probe, int order, int bos,
                                            int eos, float alpha, float beta, void* workspace, size_t workspace_bytes,
                                            int32_t* out_ids, int32_t* out_len, float* out_score, float* out_ctc, float* out_lm) {
-    if (!logits || !workspace || !out_ids || !out_len || !out_score || !out_ctc || !out_lm || T <= 0 || B <= 0 || V <= 0 ||
-        blank < 0 || blank >= V || beam_width <= 0 || top_k <= 0 || vlm < V || bos >= vlm || eos >= vlm)
-        return ASR_ERR_BAD_ARG;
+    const int lim = oneshot_check(logits, workspace, out_ids, out_len, out_score, T, B, V, blank, beam_width, top_k, 2);
+    if (lim == ASR_ERR_BAD_ARG || !out_ctc || !out_lm || vlm < V || bos >= vlm || eos >= vlm) return ASR_ERR_BAD_ARG;
     Fuse<true> fz;
-    const int rc = make_lm(uni, vlm, keys, vals, slots, max_probe, order, &fz.lm);
+    int rc = make_lm(uni, vlm, keys, vals, slots, max_probe, order, &fz.lm);
     if (rc != ASR_OK) return rc;
     if (!gram) return ASR_ERR_UNSUPPORTED;
-    if (beam_width > MAX_BEAM || top_k > MAX_TOPK || beam_width * top_k > MAX_EXT) return ASR_ERR_UNSUPPORTED;
-    if (2LL * T * beam_width > 0x7fffffffLL) return ASR_ERR_UNSUPPORTED;
+    if (lim != ASR_OK) return lim;
     const int K = min(top_k, V - 1);
     Ws ws;
     int2* cgr;
     const size_t need = gram_ws_layout(T, B, beam_width, K, (char*)workspace, &ws, &cgr);
     if (workspace_bytes < need) return ASR_ERR_WORKSPACE;
-    fz.bos = bos < 0 ? -1 : bos;
-    fz.eos = eos < 0 ? -1 : eos;
-    fz.alpha = alpha;
-    fz.beta = beta;
-    fz.out_ctc = out_ctc;
-    fz.out_lm = out_lm;
-    const long long rows = (long long)T * B;
-    hipLaunchKernelGGL(cand_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, lengths, T, B, V,
-                       blank, K, min_logp, ws);
-    ASR_LAUNCH_CHECK();
-    if (K > 0) {
-        hipLaunchKernelGGL(gram_rows_kernel, dim3((unsigned)((rows * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, lengths, T,
-                           B, K, ws, (const int2*)gram, cgr);
-        ASR_LAUNCH_CHECK();
-    }
+    fill_fuse(&fz, bos, eos, alpha, beta, out_ctc, out_lm);
+    rc = launch_cand(stream, logits, lengths, T, B, V, blank, K, min_logp, ws);
+    if (rc != ASR_OK) return rc;
+    rc = launch_gram_rows(stream, lengths, T, B, K, ws, gram, cgr);
+    if (rc != ASR_OK) return rc;
     hipLaunchKernelGGL((gram_beam_kernel<true, ONESHOT>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V,
                        beam_width, K, blank, ws, (const int2*)cgr, out_ids, out_len, out_score, fz, GStrm<ONESHOT>{});
     ASR_LAUNCH_CHECK();
@@ -2043,20 +2021,23 @@ static void launch_gram_stream(hipStream_t st, const float* x, const int32_t* le
                            out_ids, out_len, out_score, Fuse<false>{}, sz);
 }
 
+// the Gram-CTC stream's variant word (GState's header, gram_state_layout)
+static int gram_variant(bool with_lm) { return GRAM_VARIANT | (with_lm ? 1 : 0); }
+
 // the checks on dimensions, state size and the model arguments that advance and result share; fills fz->lm and sz->s
 static int gram_stream_open(int B, int W, int F, const float* uni, int vlm, const int32_t* keys, const float* vals, int slots,
                             int max_probe, int order, int bos, void* state, size_t state_bytes, Fuse<true>* fz, GStrmArgs* sz) {
-    if (!state || B <= 0 || W <= 0 || F <= 0) return ASR_ERR_BAD_ARG;
+    const int lim = stream_dims(state != nullptr, B, W, F, 2);
+    if (lim == ASR_ERR_BAD_ARG) return lim;
     const bool with_lm = uni != nullptr;
     if (with_lm) {
         if (bos >= vlm) return ASR_ERR_BAD_ARG;
         const int rc = make_lm(uni, vlm, keys, vals, slots, max_probe, order, &fz->lm);
         if (rc != ASR_OK) return rc;
     }
-    if (W > MAX_BEAM) return ASR_ERR_UNSUPPORTED;
-    if (2LL * F * W > 0x7fffffffLL) return ASR_ERR_UNSUPPORTED;           // prefix table node ids are int32
+    if (lim != ASR_OK) return lim;
     sz->max_frames = F;
-    sz->variant = GRAM_VARIANT | (with_lm ? 1 : 0);
+    sz->variant = gram_variant(with_lm);
     sz->out_frames = nullptr;
     if (state_bytes < gram_state_layout(B, W, F, sz->variant, (char*)state, &sz->s)) return ASR_ERR_WORKSPACE;
     return ASR_OK;
@@ -2066,8 +2047,8 @@ static int gram_stream_open(int B, int W, int F, const float* uni, int vlm, cons
 }  // namespace asr
 
 extern "C" size_t asr_gram_ctc_beam_stream_state_bytes(int B, int beam_width, int max_frames, int with_lm) {
-    if (B <= 0 || beam_width <= 0 || max_frames <= 0) return 0;
-    return gram_state_layout(B, beam_width, max_frames, GRAM_VARIANT | (with_lm ? 1 : 0), nullptr, nullptr);
+    if (stream_dims(true, B, beam_width, max_frames, 2) == ASR_ERR_BAD_ARG) return 0;
+    return gram_state_layout(B, beam_width, max_frames, gram_variant(with_lm), nullptr, nullptr);
 }
 
 extern "C" size_t asr_gram_ctc_beam_stream_workspace_bytes(int Tc, int B, int V, int beam_width, int top_k) {
@@ -2077,9 +2058,9 @@ extern "C" size_t asr_gram_ctc_beam_stream_workspace_bytes(int Tc, int B, int V,
 
 extern "C" int asr_gram_ctc_beam_stream_reset(void* stream, void* state, size_t state_bytes, int B, int beam_width, int max_frames,
                                               int with_lm, const int32_t* mask) {
-    if (!state || B <= 0 || beam_width <= 0 || max_frames <= 0) return ASR_ERR_BAD_ARG;
-    if (beam_width > MAX_BEAM || 2LL * max_frames * beam_width > 0x7fffffffLL) return ASR_ERR_UNSUPPORTED;
-    const int variant = GRAM_VARIANT | (with_lm ? 1 : 0);
+    const int rc = stream_dims(state != nullptr, B, beam_width, max_frames, 2);
+    if (rc != ASR_OK) return rc;
+    const int variant = gram_variant(with_lm);
     GState s;
     if (state_bytes < gram_state_layout(B, beam_width, max_frames, variant, (char*)state, &s)) return ASR_ERR_WORKSPACE;
     hipLaunchKernelGGL(gram_stream_reset_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, s, B,
@@ -2099,8 +2080,8 @@ extern "C" int asr_gram_ctc_beam_stream_advance(void* stream, const float* logit
     if (uni && vlm < V) return ASR_ERR_BAD_ARG;
     Fuse<true> fz{};
     GStrm<ADVANCE> sz{};
-    const int rc = gram_stream_open(B, beam_width, max_frames, uni, vlm, keys, vals, slots, max_probe, order, bos, state,
-                                    state_bytes, &fz, &sz);
+    int rc = gram_stream_open(B, beam_width, max_frames, uni, vlm, keys, vals, slots, max_probe, order, bos, state, state_bytes,
+                              &fz, &sz);
     if (rc != ASR_OK) return rc;
     if (!gram) return ASR_ERR_UNSUPPORTED;
     if (top_k > MAX_TOPK || beam_width * top_k > MAX_EXT) return ASR_ERR_UNSUPPORTED;
@@ -2109,19 +2090,11 @@ extern "C" int asr_gram_ctc_beam_stream_advance(void* stream, const float* logit
     Ws ws;
     int2* cgr;
     if (workspace_bytes < gram_ws_layout(Tc, B, 0, K, (char*)workspace, &ws, &cgr)) return ASR_ERR_WORKSPACE;
-    fz.bos = bos < 0 ? -1 : bos;
-    fz.eos = -1;                                     // the strings end in result
-    fz.alpha = alpha;
-    fz.beta = beta;
-    const long long rows = (long long)Tc * B;
-    hipLaunchKernelGGL(cand_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, lengths, Tc, B, V,
-                       blank, K, min_logp, ws);
-    ASR_LAUNCH_CHECK();
-    if (K > 0) {
-        hipLaunchKernelGGL(gram_rows_kernel, dim3((unsigned)((rows * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, lengths, Tc,
-                           B, K, ws, (const int2*)gram, cgr);
-        ASR_LAUNCH_CHECK();
-    }
+    fill_fuse(&fz, bos, -1, alpha, beta, nullptr, nullptr);      // the strings end in result
+    rc = launch_cand(stream, logits, lengths, Tc, B, V, blank, K, min_logp, ws);
+    if (rc != ASR_OK) return rc;
+    rc = launch_gram_rows(stream, lengths, Tc, B, K, ws, gram, cgr);
+    if (rc != ASR_OK) return rc;
     launch_gram_stream<ADVANCE>((hipStream_t)stream, logits, lengths, Tc, B, V, beam_width, K, blank, ws, (const int2*)cgr, nullptr,
                                 nullptr, nullptr, fz, sz);
     ASR_LAUNCH_CHECK();
@@ -2141,12 +2114,7 @@ extern "C" int asr_gram_ctc_beam_stream_result(void* stream, const float* uni, i
                                     const_cast<void*>(state), state_bytes, &fz, &sz);
     if (rc != ASR_OK) return rc;
     sz.out_frames = out_frames;
-    fz.bos = bos < 0 ? -1 : bos;
-    fz.eos = eos < 0 ? -1 : eos;
-    fz.alpha = alpha;
-    fz.beta = beta;
-    fz.out_ctc = out_ctc;
-    fz.out_lm = out_lm;
+    fill_fuse(&fz, bos, eos, alpha, beta, out_ctc, out_lm);
     launch_gram_stream<RESULT>((hipStream_t)stream, nullptr, nullptr, Lcap, B, 0, beam_width, 0, blank, Ws{}, nullptr, out_ids,
                                out_len, out_score, fz, sz);
     ASR_LAUNCH_CHECK();

@@ -155,3 +155,15 @@ def test_entries_in_the_header_the_binding_and_both_libraries():
         assert q(T, B, V, W, K) >= p(T, B, V, W, K) + T * B * (W * 8 + K * 8)
         assert q(5, 1, 3, 4, 16) == q(5, 1, 3, 4, 2)       # top_k above V - 1 acts as V - 1
         assert q(0, B, V, W, K) == 0 and q(T, B, V, 0, K) == 0
+
+
+def test_the_two_copies_of_the_select_are_the_same_text():
+    """phases D and E (radix select and compaction) stand in beam_kernel and in gram_beam_kernel (as one
+    function they compiled to slower frame loops); this is where ties and the canonical order are decided, so the copies must
+    not drift: from the phase D comment to the line that forms M they are the same lines"""
+    src = open(os.path.join(PKG, "csrc", "ctc_beam.hip")).read().split("\n")
+    first = [i for i, line in enumerate(src) if line.strip().startswith("// D: radix select of the W best valid entries")]
+    last = [i for i, line in enumerate(src) if line.strip().startswith("const int M = (packed_total >> 16)")]
+    assert len(first) == 2 and len(last) == 2 and first[0] < last[0] < first[1] < last[1]
+    a, b = src[first[0]:last[0] + 1], src[first[1]:last[1] + 1]
+    assert len(a) > 60 and a == b
