@@ -2188,7 +2188,6 @@ extern "C" size_t asr_gru_sync_bytes(int B, int H, int ndir) {
     return 4096 + kShardBytes + (ps > ring ? ps : ring);               // control words, sharded counters, the larger exchange area
 }
 
-static bool valid_mode(int mode) { return mode == 0 || mode == 1 || mode == 2 || mode == 4 || (mode >= 7 && mode <= 10); }
 static int check_dims(int T, int B, int H, int ndir) {
     if (T <= 0 || B <= 0 || H <= 0 || (ndir != 1 && ndir != 2)) return ASR_ERR_BAD_ARG;
     if (H % 32) return ASR_ERR_UNSUPPORTED;       // MFMA K step and 16-unit workgroup slices
@@ -2262,10 +2261,45 @@ static int device_cus() {
     return cached[dev] > 0 ? cached[dev] : 0;
 }
 
-static bool can_persist(int T, int B, int H, int ndir, int mode, const void* sync_ws) {
-    if (mode == 1 || !sync_ws) return false;
+// ---------------------------------------------------------------------------------------------- the dispatch plan
+// Which kernel form serves a call, with which hand-off, is decided HERE and nowhere else: plan_fwd / plan_bwd are host arithmetic
+// (no HIP call), the two queries and the two launch entries read the plan they return.  DESIGN.md section 28.
+// The C ABI's mode numbers (include/asr_hip.h describes them): the fastest form that serves | one launch per time step | persistent with the
+// placement-free hand-off only | XCD-local hand-off signalled by flags | the same, forged split placement | XCD-local with the payload as its
+// own signal (what mode 0 selects) | backward: the partial-sum exchange asked for | the same, forged split placement (forward: both are mode 0)
+enum Mode : int { kModeDefault = 0, kModePerStep = 1, kModeFree = 2, kModeFlags = 4, kModeFlagsSplit = 7, kModePayload = 8, kModePs = 9, kModePsSplit = 10 };
+static bool valid_mode(int mode) { return mode == kModeDefault || mode == kModePerStep || mode == kModeFree || mode == kModeFlags || (mode >= kModeFlagsSplit && mode <= kModePsSplit); }
+static int fwd_mode(int mode) { return mode == kModePs || mode == kModePsSplit ? kModeDefault : mode; }       // (those select backward kernels)
+static bool polls_payload(int mode) { return mode == kModeDefault || mode == kModePayload; }
+static bool tries_local(int mode) { return polls_payload(mode) || mode == kModeFlags || mode == kModeFlagsSplit; }     // the XCD-local hand-off
+static bool takes_ps(int mode) { return polls_payload(mode) || mode == kModePs || mode == kModePsSplit; }
+// the `forge` argument of the wide kernels: 1 a forged split placement, 8 data polling (mode 4 keeps the flag line for comparison)
+static int wide_forge(int mode) { return mode == kModeFlagsSplit ? 1 : (polls_payload(mode) ? 8 : 0); }
+
+struct Flags { int fwd_ring, fwd_rows, poll_delay; };       // ASR_DEBUG (common.hpp), read once per process
+static const Flags& debug_flags() {
+    static const Flags f = {debug_flag("fwd_ring", 1), debug_flag("gru_fwd_rows", 8), debug_flag("gru_poll_delay", -1)};
+    return f;
+}
+
+enum Form { STEP, WIDE, IO, PS };       // one launch per time step | 32 units x 4-row recurrences | 16 units x 8 rows (forward) | partial sums (backward)
+struct Plan {                   // of one direction
+    int rc_format = ASR_OK;     // UNSUPPORTED: gi_bf16 / gates_f16 is not what the form takes (the queries answer from this)
+    int rc = ASR_OK;            // UNSUPPORTED: no kernel serves the call (given after the update gate is pinned / dy is masked, as ever)
+    Form form = STEP;
+    int slab = 0;               // IO, PS: rows per launch of a batch beyond 32 rows (0: one launch)
+    bool local = false;         // try the XCD-local hand-off
+    int forge = 0;              // the kernels' `forge` argument
+    bool ring = false;          // IO: the L2-resident ring hand-off (the form that may keep half gates)
+    bool rows4 = false;         // IO: ASR_DEBUG gru_fwd_rows=4 applies to a launch of sixteen 4-row recurrences
+    int delay = 0;              // IO: first-poll delay
+};
+
+static bool offsets_fit(int T, int B, int H, int ndir) { return (size_t)T * B * ndir * 3 * H * 2 < ((size_t)1 << 31); }    // 32-bit offsets inside the hand-off buffers
+static bool can_persist(int T, int B, int H, int ndir, int mode, bool have_sync, int cus) {
+    if (mode == kModePerStep || !have_sync) return false;
     if (B > 16 * MT || (H / 16) * ndir > 128 || H > 1024) return false;
-    if ((size_t)T * B * ndir * 3 * H * 2 >= ((size_t)1 << 31)) return false;
+    if (!offsets_fit(T, B, H, ndir)) return false;
     // every workgroup of a persistent launch asks for most of a CU's LDS and must be resident together with all the others:
     // the largest grid any of the forms below builds for these sizes has to fit the device's CUs (a partitioned device --
     // CPX mode, a CU mask -- reports fewer), otherwise the per-step launches serve.  Which XCD a workgroup lands on is NOT
@@ -2273,17 +2307,13 @@ static bool can_persist(int T, int B, int H, int ndir, int mode, const void* syn
     const int rec8 = (ndir * ((B + 7) / 8) + 7) & ~7, rec4 = (ndir * ((B + 3) / 4) + 7) & ~7;
     const int narrow = rec8 * (H / 16), wide = rec4 * ((H + 31) / 32);
     const int need = narrow > wide ? narrow : wide;
-    const int cus = device_cus();
-    if (cus > 0 && need > cus) return false;
-    return true;
+    return !(cus > 0 && need > cus);
 }
 
 // first-poll delay of the forward hand-off in s_sleep(1) units (~70 cycles each), see kFirstPollDelay: measured per H (the number of
 // producers of a recurrence, H / 16, shifts the moment the last store lands); ASR_DEBUG gru_poll_delay overrides
-static int fwd_poll_delay(int H, bool ring) {
-    static int env = -2;
-    if (env == -2) env = debug_flag("gru_poll_delay", -1);
-    if (env >= 0) return env > 255 ? 255 : env;
+static int fwd_poll_delay(int H, bool ring, const Flags& f) {
+    if (f.poll_delay >= 0) return f.poll_delay > 255 ? 255 : f.poll_delay;
     // T=1000, B=32, us per step at 0 / best.  Ring form (whole-line stores into L2-resident slots): H=512 1.30 / 1.23 (5-6),
     // H=384 1.20 / 1.18 (3), H=256 1.03 / 1.00 (3), H=128 1.20 flat.  Sequence form (32-B pieces of fresh lines): H=512 1.49 / 1.34 (11),
     // H=384 1.41 / 1.39 (2-4), H=256 1.156 / 1.137 (2-4), H=128 1.24 / 1.21 (6-12)
@@ -2293,68 +2323,77 @@ static int fwd_poll_delay(int H, bool ring) {
     return H >= 512 ? kFirstPollDelay : (H >= 256 ? 3 : 6);
 }
 
-// which forward kernel family serves a call: 0 one launch per time step, 1 wide (32 units x 4-row recurrences), 2 the 16-unit x 8-row
-// kernel (the default at 16 < B <= 32, and of every slab of a larger batch)
-static int fwd_family(int T, int B, int H, int ndir, int mode, const void* sync_ws) {
-    if (!can_persist(T, B, H, ndir, mode, sync_ws)) return 0;
+// the form of ONE forward launch over B rows (a whole batch of <= 32 rows, or the slabs of a larger one)
+static Plan fwd_form(int T, int B, int H, int ndir, int mode, bool have_sync, const Flags& f, int cus) {
+    Plan p;
+    if (!can_persist(T, B, H, ndir, mode, have_sync, cus)) return p;
     // (until round 4 the wide form also served 4 < B <= 16 in the default modes -- "a 4-row recurrence fetches half the hand-off bytes" --
     // but the 8-row kernel has since gained the ring hand-off, bf16 input projections and half gates: T=1000, H=512, us per step,
-    // wide / 8-row: B=16 1.64 / 1.18, B=12 1.58 / 1.17, B=8 1.46 / 1.16, B=5 1.42 / 1.16.  The wide form is the placement-free mode 2's.)
-    if (mode == 2 && H >= 128 && ndir * ((B + 3) / 4) <= 16 && (H / 32 + 7) / 8 <= 4) return 1;
-    return 2;
+    // wide / 8-row: B=16 1.64 / 1.18, B=12 1.58 / 1.17, B=8 1.46 / 1.16, B=5 1.42 / 1.16.  The wide form is the placement-free mode 2's:
+    // at T=1000, B=32, H=512 it ties the 8-row kernel with the XCD-local hand-off (2.11 vs 2.12 us: the smaller payload is paid back in
+    // the 8-wave reduction) and wins with the placement-free one (2.47 vs 2.72 us); the backward pass is wide in both.)
+    p.local = tries_local(mode);
+    p.forge = wide_forge(mode);
+    if (mode == kModeFree && H >= 128 && ndir * ((B + 3) / 4) <= 16 && (H / 32 + 7) / 8 <= 4) {
+        p.form = WIDE;
+        return p;
+    }
+    // the 16-unit x 8-row kernel: the default at B <= 32 and of every slab of a larger batch.  Data polling is the default of its XCD-local
+    // form (mode 4 keeps the flag line for comparison); the payload travels through the L2-resident ring (ASR_DEBUG fwd_ring=0: it is polled in
+    // the bf16 sequence itself).  A rows4 launch has 16 recurrences of 4 rows; at <= 32 rows they fit like the 8 of 8 rows reasoned with here.
+    const int ksw = (H / 32 + 3) / 4;
+    p.form = IO;
+    p.local = p.local && ndir * ((B + 7) / 8) <= 8;
+    p.forge = mode == kModeFlagsSplit ? 1 : (p.local && polls_payload(mode) && ksw >= 2 ? 8 : 0);
+    p.ring = p.local && (p.forge & 8) && f.fwd_ring;
+    p.delay = fwd_poll_delay(H, p.ring, f);
+    return p;
 }
 
-// the default pair -- forward with the L2-resident ring hand-off, backward with the partial-sum exchange -- can keep the saved gates
-// in IEEE half (kernel comments: G16); every other kernel form reads / writes float32 gates
-static bool fwd_ring_form(int T, int B, int H, int ndir, int mode, const void* sync_ws) {
-    if (fwd_family(T, B, H, ndir, mode, sync_ws) != 2) return false;
-    static int ring_env = -1;
-    if (ring_env < 0) ring_env = debug_flag("fwd_ring", 1);
-    const int Gio = (B + 7) / 8, ksw = (H / 32 + 3) / 4;
-    return (mode == 0 || mode == 8) && ndir * Gio <= 8 && ksw >= 2 && ring_env != 0;
+// the form of ONE backward launch over B rows
+static Plan bwd_form(int T, int B, int H, int ndir, int mode, bool have_sync, bool have_bias_sums, int cus) {
+    Plan p;
+    const int ksw = (3 * H / 32 + 3) / 4, ks8 = (3 * H / 32 + 7) / 8;
+    // the persistent kernels sum the bias gradients in registers and have no form without them
+    if (!(can_persist(T, B, H, ndir, mode, have_sync, cus) && ksw <= 12 && have_bias_sums && ndir * ((B + 3) / 4) <= 16)) return p;
+    // partial-sum exchange (bwd_ps_kernel): the default where it applies (modes 0 / 8; 9 asks for it, 10 forges a split
+    // placement so that its placement-free stores are exercised); measured 1.78 -> 1.59 us per step at T=1000, B=32, H=512
+    if (takes_ps(mode) && H % 128 == 0 && H <= 1024) {
+        p.form = PS;
+        p.forge = mode == kModePsSplit ? 1 : 0;
+    } else if (H >= 64 && ks8 <= 6) {       // wide form (32 units x 4-row recurrences): every other persistent case
+        p.form = WIDE;
+        p.local = tries_local(mode);
+        p.forge = wide_forge(mode);
+    }
+    return p;
 }
-static bool bwd_ps_form(int T, int B, int H, int ndir, int mode, const void* sync_ws) {
-    const int ksw = (3 * H / 32 + 3) / 4;
-    return can_persist(T, B, H, ndir, mode, sync_ws) && ksw <= 12 && (mode == 0 || mode == 8 || mode == 9 || mode == 10) && H % 128 == 0 &&
-           H <= 1024 && ndir * ((B + 3) / 4) <= 16;
-}
+
 // Any batch size on the fast path.  The persistent kernels are resident on every CU at 32 utterances (8 recurrences x 32 workgroups
 // forward, 16 x 16 backward), and a recurrence's step time does not depend on how many of its rows are live.  A larger batch --
 // the reference trains with 128 per bucket, shrinking by 16 (run/ctc/cnn/train.py:72-73,165,208-209) -- runs as consecutive slabs of
 // <= 32 rows through the default kernel pair: utterances are independent, so the results are those of one launch; B = 64 costs two
 // recurrences' time instead of the 8 x of the per-step launches.  0 = no slabs (the batch fits, another kernel form was asked
 // for, or the 32-bit offsets inside the hand-off buffers would not cover the whole batch).
-static int slab_rows(int T, int B, int H, int ndir, int mode, const void* sync_ws) {
+static int slab_rows(int T, int B, int H, int ndir, int mode, bool have_sync, const Flags& f, int cus) {
     constexpr int kSlab = 16 * MT;
-    if (B <= kSlab || !(mode == 0 || mode == 8)) return 0;
-    if ((size_t)T * B * ndir * 3 * H * 2 >= ((size_t)1 << 31)) return 0;
-    // the 16-unit x 8-row forward kernel (its ring form, or -- K split too shallow for it, H < 256 -- its flag form, which fills no
-    // sentinels into the whole sequence) and the partial-sum backward kernel: both take (boff, Bn)
-    if (fwd_family(T, kSlab, H, ndir, mode, sync_ws) != 2 || !bwd_ps_form(T, kSlab, H, ndir, mode, sync_ws)) return 0;
-    if (!fwd_ring_form(T, kSlab, H, ndir, mode, sync_ws) && (H / 32 + 3) / 4 >= 2) return 0;       // (ASR_DEBUG fwd_ring=0: sequence polling)
+    if (B <= kSlab || !polls_payload(mode) || !offsets_fit(T, B, H, ndir)) return 0;
+    // the 16-unit x 8-row forward kernel and the partial-sum backward kernel: both take (boff, Bn)
+    const Plan fw = fwd_form(T, kSlab, H, ndir, mode, have_sync, f, cus);
+    if (fw.form != IO || bwd_form(T, kSlab, H, ndir, mode, have_sync, true, cus).form != PS) return 0;
+    if (!fw.ring && (fw.forge & 8)) return 0;       // (ASR_DEBUG fwd_ring=0: sequence polling fills / polls the whole sequence, not a slab)
     return kSlab;
 }
 
-extern "C" int asr_gru_gates_f16_ok(int T, int B, int H, int ndir, int mode) {
-    if (check_dims(T, B, H, ndir) != ASR_OK) return 0;
-    static int dummy;
-    const int fmode = (mode == 9 || mode == 10) ? 0 : mode;
-    if (const int slab = slab_rows(T, B, H, ndir, mode, &dummy)) return fwd_ring_form(T, slab, H, ndir, fmode, &dummy) ? 1 : 0;
-    return fwd_ring_form(T, B, H, ndir, fmode, &dummy) && bwd_ps_form(T, B, H, ndir, mode, &dummy) ? 1 : 0;
-}
-
-extern "C" int asr_gru_fwd_accepts_bf16_gi(int T, int B, int H, int ndir, int mode) {
-    if (check_dims(T, B, H, ndir) != ASR_OK) return 0;
-    if (mode == 9 || mode == 10) mode = 0;
-    static int dummy;
-    if (slab_rows(T, B, H, ndir, mode, &dummy)) return 1;
-    return fwd_family(T, B, H, ndir, mode, &dummy) == 2 ? 1 : 0;
-}
-
-// The 16-unit x 8-row forward kernel (family 2 of fwd_family: the default) on the batch rows [boff, boff + Bn) of a (T, B, ..) problem.
-static int fwd_io_launch(hipStream_t st, void* gi_any, int gi_bf16, const void* whh_bf16, const float* bhh, float* hseq, void* hseq_bf16,
-                     float* gates, void* sync_ws, int T, int B, int H, int ndir, int mode, int gates_f16, int boff, int Bn) {
+// `mode` is the forward pass's (fwd_mode)
+static Plan plan_fwd(int T, int B, int H, int ndir, int mode, bool have_sync, bool gi_bf16, bool gates_f16, const Flags& f, int cus) {
+    const int slab = slab_rows(T, B, H, ndir, mode, have_sync, f, cus);
+    Plan p = fwd_form(T, slab ? slab : B, H, ndir, mode, have_sync, f, cus);
+    p.slab = slab;
     const int ksw = (H / 32 + 3) / 4;
+    // the ring form can keep the saved gates in IEEE half (kernel comments: G16), the 8-row kernel reads bf16 input projections;
+    // every other kernel form reads float32 projections and writes float32 gates
+    if ((gates_f16 && !p.ring) || (gi_bf16 && p.form != IO)) p.rc_format = ASR_ERR_UNSUPPORTED;
     // ASR_DEBUG gru_fwd_rows=4 (what-if of round 5, VERDICT r4 next 2: "hide the hand-off of one half slab behind the compute of the
     // other"): recurrences of FOUR rows, sixteen of them, 2 x 256 workgroups that ask for 72 KB of LDS so that exactly two share a CU --
     // the hardware then interleaves two independent half slabs per CU, each with its own waves (an upper bound for what one workgroup
@@ -2362,55 +2401,157 @@ static int fwd_io_launch(hipStream_t st, void* gi_any, int gi_bf16, const void* 
     // full slab (all sixteen recurrences live: a grid whose workgroups partly leave at once starves the rest of dispatch slots), the
     // ring hand-off, half gates and bf16 input projections (the default kernel instance).  Measured (tools/time_gru_fwd_rows.py,
     // profiles/r05_gru_fwd_half_slabs_whatif.txt): 1.33 us per time step against 1.27 for the 8-row form, outputs bit-identical.
-    static const int rows_env = debug_flag("gru_fwd_rows", 8);
-    const bool rows4 = rows_env == 4 && (mode == 0 || mode == 8) && ndir * ((Bn + 3) / 4) == 16 && ksw == 4 && gi_bf16 && gates_f16;
-    const int io_rows = rows4 ? 4 : 8, io_lds = rows4 ? 72 * 1024 : kPersistLds;
-    const int nrecmax = rows4 ? 16 : 8;
+    p.rows4 = f.fwd_rows == 4 && p.form == IO && polls_payload(mode) && ksw == 4 && gi_bf16 && gates_f16;
+    // H <= 1024; modes >= 2 do not fall back to one launch per time step (judged on the whole batch: mode 8 takes no slabs)
+    if (ksw > 8 || (mode >= 2 && !can_persist(T, B, H, ndir, mode, have_sync, cus))) p.rc = ASR_ERR_UNSUPPORTED;
+    return p;
+}
+
+// slabs are taken only with both bias-sum pointers
+static Plan plan_bwd(int T, int B, int H, int ndir, int mode, bool have_sync, bool have_bias_sums, bool gates_f16, const Flags& f, int cus) {
+    const int slab = have_bias_sums ? slab_rows(T, B, H, ndir, mode, have_sync, f, cus) : 0;
+    Plan p = bwd_form(T, slab ? slab : B, H, ndir, mode, have_sync, have_bias_sums, cus);
+    p.slab = slab;
+    if (gates_f16 && p.form != PS) p.rc_format = ASR_ERR_UNSUPPORTED;
+    // modes >= 2 do not fall back (judged on the whole batch); the per-step kernel holds at most 12 K steps per wave: H <= 512
+    const int ksw = (3 * H / 32 + 3) / 4;
+    const bool persist = can_persist(T, B, H, ndir, mode, have_sync, cus) && ksw <= 12;
+    if ((mode >= 2 && !persist) || (p.form == STEP && (mode >= 2 || ksw > 12))) p.rc = ASR_ERR_UNSUPPORTED;
+    return p;
+}
+
+// The queries ask the plans what the launch entries will read (a stand-in for sync_ws; the default pair: both bias sums given).
+extern "C" int asr_gru_gates_f16_ok(int T, int B, int H, int ndir, int mode) {
+    if (check_dims(T, B, H, ndir) != ASR_OK) return 0;
+    const int cus = device_cus();
+    return plan_fwd(T, B, H, ndir, fwd_mode(mode), true, false, true, debug_flags(), cus).rc_format == ASR_OK &&
+           plan_bwd(T, B, H, ndir, mode, true, true, true, debug_flags(), cus).rc_format == ASR_OK;
+}
+
+extern "C" int asr_gru_fwd_accepts_bf16_gi(int T, int B, int H, int ndir, int mode) {
+    if (check_dims(T, B, H, ndir) != ASR_OK) return 0;
+    return plan_fwd(T, B, H, ndir, fwd_mode(mode), true, true, false, debug_flags(), device_cus()).rc_format == ASR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- launches
+// a kernel with dynamic LDS has its limit raised in front of every launch
+template <typename... P, typename... A>
+static void launch_lds(void (*kernel)(P...), int max_lds, dim3 grid, dim3 block, int lds, hipStream_t st, A... args) {
+    (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+}
+
+// the template instance a launch runs: the K split by width, the hand-off and the formats as the plan has them
+using FwdStepFn = decltype(&fwd_step_kernel<1>);
+using BwdStepFn = decltype(&bwd_step_kernel<2>);
+using FwdWideFn = decltype(&fwd_wide_kernel<1, false>);
+using BwdWideFn = decltype(&bwd_wide_kernel<2, false>);
+using FwdIoFn = decltype(&fwd_persistent_io_kernel<1, false, false, false>);
+using BwdPsFn = decltype(&bwd_ps_kernel<1, true, false>);
+
+// f(integral_constant<K>) for the first K of the list with k <= K (the last K serves every larger k)
+template <int K, int... Ks, typename F>
+static auto first_k(int k, F f) {
+    if constexpr (sizeof...(Ks) == 0) return f(std::integral_constant<int, K>());
+    else return k <= K ? f(std::integral_constant<int, K>()) : first_k<Ks...>(k, f);
+}
+static FwdStepFn fwd_step_instance(int H) { return first_k<1, 2, 4, 8>((H / 32 + 3) / 4, [](auto K) -> FwdStepFn { return fwd_step_kernel<K()>; }); }
+static BwdStepFn bwd_step_instance(int H) { return first_k<2, 6, 12>((3 * H / 32 + 3) / 4, [](auto K) -> BwdStepFn { return bwd_step_kernel<K()>; }); }
+static FwdWideFn fwd_wide_instance(int H, bool local) {
+    return first_k<1, 2, 4>((H / 32 + 7) / 8, [=](auto K) -> FwdWideFn { return local ? fwd_wide_kernel<K(), true> : fwd_wide_kernel<K(), false>; });
+}
+static BwdWideFn bwd_wide_instance(int H, bool local) {
+    return first_k<2, 3, 4, 5, 6>((3 * H / 32 + 7) / 8, [=](auto K) -> BwdWideFn { return local ? bwd_wide_kernel<K(), true> : bwd_wide_kernel<K(), false>; });
+}
+static FwdIoFn fwd_io_instance(int H, bool local, bool ring, bool gi_bf16, bool gates_f16) {
+    return first_k<1, 2, 4, 8>((H / 32 + 3) / 4, [=](auto K) -> FwdIoFn {
+        if (ring && gates_f16) return gi_bf16 ? fwd_persistent_io_kernel<K(), true, true, true, true> : fwd_persistent_io_kernel<K(), true, false, true, true>;
+        if (ring) return gi_bf16 ? fwd_persistent_io_kernel<K(), true, true, true> : fwd_persistent_io_kernel<K(), true, false, true>;
+        if (local) return gi_bf16 ? fwd_persistent_io_kernel<K(), true, true, false> : fwd_persistent_io_kernel<K(), true, false, false>;
+        return gi_bf16 ? fwd_persistent_io_kernel<K(), false, true, false> : fwd_persistent_io_kernel<K(), false, false, false>;
+    });
+}
+static BwdPsFn bwd_ps_instance(int H, bool gates_f16) {       // nullptr: no instance of this width (H = 640, 768, 896)
+    const int nt = H / 128;
+    if (nt < 1 || (nt > 4 && nt != 8)) return nullptr;
+    return first_k<1, 2, 3, 4, 8>(nt, [=](auto K) -> BwdPsFn { return gates_f16 ? bwd_ps_kernel<K(), true, true> : bwd_ps_kernel<K(), true, false>; });
+}
+
+// ---- what the plain and the _state entries share
+// pin the update gate of the rows beyond each utterance's length (see pin_update_gate_kernel)
+static int pin_update_gate(hipStream_t st, void* gi_any, bool gi_bf16, const int* x_len, int T, int B, int H, int ndir) {
+    if ((long long)T * B > 0x7fffffffLL) return ASR_ERR_UNSUPPORTED;
+    if (gi_bf16) hipLaunchKernelGGL(pin_update_gate_kernel<uint16_t>, dim3((unsigned)(T * B)), dim3(256), 0, st, (uint16_t*)gi_any, x_len, B, H, ndir);
+    else hipLaunchKernelGGL(pin_update_gate_kernel<float>, dim3((unsigned)(T * B)), dim3(256), 0, st, (float*)gi_any, x_len, B, H, ndir);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+// the forward pass pinned z = 1 beyond the lengths (no gate gradient, dh passes); drop dy there: a masked copy in dy_ws
+static int mask_dy(hipStream_t st, const void* dy_bf16, void* dy_ws, const int* x_len, int T, int B, int H) {
+    if (!dy_ws || (H % 8)) return ASR_ERR_BAD_ARG;
+    const long long n = (long long)T * B * (H / 8);
+    long long g = (n + 255) / 256;
+    if (g > 8192) g = 8192;
+    hipLaunchKernelGGL(mask_rows_kernel, dim3((unsigned)g), dim3(256), 0, st, (const uint16_t*)dy_bf16, (uint16_t*)dy_ws, x_len,
+                       (long long)T * B, B, H / 8);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+// one launch per time step; hx (ndir, B, H) or NULL: the state in front of the first step
+static void fwd_steps(hipStream_t st, const float* gi, const void* whh_bf16, const float* bhh, const float* hx, float* hseq, void* hseq_bf16,
+                      float* gates, int T, int B, int H, int ndir) {
+    const FwdStepFn kernel = fwd_step_instance(H);
+    const dim3 grid(H / 16, ndir), block(256);
+    for (int s = 0; s < T; ++s)
+        hipLaunchKernelGGL(kernel, grid, block, 0, st, gi, (const uint16_t*)whh_bf16, bhh, hseq, (uint16_t*)hseq_bf16, gates, T, B, H, ndir, s, hx);
+}
+
+// carry_init: carry_ws arrives holding the gradient of the final state
+static void bwd_steps(hipStream_t st, const void* dy_bf16, const float* gates, const float* hseq, const float* hx, const void* whhT_bf16,
+                      void* dgi_bf16, void* dgh_bf16, float* carry_ws, int carry_init, int T, int B, int H, int ndir) {
+    const BwdStepFn kernel = bwd_step_instance(H);
+    const dim3 grid(H / 16, ndir), block(256);
+    for (int s = 0; s < T; ++s)
+        hipLaunchKernelGGL(kernel, grid, block, 0, st, (const uint16_t*)dy_bf16, gates, hseq, (const uint16_t*)whhT_bf16, (uint16_t*)dgi_bf16,
+                           (uint16_t*)dgh_bf16, carry_ws, T, B, H, ndir, s, hx, carry_init);
+}
+
+// y = hf + hb in bf16, zero beyond the lengths
+static int merge_dirs(hipStream_t st, const float* hseq, void* y_bf16, int T, int B, int H, int ndir, const int* x_len) {
+    const bool vec = (H & 7) == 0 && ((((uintptr_t)hseq) | ((uintptr_t)y_bf16)) & 15) == 0;
+    const long long n = (long long)T * B * (vec ? H / 8 : H);
+    long long g = (n + 255) / 256;
+    if (g > 4096) g = 4096;
+    hipLaunchKernelGGL(vec ? merge_dirs_vec_kernel : merge_dirs_kernel, dim3((unsigned)g), dim3(256), 0, st, hseq, (uint16_t*)y_bf16, (long long)T * B, H,
+                       ndir, x_len, B);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+// bias gradients after the per-step kernels (the persistent kernels sum them in registers): a column sum over all (t, b) rows
+static int bias_colsums(void* stream, const void* dgi_bf16, const void* dgh_bf16, float* db_ih, float* db_hh, int T, int B, int H, int ndir) {
+    int rc = db_ih ? asr_colsum_acc(stream, dgi_bf16, 1, (long long)T * B, ndir * 3 * H, ndir * 3 * H, db_ih) : ASR_OK;
+    if (rc == ASR_OK && db_hh) rc = asr_colsum_acc(stream, dgh_bf16, 1, (long long)T * B, ndir * 3 * H, ndir * 3 * H, db_hh);
+    return rc;
+}
+
+// The 16-unit x 8-row forward kernel on the batch rows [boff, boff + Bn) of a (T, B, ..) problem.
+static int fwd_io_launch(const Plan& p, hipStream_t st, void* gi_any, int gi_bf16, const void* whh_bf16, const float* bhh, float* hseq,
+                         void* hseq_bf16, float* gates, void* sync_ws, int T, int B, int H, int ndir, int gates_f16, int boff, int Bn) {
+    const bool rows4 = p.rows4 && ndir * ((Bn + 3) / 4) == 16;       // (all sixteen recurrences live)
+    if (rows4 && !p.ring) return ASR_ERR_UNSUPPORTED;
+    const int io_rows = rows4 ? 4 : 8, io_lds = rows4 ? 72 * 1024 : kPersistLds, nrecmax = rows4 ? 16 : 8;
     const int Gio = (Bn + io_rows - 1) / io_rows;
-    const bool local = (mode == 0 || mode == 4 || mode == 7 || mode == 8) && ndir * Gio <= nrecmax;     // try the XCD-local hand-off
-    // data polling (kernel comment): the default of the XCD-local form; mode 4 keeps the flag line for comparison
-    const int forge = (mode == 7 ? 1 : (local && (mode == 0 || mode == 8) && ksw >= 2 ? 8 : 0));
-    static int ring_env = -1;
-    if (ring_env < 0) ring_env = debug_flag("fwd_ring", 1);      // (0: the payload is polled in the bf16 sequence itself)
-    const bool use_ring = local && (forge & 8) && ring_env;
-    if (rows4 && !use_ring) return ASR_ERR_UNSUPPORTED;
-    if (gates_f16 && !use_ring) return ASR_ERR_UNSUPPORTED;
-    if (!use_ring && (forge & 8) && (boff != 0 || Bn != B)) return ASR_ERR_UNSUPPORTED;      // (slabs: not the form that fills / polls the whole sequence)
-    if (use_ring) {
+    if (p.ring) {
         if (!clear_sync_fill(sync_ws, kShardBytes, (char*)sync_ws + kPsOffset, (size_t)nrecmax * PS_RING * 8 * H * 2, st)) return ASR_ERR_LAUNCH;
-    } else if (!clear_sync_fill(sync_ws, kShardBytes, (forge & 8) ? hseq_bf16 : nullptr, (size_t)T * B * ndir * H * 2, st)) return ASR_ERR_LAUNCH;
-    const int forge_k = forge | (fwd_poll_delay(H, use_ring) << 8);
-    const dim3 igrid = local ? dim3(nrecmax * (H / 16)) : dim3(H / 16, Gio, ndir), iblock(384);
-    if (rows4) {
-        (void)hipFuncSetAttribute((const void*)fwd_persistent_io_kernel<4, true, true, true, true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, kPersistLds);
-        hipLaunchKernelGGL((fwd_persistent_io_kernel<4, true, true, true, true, 4>), igrid, iblock, io_lds, st, gi_any, (const uint16_t*)whh_bf16, bhh, hseq,
-                           (uint16_t*)hseq_bf16, gates, (unsigned*)sync_ws, T, B, H, ndir, io_rows, forge_k, boff, Bn);
-        ASR_LAUNCH_CHECK();
-        return ASR_OK;
-    }
-#define ASR_FWDIO_(K, L, G, R)                                                                                            \
-    do {                                                                                                                  \
-        (void)hipFuncSetAttribute((const void*)fwd_persistent_io_kernel<K, L, G, R>, hipFuncAttributeMaxDynamicSharedMemorySize, kPersistLds); \
-        hipLaunchKernelGGL((fwd_persistent_io_kernel<K, L, G, R>), igrid, iblock, io_lds, st, gi_any, (const uint16_t*)whh_bf16, bhh, hseq, \
-                           (uint16_t*)hseq_bf16, gates, (unsigned*)sync_ws, T, B, H, ndir, io_rows, L ? forge_k : 0, boff, Bn);         \
-    } while (0)
-#define ASR_FWDIO16_(K, G)                                                                                                \
-    do {                                                                                                                  \
-        (void)hipFuncSetAttribute((const void*)fwd_persistent_io_kernel<K, true, G, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kPersistLds); \
-        hipLaunchKernelGGL((fwd_persistent_io_kernel<K, true, G, true, true>), igrid, iblock, io_lds, st, gi_any, (const uint16_t*)whh_bf16, bhh, hseq, \
-                           (uint16_t*)hseq_bf16, gates, (unsigned*)sync_ws, T, B, H, ndir, io_rows, forge_k, boff, Bn);                 \
-    } while (0)
-#define ASR_FWDIO(K)                                                                                                      \
-    do {                                                                                                                  \
-        if (use_ring && gates_f16) { if (gi_bf16) ASR_FWDIO16_(K, true); else ASR_FWDIO16_(K, false); }                   \
-        else if (use_ring) { if (gi_bf16) ASR_FWDIO_(K, true, true, true); else ASR_FWDIO_(K, true, false, true); }       \
-        else if (local) { if (gi_bf16) ASR_FWDIO_(K, true, true, false); else ASR_FWDIO_(K, true, false, false); }        \
-        else { if (gi_bf16) ASR_FWDIO_(K, false, true, false); else ASR_FWDIO_(K, false, false, false); }                 \
-    } while (0)
-    if (ksw <= 1) ASR_FWDIO(1); else if (ksw <= 2) ASR_FWDIO(2); else if (ksw <= 4) ASR_FWDIO(4); else ASR_FWDIO(8);
-#undef ASR_FWDIO_
-#undef ASR_FWDIO16_
-#undef ASR_FWDIO
+    } else if (!clear_sync_fill(sync_ws, kShardBytes, (p.forge & 8) ? hseq_bf16 : nullptr, (size_t)T * B * ndir * H * 2, st)) return ASR_ERR_LAUNCH;
+    const int forge_k = p.forge | (p.delay << 8);
+    const dim3 igrid = p.local ? dim3(nrecmax * (H / 16)) : dim3(H / 16, Gio, ndir), iblock(384);
+    const FwdIoFn kernel = rows4 ? fwd_persistent_io_kernel<4, true, true, true, true, 4> : fwd_io_instance(H, p.local, p.ring, gi_bf16, gates_f16);
+    launch_lds(kernel, kPersistLds, igrid, iblock, io_lds, st, (const void*)gi_any, (const uint16_t*)whh_bf16, bhh, hseq, (uint16_t*)hseq_bf16, gates,
+               (unsigned*)sync_ws, T, B, H, ndir, io_rows, p.local ? forge_k : 0, boff, Bn);
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }
@@ -2421,84 +2562,34 @@ extern "C" int asr_gru_fwd(void* stream, void* gi_any, int gi_bf16, const void* 
     if (ASR_ACT_IS_F16) return ASR_ERR_UNSUPPORTED;      // (the recurrences handle bfloat16 bits directly: common.hpp)
     float* gates = reinterpret_cast<float*>(gates_any);
     if (!gi_any || !whh_bf16 || !bhh || !hseq || !hseq_bf16 || !gates) return ASR_ERR_BAD_ARG;
-    const int rc = check_dims(T, B, H, ndir);
+    int rc = check_dims(T, B, H, ndir);
     if (rc != ASR_OK) return rc;
     if (!valid_mode(mode)) return ASR_ERR_BAD_ARG;
-    if (mode == 9 || mode == 10) mode = 0;      // (those select backward kernels)
-    const int slab = slab_rows(T, B, H, ndir, mode, sync_ws);
-    if (gates_f16 && !fwd_ring_form(T, slab ? slab : B, H, ndir, mode, sync_ws)) return ASR_ERR_UNSUPPORTED;       // (ask asr_gru_gates_f16_ok)
+    const Plan p = plan_fwd(T, B, H, ndir, fwd_mode(mode), sync_ws != nullptr, gi_bf16, gates_f16, debug_flags(), device_cus());
+    if (p.rc_format != ASR_OK) return p.rc_format;      // (ask asr_gru_gates_f16_ok / asr_gru_fwd_accepts_bf16_gi)
     const float* gi = reinterpret_cast<const float*>(gi_any);
-    if (gi_bf16 && !slab && fwd_family(T, B, H, ndir, mode, sync_ws) != 2) return ASR_ERR_UNSUPPORTED;      // (ask asr_gru_fwd_accepts_bf16_gi)
     hipStream_t st = (hipStream_t)stream;
-    if (x_len) {        // pin the update gate of the rows beyond each utterance's length (see pin_update_gate_kernel)
-        if ((long long)T * B > 0x7fffffffLL) return ASR_ERR_UNSUPPORTED;
-        if (gi_bf16) hipLaunchKernelGGL(pin_update_gate_kernel<uint16_t>, dim3((unsigned)(T * B)), dim3(256), 0, st, (uint16_t*)gi_any, x_len, B, H, ndir);
-        else hipLaunchKernelGGL(pin_update_gate_kernel<float>, dim3((unsigned)(T * B)), dim3(256), 0, st, (float*)gi_any, x_len, B, H, ndir);
-        ASR_LAUNCH_CHECK();
-    }
-    const dim3 grid(H / 16, ndir), block(256);
-    const int ksw = (H / 32 + 3) / 4;
-    if (ksw > 8) return ASR_ERR_UNSUPPORTED;      // H <= 1024
-    const bool persist = can_persist(T, B, H, ndir, mode, sync_ws);
-    if (mode >= 2 && !persist) return ASR_ERR_UNSUPPORTED;
-    const int family = fwd_family(T, B, H, ndir, mode, sync_ws);
-    // (the wide form serves the placement-free mode 2; see fwd_family)
-    if (slab) {         // consecutive slabs of <= 32 rows through the default kernel (see slab_rows); the launches share sync_ws in stream order
-        for (int boff = 0; boff < B; boff += slab) {
-            const int rc2 = fwd_io_launch(st, gi_any, gi_bf16, whh_bf16, bhh, hseq, hseq_bf16, gates, sync_ws, T, B, H, ndir, mode, gates_f16, boff,
-                                          B - boff < slab ? B - boff : slab);
-            if (rc2 != ASR_OK) return rc2;
+    if (x_len && (rc = pin_update_gate(st, gi_any, gi_bf16, x_len, T, B, H, ndir)) != ASR_OK) return rc;
+    if (p.rc != ASR_OK) return p.rc;
+    if (p.form == IO) {         // (slabs: the launches share sync_ws in stream order)
+        const int rows = p.slab ? p.slab : B;
+        for (int boff = 0; boff < B; boff += rows) {
+            rc = fwd_io_launch(p, st, gi_any, gi_bf16, whh_bf16, bhh, hseq, hseq_bf16, gates, sync_ws, T, B, H, ndir, gates_f16, boff,
+                               B - boff < rows ? B - boff : rows);
+            if (rc != ASR_OK) return rc;
         }
-    } else if (family == 1) {
-        // wide form (32 units x 4-row recurrences).  Measured at T=1000, B=32, H=512: with the XCD-local hand-off it ties
-        // the 16-unit x 8-row kernel (2.11 vs 2.12 us: the smaller payload is paid back in the 8-wave reduction), with the
-        // placement-free hand-off it wins (2.47 vs 2.72 us) -- so it serves mode 2 only; the backward pass is wide in both.
-        const int Gw = (B + 3) / 4, nrec = ndir * Gw, nrec_pad = (nrec + 7) & ~7;
-        const int ks8 = (H / 32 + 7) / 8;
+    } else if (p.form == WIDE) {
+        const int Gw = (B + 3) / 4, nrec_pad = (ndir * Gw + 7) & ~7;
         if (!clear_sync(sync_ws, kShardBytes, st)) return ASR_ERR_LAUNCH;
-        const bool local = mode == 0 || mode == 4 || mode == 7 || mode == 8;
-        const int forge = (mode == 7 ? 1 : (mode == 0 || mode == 8 ? 8 : 0));
-        if ((forge & 8) && hipMemsetAsync(hseq_bf16, 0xff, (size_t)T * B * ndir * H * 2, st) != hipSuccess) return ASR_ERR_LAUNCH;
-        const dim3 wgrid = local ? dim3(nrec_pad * (H / 32)) : dim3(H / 32, Gw, ndir), wblock(640);
-#define ASR_FWDW(K)                                                                                                       \
-    do {                                                                                                                  \
-        if (local) {                                                                                                      \
-            (void)hipFuncSetAttribute((const void*)fwd_wide_kernel<K, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kPersistLds); \
-            hipLaunchKernelGGL((fwd_wide_kernel<K, true>), wgrid, wblock, kPersistLds, st, gi, (const uint16_t*)whh_bf16, bhh, hseq,  \
-                               (uint16_t*)hseq_bf16, gates, (unsigned*)sync_ws, T, B, H, ndir, forge);                        \
-        } else {                                                                                                          \
-            (void)hipFuncSetAttribute((const void*)fwd_wide_kernel<K, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kPersistLds); \
-            hipLaunchKernelGGL((fwd_wide_kernel<K, false>), wgrid, wblock, kPersistLds, st, gi, (const uint16_t*)whh_bf16, bhh, hseq, \
-                               (uint16_t*)hseq_bf16, gates, (unsigned*)sync_ws, T, B, H, ndir, 0);                            \
-        }                                                                                                                 \
-    } while (0)
-        if (ks8 <= 1) ASR_FWDW(1); else if (ks8 <= 2) ASR_FWDW(2); else ASR_FWDW(4);
-#undef ASR_FWDW
-    } else if (family == 2) {
-        const int rc2 = fwd_io_launch(st, gi_any, gi_bf16, whh_bf16, bhh, hseq, hseq_bf16, gates, sync_ws, T, B, H, ndir, mode, gates_f16, 0, B);
-        if (rc2 != ASR_OK) return rc2;
-    } else
-    for (int s = 0; s < T; ++s) {
-#define ASR_FWD(K) hipLaunchKernelGGL(fwd_step_kernel<K>, grid, block, 0, st, gi, (const uint16_t*)whh_bf16, bhh, hseq, \
-                                      (uint16_t*)hseq_bf16, gates, T, B, H, ndir, s, (const float*)nullptr)
-        if (ksw <= 1) ASR_FWD(1); else if (ksw <= 2) ASR_FWD(2); else if (ksw <= 4) ASR_FWD(4); else ASR_FWD(8);
-#undef ASR_FWD
+        if ((p.forge & 8) && hipMemsetAsync(hseq_bf16, 0xff, (size_t)T * B * ndir * H * 2, st) != hipSuccess) return ASR_ERR_LAUNCH;
+        const dim3 wgrid = p.local ? dim3(nrec_pad * (H / 32)) : dim3(H / 32, Gw, ndir), wblock(640);
+        launch_lds(fwd_wide_instance(H, p.local), kPersistLds, wgrid, wblock, kPersistLds, st, gi, (const uint16_t*)whh_bf16, bhh, hseq,
+                   (uint16_t*)hseq_bf16, gates, (unsigned*)sync_ws, T, B, H, ndir, p.local ? p.forge : 0);
+    } else {
+        fwd_steps(st, gi, whh_bf16, bhh, nullptr, hseq, hseq_bf16, gates, T, B, H, ndir);
     }
     ASR_LAUNCH_CHECK();
-    if (y_bf16) {
-        const bool vec = (H & 7) == 0 && ((((uintptr_t)hseq) | ((uintptr_t)y_bf16)) & 15) == 0;
-        const long long n = (long long)T * B * (vec ? H / 8 : H);
-        long long g = (n + 255) / 256;
-        if (g > 4096) g = 4096;
-        if (vec)
-            hipLaunchKernelGGL(merge_dirs_vec_kernel, dim3((unsigned)g), dim3(256), 0, st, hseq, (uint16_t*)y_bf16,
-                               (long long)T * B, H, ndir, x_len, B);
-        else
-            hipLaunchKernelGGL(merge_dirs_kernel, dim3((unsigned)g), dim3(256), 0, st, hseq, (uint16_t*)y_bf16,
-                               (long long)T * B, H, ndir, x_len, B);
-        ASR_LAUNCH_CHECK();
-    }
-    return ASR_OK;
+    return y_bf16 ? merge_dirs(st, hseq, y_bf16, T, B, H, ndir, x_len) : ASR_OK;
 }
 
 extern "C" int asr_gru_bwd(void* stream, const void* dy_bf16, const void* gates_any, const float* hseq,
@@ -2509,108 +2600,45 @@ extern "C" int asr_gru_bwd(void* stream, const void* dy_bf16, const void* gates_
     if (!dy_bf16 || !gates_any || !hseq || !whhT_bf16 || !dgi_bf16 || !dgh_bf16 || !carry_ws) return ASR_ERR_BAD_ARG;
     const float* gates = reinterpret_cast<const float*>(gates_any);
     if (!valid_mode(mode)) return ASR_ERR_BAD_ARG;
-    if (gates_f16 && !((bwd_ps_form(T, B, H, ndir, mode, sync_ws) || slab_rows(T, B, H, ndir, mode, sync_ws)) && db_ih && db_hh)) return ASR_ERR_UNSUPPORTED;
-    const int rc = check_dims(T, B, H, ndir);
+    const Plan p = plan_bwd(T, B, H, ndir, mode, sync_ws != nullptr, db_ih && db_hh, gates_f16, debug_flags(), device_cus());
+    if (p.rc_format != ASR_OK) return p.rc_format;      // (ask asr_gru_gates_f16_ok; given before the sizes are looked at, as ever)
+    int rc = check_dims(T, B, H, ndir);
     if (rc != ASR_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (x_len) {        // the forward pass pinned z = 1 beyond the lengths (no gate gradient, dh passes); drop dy there
-        if (!dy_ws || (H % 8)) return ASR_ERR_BAD_ARG;
-        const long long n = (long long)T * B * (H / 8);
-        long long g = (n + 255) / 256;
-        if (g > 8192) g = 8192;
-        hipLaunchKernelGGL(mask_rows_kernel, dim3((unsigned)g), dim3(256), 0, st, (const uint16_t*)dy_bf16, (uint16_t*)dy_ws, x_len,
-                           (long long)T * B, B, H / 8);
-        ASR_LAUNCH_CHECK();
+    if (x_len) {
+        if ((rc = mask_dy(st, dy_bf16, dy_ws, x_len, T, B, H)) != ASR_OK) return rc;
         dy_bf16 = dy_ws;
     }
-    const dim3 grid(H / 16, ndir), block(256);
-    const int ksw = (3 * H / 32 + 3) / 4;
-    const bool persist = can_persist(T, B, H, ndir, mode, sync_ws) && ksw <= 12;
-    if (mode >= 2 && !persist) return ASR_ERR_UNSUPPORTED;
-    // partial-sum exchange (bwd_ps_kernel): the default where it applies (modes 0 / 8; 9 asks for it, 10 forges a split
-    // placement so that its placement-free stores are exercised); measured 1.78 -> 1.59 us per step at T=1000, B=32, H=512
-    const int slab = (db_ih && db_hh) ? slab_rows(T, B, H, ndir, mode, sync_ws) : 0;       // (see slab_rows: batches beyond 32 rows)
-    if (slab || (persist && (mode == 0 || mode == 8 || mode == 9 || mode == 10) && db_ih && db_hh && H % 128 == 0 && H <= 1024 &&
-                 ndir * ((B + 3) / 4) <= 16)) {
-        for (int boff = 0; boff < B; boff += slab ? slab : B) {
-            const int Bn = slab ? (B - boff < slab ? B - boff : slab) : B;
-            const int Gw = (Bn + 3) / 4, nrec = ndir * Gw, nrec_pad = (nrec + 7) & ~7;
+    if (p.rc != ASR_OK) return p.rc;
+    if (p.form == PS) {         // (slabs: the launches share sync_ws in stream order)
+        const int rows = p.slab ? p.slab : B;
+        const BwdPsFn kernel = bwd_ps_instance(H, gates_f16);
+        for (int boff = 0; boff < B; boff += rows) {
+            const int Bn = B - boff < rows ? B - boff : rows;
+            const int Gw = (Bn + 3) / 4, nrec_pad = (ndir * Gw + 7) & ~7;
             if (!clear_sync_fill(sync_ws, kShardBytes, (char*)sync_ws + kPsOffset, ps_exchange_bytes(nrec_pad, H), st)) return ASR_ERR_LAUNCH;
-            const dim3 wgrid(nrec_pad * (H / 32)), wblock(640);
-#define ASR_BWDPS_(NT_, G)                                                                                                \
-    do {                                                                                                                  \
-        (void)hipFuncSetAttribute((const void*)bwd_ps_kernel<NT_, true, G>, hipFuncAttributeMaxDynamicSharedMemorySize, kExclusiveLds); \
-        hipLaunchKernelGGL((bwd_ps_kernel<NT_, true, G>), wgrid, wblock, kExclusiveLds, st, (const uint16_t*)dy_bf16, gates, hseq, \
-                           (const uint16_t*)whhT_bf16, (uint16_t*)dgi_bf16, (uint16_t*)dgh_bf16, db_ih, db_hh, (unsigned*)sync_ws, \
-                           T, B, H, ndir, mode == 10 ? 1 : 0, boff, Bn);                                                  \
-    } while (0)
-#define ASR_BWDPS(NT_)                                                                                                    \
-    do {                                                                                                                  \
-        if (gates_f16) ASR_BWDPS_(NT_, true); else ASR_BWDPS_(NT_, false);                                                \
-    } while (0)
-            switch (H / 128) {
-                case 1: ASR_BWDPS(1); break;
-                case 2: ASR_BWDPS(2); break;
-                case 3: ASR_BWDPS(3); break;
-                case 4: ASR_BWDPS(4); break;
-                case 8: ASR_BWDPS(8); break;
-                default: return ASR_ERR_UNSUPPORTED;
-            }
-#undef ASR_BWDPS
-#undef ASR_BWDPS_
+            if (!kernel) return ASR_ERR_UNSUPPORTED;
+            launch_lds(kernel, kExclusiveLds, dim3(nrec_pad * (H / 32)), dim3(640), kExclusiveLds, st, (const uint16_t*)dy_bf16, gates, hseq,
+                       (const uint16_t*)whhT_bf16, (uint16_t*)dgi_bf16, (uint16_t*)dgh_bf16, db_ih, db_hh, (unsigned*)sync_ws, T, B, H, ndir,
+                       p.forge, boff, Bn);
             ASR_LAUNCH_CHECK();
         }
         return ASR_OK;
     }
-    // wide form (32 units x 4-row recurrences): every other persistent case
-    if (persist && db_ih && db_hh && H >= 64 && ndir * ((B + 3) / 4) <= 16) {
-        const int Gw = (B + 3) / 4, nrec = ndir * Gw, nrec_pad = (nrec + 7) & ~7;
-        const int ks8 = (3 * H / 32 + 7) / 8;
-        if (ks8 <= 6) {
-            if (!clear_sync(sync_ws, kShardBytes, st)) return ASR_ERR_LAUNCH;
-            const bool local = mode == 0 || mode == 4 || mode == 7 || mode == 8;
-            const int forge = (mode == 7 ? 1 : (mode == 0 || mode == 8 ? 8 : 0));     // 8: data polling (mode 4: flag line)
-            if ((forge & 8) && hipMemsetAsync(dgh_bf16, 0xff, (size_t)T * B * ndir * 3 * H * 2, st) != hipSuccess) return ASR_ERR_LAUNCH;
-            const dim3 wgrid = local ? dim3(nrec_pad * (H / 32)) : dim3(H / 32, Gw, ndir), wblock(640);
-#define ASR_BWDW(K)                                                                                                       \
-    do {                                                                                                                  \
-        if (local) {                                                                                                      \
-            (void)hipFuncSetAttribute((const void*)bwd_wide_kernel<K, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kExclusiveLds); \
-            hipLaunchKernelGGL((bwd_wide_kernel<K, true>), wgrid, wblock, kExclusiveLds, st, (const uint16_t*)dy_bf16, gates, hseq, \
-                               (const uint16_t*)whhT_bf16, (uint16_t*)dgi_bf16, (uint16_t*)dgh_bf16, db_ih, db_hh,                \
-                               (unsigned*)sync_ws, T, B, H, ndir, forge);                                                         \
-        } else {                                                                                                          \
-            (void)hipFuncSetAttribute((const void*)bwd_wide_kernel<K, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kPersistLds); \
-            hipLaunchKernelGGL((bwd_wide_kernel<K, false>), wgrid, wblock, kPersistLds, st, (const uint16_t*)dy_bf16, gates, hseq, \
-                               (const uint16_t*)whhT_bf16, (uint16_t*)dgi_bf16, (uint16_t*)dgh_bf16, db_ih, db_hh,                \
-                               (unsigned*)sync_ws, T, B, H, ndir, 0);                                                             \
-        }                                                                                                                 \
-    } while (0)
-            if (ks8 <= 2) ASR_BWDW(2); else if (ks8 <= 3) ASR_BWDW(3); else if (ks8 <= 4) ASR_BWDW(4); else if (ks8 <= 5) ASR_BWDW(5); else ASR_BWDW(6);
-#undef ASR_BWDW
-            ASR_LAUNCH_CHECK();
-            return ASR_OK;
-        }
+    if (p.form == WIDE) {
+        const int Gw = (B + 3) / 4, nrec_pad = (ndir * Gw + 7) & ~7;
+        if (!clear_sync(sync_ws, kShardBytes, st)) return ASR_ERR_LAUNCH;
+        if ((p.forge & 8) && hipMemsetAsync(dgh_bf16, 0xff, (size_t)T * B * ndir * 3 * H * 2, st) != hipSuccess) return ASR_ERR_LAUNCH;
+        const dim3 wgrid = p.local ? dim3(nrec_pad * (H / 32)) : dim3(H / 32, Gw, ndir), wblock(640);
+        const int lds = p.local ? kExclusiveLds : kPersistLds;
+        launch_lds(bwd_wide_instance(H, p.local), lds, wgrid, wblock, lds, st, (const uint16_t*)dy_bf16, gates, hseq, (const uint16_t*)whhT_bf16,
+                   (uint16_t*)dgi_bf16, (uint16_t*)dgh_bf16, db_ih, db_hh, (unsigned*)sync_ws, T, B, H, ndir, p.local ? p.forge : 0);
+        ASR_LAUNCH_CHECK();
+        return ASR_OK;
     }
-    if (mode >= 2) return ASR_ERR_UNSUPPORTED;       // (no persistent kernel serves this shape; modes >= 2 do not fall back)
-    if (ksw > 12) return ASR_ERR_UNSUPPORTED;        // (the per-step kernel holds at most 12 K steps per wave: H <= 512)
-    for (int s = 0; s < T; ++s) {
-#define ASR_BWD(K) hipLaunchKernelGGL(bwd_step_kernel<K>, grid, block, 0, st, (const uint16_t*)dy_bf16, gates, hseq, \
-                                      (const uint16_t*)whhT_bf16, (uint16_t*)dgi_bf16, (uint16_t*)dgh_bf16, carry_ws, T, B, H, ndir, s, (const float*)nullptr, 0)
-        if (ksw <= 2) ASR_BWD(2); else if (ksw <= 6) ASR_BWD(6); else ASR_BWD(12);
-#undef ASR_BWD
-    }
+    bwd_steps(st, dy_bf16, gates, hseq, nullptr, whhT_bf16, dgi_bf16, dgh_bf16, carry_ws, 0, T, B, H, ndir);
     ASR_LAUNCH_CHECK();
-    // bias gradients (the persistent kernels sum them in registers; here a column sum over all (t, b) rows)
-    if (db_ih) {
-        const int rc2 = asr_colsum_acc(stream, dgi_bf16, 1, (long long)T * B, ndir * 3 * H, ndir * 3 * H, db_ih);
-        if (rc2 != ASR_OK) return rc2;
-    }
-    if (db_hh) {
-        const int rc2 = asr_colsum_acc(stream, dgh_bf16, 1, (long long)T * B, ndir * 3 * H, ndir * 3 * H, db_hh);
-        if (rc2 != ASR_OK) return rc2;
-    }
-    return ASR_OK;
+    return bias_colsums(stream, dgi_bf16, dgh_bf16, db_ih, db_hh, T, B, H, ndir);
 }
 
 // ---------------------------------------------------------------------------------------------- a layer with a given initial state
@@ -2622,34 +2650,14 @@ extern "C" int asr_gru_fwd_state(void* stream, const float* gi, const void* whh_
                                  void* hseq_bf16, float* gates, void* y_bf16, int T, int B, int H, int ndir, const int* x_len) {
     if (ASR_ACT_IS_F16) return ASR_ERR_UNSUPPORTED;
     if (!gi || !whh_bf16 || !bhh || !hseq || !hseq_bf16 || !gates) return ASR_ERR_BAD_ARG;
-    const int rc = check_dims(T, B, H, ndir);
+    int rc = check_dims(T, B, H, ndir);
     if (rc != ASR_OK) return rc;
-    const int ksw = (H / 32 + 3) / 4;
-    if (ksw > 8 || (H % 8)) return ASR_ERR_UNSUPPORTED;
+    if ((H / 32 + 3) / 4 > 8) return ASR_ERR_UNSUPPORTED;       // H <= 1024
     hipStream_t st = (hipStream_t)stream;
-    if (x_len) {
-        if ((long long)T * B > 0x7fffffffLL) return ASR_ERR_UNSUPPORTED;
-        hipLaunchKernelGGL(pin_update_gate_kernel<float>, dim3((unsigned)(T * B)), dim3(256), 0, st, (float*)gi, x_len, B, H, ndir);
-        ASR_LAUNCH_CHECK();
-    }
-    const dim3 grid(H / 16, ndir), block(256);
-    for (int s = 0; s < T; ++s) {
-#define ASR_FWD(K) hipLaunchKernelGGL(fwd_step_kernel<K>, grid, block, 0, st, gi, (const uint16_t*)whh_bf16, bhh, hseq, \
-                                      (uint16_t*)hseq_bf16, gates, T, B, H, ndir, s, hx)
-        if (ksw <= 1) ASR_FWD(1); else if (ksw <= 2) ASR_FWD(2); else if (ksw <= 4) ASR_FWD(4); else ASR_FWD(8);
-#undef ASR_FWD
-    }
+    if (x_len && (rc = pin_update_gate(st, (void*)gi, false, x_len, T, B, H, ndir)) != ASR_OK) return rc;
+    fwd_steps(st, gi, whh_bf16, bhh, hx, hseq, hseq_bf16, gates, T, B, H, ndir);
     ASR_LAUNCH_CHECK();
-    if (y_bf16) {
-        const bool vec = ((((uintptr_t)hseq) | ((uintptr_t)y_bf16)) & 15) == 0;
-        const long long n = (long long)T * B * (vec ? H / 8 : H);
-        long long g = (n + 255) / 256;
-        if (g > 4096) g = 4096;
-        if (vec) hipLaunchKernelGGL(merge_dirs_vec_kernel, dim3((unsigned)g), dim3(256), 0, st, hseq, (uint16_t*)y_bf16, (long long)T * B, H, ndir, x_len, B);
-        else hipLaunchKernelGGL(merge_dirs_kernel, dim3((unsigned)g), dim3(256), 0, st, hseq, (uint16_t*)y_bf16, (long long)T * B, H, ndir, x_len, B);
-        ASR_LAUNCH_CHECK();
-    }
-    return ASR_OK;
+    return y_bf16 ? merge_dirs(st, hseq, y_bf16, T, B, H, ndir, x_len) : ASR_OK;
 }
 
 extern "C" int asr_gru_bwd_state(void* stream, const void* dy_bf16, const float* gates, const float* hseq, const float* hx, const float* dhy,
@@ -2657,28 +2665,16 @@ extern "C" int asr_gru_bwd_state(void* stream, const void* dy_bf16, const float*
                                  float* dhx, int T, int B, int H, int ndir, const int* x_len, void* dy_ws) {
     if (ASR_ACT_IS_F16) return ASR_ERR_UNSUPPORTED;
     if (!dy_bf16 || !gates || !hseq || !whhT_bf16 || !dgi_bf16 || !dgh_bf16 || !carry_ws) return ASR_ERR_BAD_ARG;
-    const int rc = check_dims(T, B, H, ndir);
+    int rc = check_dims(T, B, H, ndir);
     if (rc != ASR_OK) return rc;
-    const int ksw = (3 * H / 32 + 3) / 4;
-    if (ksw > 12 || (H % 8)) return ASR_ERR_UNSUPPORTED;        // (the per-step kernel holds at most 12 K steps per wave: H <= 512)
+    if ((3 * H / 32 + 3) / 4 > 12) return ASR_ERR_UNSUPPORTED;      // (the per-step kernel holds at most 12 K steps per wave: H <= 512)
     hipStream_t st = (hipStream_t)stream;
     if (x_len) {
-        if (!dy_ws) return ASR_ERR_BAD_ARG;
-        const long long n = (long long)T * B * (H / 8);
-        long long g = (n + 255) / 256;
-        if (g > 8192) g = 8192;
-        hipLaunchKernelGGL(mask_rows_kernel, dim3((unsigned)g), dim3(256), 0, st, (const uint16_t*)dy_bf16, (uint16_t*)dy_ws, x_len, (long long)T * B, B, H / 8);
-        ASR_LAUNCH_CHECK();
+        if ((rc = mask_dy(st, dy_bf16, dy_ws, x_len, T, B, H)) != ASR_OK) return rc;
         dy_bf16 = dy_ws;
     }
     if (dhy && hipMemcpyAsync(carry_ws, dhy, (size_t)ndir * B * H * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return ASR_ERR_LAUNCH;
-    const dim3 grid(H / 16, ndir), block(256);
-    for (int s = 0; s < T; ++s) {
-#define ASR_BWD(K) hipLaunchKernelGGL(bwd_step_kernel<K>, grid, block, 0, st, (const uint16_t*)dy_bf16, gates, hseq, (const uint16_t*)whhT_bf16, \
-                                      (uint16_t*)dgi_bf16, (uint16_t*)dgh_bf16, carry_ws, T, B, H, ndir, s, hx, dhy ? 1 : 0)
-        if (ksw <= 2) ASR_BWD(2); else if (ksw <= 6) ASR_BWD(6); else ASR_BWD(12);
-#undef ASR_BWD
-    }
+    bwd_steps(st, dy_bf16, gates, hseq, hx, whhT_bf16, dgi_bf16, dgh_bf16, carry_ws, dhy ? 1 : 0, T, B, H, ndir);
     ASR_LAUNCH_CHECK();
     if (dhx) {
         const long long total = (long long)ndir * B * H;
@@ -2686,13 +2682,5 @@ extern "C" int asr_gru_bwd_state(void* stream, const void* dy_bf16, const float*
                            (const float*)carry_ws, dhx, T, B, H, ndir);
         ASR_LAUNCH_CHECK();
     }
-    if (db_ih) {
-        const int rc2 = asr_colsum_acc(stream, dgi_bf16, 1, (long long)T * B, ndir * 3 * H, ndir * 3 * H, db_ih);
-        if (rc2 != ASR_OK) return rc2;
-    }
-    if (db_hh) {
-        const int rc2 = asr_colsum_acc(stream, dgh_bf16, 1, (long long)T * B, ndir * 3 * H, ndir * 3 * H, db_hh);
-        if (rc2 != ASR_OK) return rc2;
-    }
-    return ASR_OK;
+    return bias_colsums(stream, dgi_bf16, dgh_bf16, db_ih, db_hh, T, B, H, ndir);
 }
