@@ -76,6 +76,11 @@ SIGNATURES = {
     "asr_argmax_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "asr_ctc_collapse": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_void_p] * 2),
     "asr_edit_distance": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "asr_edit_align_workspace_bytes": (c_size_t, [c_int] * 3),
+    "asr_edit_align": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 4 + [c_size_t]),
+    "asr_nbest_pairwise_distance": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p]),
+    "asr_nbest_consensus_workspace_bytes": (c_size_t, [c_int] * 3),
+    "asr_nbest_consensus": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p, c_void_p, c_size_t]),
     "asr_ctc_beam_workspace_bytes": (c_size_t, [c_int] * 5),
     "asr_ctc_beam_search": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_float, c_void_p, c_size_t] + [c_void_p] * 3),
     "asr_ngram_score": (c_int, [c_void_p] * 2 + [c_int, c_void_p, c_void_p] + [c_int] * 3 + [c_void_p] * 2 + [c_int] * 4 + [c_void_p] * 2),

@@ -757,6 +757,62 @@ def edit_distance(ref, ref_len, hyp, hyp_len):
     return dist
 
 
+def edit_align(ref, ref_len, hyp, hyp_len, paths=True, budget=None):
+    """row-wise edit alignment of two padded int32 id matrices (asr_edit_align) -> (counts (pairs, 4) int32: distance,
+    substitutions, deletions, insertions; ref_to_hyp (pairs, ref_pitch) int32; hyp_to_ref (pairs, hyp_pitch) int32), the maps None
+    without `paths`.  With `paths` the back-pointer workspace of one launch stays within `budget` bytes (None: one launch): the
+    pairs are split over several launches that reuse it; a single pair beyond the budget still gets its launch."""
+    pairs, rp, hp = ref.shape[0], ref.shape[1], hyp.shape[1]
+    dev = ref.device
+    counts = torch.empty((pairs, 4), dtype=I32, device=dev)
+    rmap = torch.empty((pairs, rp), dtype=I32, device=dev) if paths else None
+    hmap = torch.empty((pairs, hp), dtype=I32, device=dev) if paths else None
+    if pairs == 0:
+        return counts, rmap, hmap
+    lib = _lib.lib()
+    step = pairs
+    if paths and budget is not None:
+        step = max(1, min(pairs, int(budget) // max(1, lib.asr_edit_align_workspace_bytes(1, rp, hp))))
+    nbytes = lib.asr_edit_align_workspace_bytes(step, rp, hp) if paths else 0
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev) if paths else None
+    for s in range(0, pairs, step):
+        e = min(pairs, s + step)
+        rc = lib.asr_edit_align(stream(), ptr(ref[s:e]), ptr(ref_len[s:e]), rp, ptr(hyp[s:e]), ptr(hyp_len[s:e]), hp, e - s,
+                                ptr(counts[s:e]), ptr(rmap[s:e]) if paths else None, ptr(hmap[s:e]) if paths else None, ptr(ws), nbytes)
+        check(rc, "asr_edit_align")
+    return counts, rmap, hmap
+
+
+def nbest_pairwise_distance(ids, lens):
+    """ids (B, N, L) int32, lens (B, N) int32 (negative: unused slot) -> (B, N, N) int32 Levenshtein distances between the slots of
+    every utterance (asr_nbest_pairwise_distance): symmetric, diagonal 0, rows and columns of unused slots 0."""
+    B, N, L = ids.shape
+    dist = torch.empty((B, N, N), dtype=I32, device=ids.device)
+    if dist.numel():
+        check(_lib.lib().asr_nbest_pairwise_distance(stream(), ptr(ids), ptr(lens), B, N, L, ptr(dist)), "asr_nbest_pairwise_distance")
+    return dist
+
+
+def nbest_consensus(ids, lens, pivot, post, budget=None):
+    """ids (B, N, L) int32, lens (B, N) int32 (negative: unused), pivot (B) int32 (-1: none), post (B, N) f32 -> conf (B, L) f32: the
+    posterior mass of the slots whose token aligned to position l of the pivot equals the pivot's (asr_nbest_consensus).  The
+    workspace of one launch stays within `budget` bytes (None: one launch): the utterances are split over several launches."""
+    B, N, L = ids.shape
+    conf = torch.empty((B, L), dtype=torch.float32, device=ids.device)
+    if conf.numel() == 0 or N == 0:
+        return conf.zero_()
+    lib = _lib.lib()
+    step = B if budget is None else max(1, min(B, int(budget) // max(1, lib.asr_nbest_consensus_workspace_bytes(1, N, L))))
+    nbytes = lib.asr_nbest_consensus_workspace_bytes(step, N, L)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=ids.device)
+    for s in range(0, B, step):
+        e = min(B, s + step)
+        rc = lib.asr_nbest_consensus(stream(), ptr(ids[s:e]), ptr(lens[s:e]), ptr(pivot[s:e]), ptr(post[s:e]), e - s, N, L,
+                                     ptr(conf[s:e]), ptr(ws), nbytes)
+        check(rc, "asr_nbest_consensus")
+    return conf
+
+
 def _min_logp(min_logp):
     """the candidate threshold as the C entries take it: None is no threshold"""
     return float("-inf") if min_logp is None else float(min_logp)

@@ -5,6 +5,8 @@ the Levenshtein distances of the whole minibatch on the GPU (``libasr_hip``: asr
 back only one distance and two lengths per utterance; given host arrays it moves them to the GPU first.  There is no CPU
 implementation of the batch path here (the CPU restatement lives in ``oracle/text.py``, test infrastructure).
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -315,22 +317,27 @@ class GramBeamStream(_Stream):
         return (out[0][:, :, :2 * self.fed],) + out[1:]
 
 
+def _retokenised(pred, pred_len, BLANK, vocab_token_to_id, vocab_id_to_token):
+    """collapsed predictions as unigram ids: themselves, unless the inventory has multi-unigram tokens (asr/error.py:49-53)"""
+    if not _needs_retokenisation(vocab_id_to_token, vocab_token_to_id):
+        return pred, pred_len
+    # string work: inherently host side (only for inventories with multi-unigram tokens)
+    dev = pred.device
+    ph, pl = pred.cpu().numpy(), pred_len.cpu().numpy()
+    rows = []
+    for b in range(ph.shape[0]):
+        sentence = "".join(vocab_id_to_token[int(i)] for i in ph[b, :pl[b]])
+        rows.append(convert_sentence_to_unigram_ids(sentence, vocab_token_to_id))
+    width = max(1, max(len(r) for r in rows))
+    host = np.full((len(rows), width), BLANK, dtype=np.int32)
+    for b, r in enumerate(rows):
+        host[b, :len(r)] = r
+    return torch.from_numpy(host).to(dev), torch.tensor([len(r) for r in rows], dtype=torch.int32, device=dev)
+
+
 def _error_rate(pred, pred_len, true, true_len, BLANK, vocab_token_to_id, vocab_id_to_token, print_sequences):
     """mean over the batch of Levenshtein(pred, true) / len(true) for collapsed id rows on the GPU (asr/error.py:49-68)"""
-    dev = pred.device
-    if _needs_retokenisation(vocab_id_to_token, vocab_token_to_id):
-        # string work: inherently host side (only for inventories with multi-unigram tokens)
-        ph, pl = pred.cpu().numpy(), pred_len.cpu().numpy()
-        rows = []
-        for b in range(ph.shape[0]):
-            sentence = "".join(vocab_id_to_token[int(i)] for i in ph[b, :pl[b]])
-            rows.append(convert_sentence_to_unigram_ids(sentence, vocab_token_to_id))
-        width = max(1, max(len(r) for r in rows))
-        host = np.full((len(rows), width), BLANK, dtype=np.int32)
-        for b, r in enumerate(rows):
-            host[b, :len(r)] = r
-        pred = torch.from_numpy(host).to(dev)
-        pred_len = torch.tensor([len(r) for r in rows], dtype=torch.int32, device=dev)
+    pred, pred_len = _retokenised(pred, pred_len, BLANK, vocab_token_to_id, vocab_id_to_token)
     dist = _ops.edit_distance(true, true_len, pred, pred_len)
     d, n = dist.cpu().numpy().astype(np.float64), true_len.cpu().numpy()
     _ops.gru_check_all()        # the ids came from a forward pass nobody else checks: raise if a recurrence gave up a wait
@@ -374,3 +381,128 @@ def compute_sequence_error(pred, pred_len, t_batch, BLANK, vocab_token_to_id, vo
     t = _device_ids(t_batch, dev)
     true, true_len = _ops.ctc_collapse(t, None, BLANK, False)
     return _error_rate(p, pl, true, true_len, BLANK, vocab_token_to_id, vocab_id_to_token, print_sequences)
+
+
+# ------------------------------------------------------------------------------------------ edit alignment, counts, consensus
+# Back-pointer bytes one launch of asr_edit_align / asr_nbest_consensus may ask for; beyond it the wrappers split the pairs (the
+# utterances) over several launches that reuse the same workspace.  One cell is one byte, stored diagonal by diagonal in
+# (Lr + Lh - 1) * min(Lr, Lh) bytes per pair: 256 MiB hold 2048 pairs of 256 x 256.
+ALIGN_WORKSPACE_BUDGET = 256 << 20
+
+EditAlignment = collections.namedtuple("EditAlignment", "distance substitutions deletions insertions ref_to_hyp hyp_to_ref")
+ErrorCounts = collections.namedtuple("ErrorCounts", "substitutions deletions insertions reference_length")
+MBR = collections.namedtuple("MBR", "ids lengths index risk posterior confidence")
+
+
+def _id_rows(a, a_len, dev):
+    """a padded id matrix and its lengths as contiguous int32 device tensors -> (ids, at least one column wide; lengths, which
+    the kernel clamps to [0, L]; L)"""
+    a, a_len = _device_ids(a, dev), _device_ids(a_len, dev)
+    if a.dim() != 2 or tuple(a_len.shape) != (a.shape[0],):
+        raise ValueError("ids must be (pairs, L) and lengths (pairs)")
+    L = a.shape[1]
+    if L == 0:          # no column to point at: one of padding, and every length 0
+        a, a_len = torch.zeros((a.shape[0], 1), dtype=torch.int32, device=dev), torch.zeros_like(a_len)
+    return a, a_len, L
+
+
+def edit_alignment(ref, ref_len, hyp, hyp_len, paths=True):
+    """Row-wise Levenshtein alignment of two padded int32 id matrices ref (pairs, Lr) / ref_len (pairs) and hyp (pairs, Lh) /
+    hyp_len (pairs) on the GPU -> ``EditAlignment(distance, substitutions, deletions, insertions, ref_to_hyp, hyp_to_ref)`` of
+    device tensors: four (pairs) int32 counts with distance = substitutions + deletions + insertions; ref_to_hyp (pairs, Lr) the
+    hypothesis position aligned to each reference position by a match or a substitution, -1 where the position is deleted or
+    beyond the length; hyp_to_ref (pairs, Lh) likewise, -1 for an insertion.  Lengths are clamped to [0, L]; ids beyond them are
+    never read.  ``paths=False`` returns the same counts, None for the maps, and needs no workspace.
+
+    Several alignments reach the same distance (``ab`` against ``ba``: two substitutions, or a deletion and an insertion around
+    either match); the one reported walks back from the ends and takes, in this order, a match, a substitution, a deletion, an
+    insertion.  The back-pointers take (Lr + Lh - 1) * min(Lr, Lh) bytes per pair: beyond
+    ``ALIGN_WORKSPACE_BUDGET`` bytes the pairs are split over several launches.  Lr above 5460 (the sweep's diagonals live in LDS) raises ``AsrHipError``."""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    r, rl, Lr = _id_rows(ref, ref_len, dev)
+    h, hl, Lh = _id_rows(hyp, hyp_len, dev)
+    if r.shape[0] != h.shape[0]:
+        raise ValueError("ref and hyp must have one row per pair")
+    counts, rmap, hmap = _ops.edit_align(r, rl, h, hl, paths, ALIGN_WORKSPACE_BUDGET)
+    if paths:
+        rmap, hmap = rmap[:, :Lr], hmap[:, :Lh]
+    return EditAlignment(counts[:, 0], counts[:, 1], counts[:, 2], counts[:, 3], rmap, hmap)
+
+
+def error_counts(pred, pred_len, true, true_len):
+    """Substitutions, deletions, insertions and reference length per utterance -> ``ErrorCounts`` of four (B) int32 device tensors:
+    pred (B, L) / pred_len (B) collapsed hypotheses, true (B, L') / true_len (B) the transcripts they are aligned against
+    (``edit_alignment``'s pinned path, no maps).  S + D + I is the Levenshtein distance ``compute_minibatch_error`` divides by the
+    reference length."""
+    a = edit_alignment(true, true_len, pred, pred_len, paths=False)
+    dev = a.distance.device
+    n_ref = _device_ids(true_len, dev).clamp(0, _device_ids(true, dev).shape[1])
+    return ErrorCounts(a.substitutions, a.deletions, a.insertions, n_ref)
+
+
+def compute_minibatch_error_counts(y_batch, t_batch, BLANK, vocab_token_to_id, vocab_id_to_token):
+    """The arguments of ``compute_minibatch_error`` and the same collapse and retokenisation -> ``ErrorCounts`` of four Python
+    ints, the totals over the minibatch: what a corpus-level error rate (S + D + I) / N_ref and its breakdown are summed from."""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    y = _device_ids(y_batch, dev)
+    t = _device_ids(t_batch, dev)
+    pred, pred_len = _ops.ctc_collapse(y, None, BLANK, True)
+    true, true_len = _ops.ctc_collapse(t, None, BLANK, False)
+    pred, pred_len = _retokenised(pred, pred_len, BLANK, vocab_token_to_id, vocab_id_to_token)
+    totals = torch.stack(error_counts(pred, pred_len, true, true_len)).sum(dim=1).cpu()
+    _ops.gru_check_all()        # as in compute_minibatch_error: the ids came from a forward pass nobody else checks
+    return ErrorCounts(*(int(v) for v in totals))
+
+
+def mbr_decode(ids, lengths, scores, scale=1.0, confidence=True):
+    """Minimum-Bayes-risk pick from an N-best list, the decode-side dual of ``asr.loss.mwer_loss``: ids (B, N, L) int32, lengths
+    (B, N) int32 and scores (B, N) float exactly as ``beam_decode``, ``beam_decode_lm``, ``beam_decode_biased``, ``gram_beam_decode*``
+    or a ``*Stream.result()`` return them (for the searches with more scores, pass the one to rank by).  A slot is used iff its
+    score is finite; an empty hypothesis with a finite score is a hypothesis.  With post = softmax(scale * scores) over the used
+    slots and dist the Levenshtein distance between slots,
+
+        risk[b, i] = sum_j post[b, j] dist[b, i, j]   (+inf for an unused i),      index[b] = argmin_i risk[b, i]
+
+    (ties to the lowest index; -1 where no slot is used): the hypothesis with the least expected number of errors under the
+    list's own posterior.  -> ``MBR(ids (B, L), lengths (B), index (B) int32, risk (B, N) f64, posterior (B, N) f64, confidence
+    (B, L) f32 or None)``; ids / lengths are the chosen slot's (slot 0's ids with length 0 where index is -1).  confidence[b, l]
+    is the posterior mass of the hypotheses that, aligned against the chosen one by ``edit_alignment``'s rule, carry the same
+    token at its position l (0 at and beyond its length): a token confidence over competing hypotheses, which ``ctc_align``'s
+    acoustic log-probability is not.  For a Gram-CTC list the units are characters.
+
+    Beam scores are lower bounds on log p(hypothesis | x): the beam drops paths.  ``asr.loss.ctc_nbest_logp`` /
+    ``gram_ctc_nbest_logp`` give the exact ones, to be passed as `scores`.  The distances and the confidence are integer kernels
+    (asr_nbest_pairwise_distance, asr_nbest_consensus, in launches of at most ``ALIGN_WORKSPACE_BUDGET`` workspace bytes); the
+    (B, N) arithmetic is float64 torch on the device, as in ``mwer_parts``.  Nothing here synchronises with the host.  The
+    consensus workspace grows with L squared: a caller who can afford one synchronisation cuts the T-wide ids of a search to the
+    longest hypothesis first, as ``mwer_loss`` does (B = 32, N = 16: 0.55 ms instead of 1.16 ms at L = 1000)."""
+    if ids.dim() != 3 or tuple(lengths.shape) != tuple(ids.shape[:2]) or tuple(scores.shape) != tuple(ids.shape[:2]):
+        raise ValueError("ids must be (B, N, L), lengths and scores (B, N)")
+    if ids.dtype != torch.int32 or lengths.dtype != torch.int32:
+        raise TypeError("ids and lengths must be int32")
+    B, N, L = ids.shape
+    if N == 0:
+        raise ValueError("the list has no slots")
+    dev = ids.device
+    if L == 0:
+        ids = torch.zeros((B, N, 1), dtype=torch.int32, device=dev)
+    ids = ids.contiguous()
+    used = torch.isfinite(scores)
+    lens = torch.where(used, lengths.clamp(0, L), torch.full_like(lengths, -1)).contiguous()
+    dist = _ops.nbest_pairwise_distance(ids, lens)
+    s = torch.where(used, float(scale) * scores.double(), torch.full_like(scores, float("-inf"), dtype=torch.float64))
+    top = s.max(dim=1, keepdim=True).values
+    e = torch.where(used, torch.exp(s - torch.where(torch.isfinite(top), top, torch.zeros_like(top))), torch.zeros_like(s))
+    z = e.sum(dim=1, keepdim=True)
+    post = e / torch.where(z > 0, z, torch.ones_like(z))
+    risk = torch.where(used, (post[:, None, :] * dist.double()).sum(dim=2), torch.full_like(post, float("inf")))
+    slot = torch.arange(N, device=dev)[None, :].expand(B, N)
+    first = torch.where(risk == risk.min(dim=1, keepdim=True).values, slot, torch.full_like(slot, N)).min(dim=1).values
+    index = torch.where(used.any(dim=1), first, torch.full_like(first, -1)).to(torch.int32)
+    pick = index.clamp_min(0).long()
+    out_ids = ids.gather(1, pick[:, None, None].expand(B, 1, ids.shape[2]))[:, 0, :L]
+    out_len = torch.where(index >= 0, lens.gather(1, pick[:, None])[:, 0], torch.zeros_like(index))
+    conf = None
+    if confidence:
+        conf = _ops.nbest_consensus(ids, lens, index.contiguous(), post.to(torch.float32).contiguous(), ALIGN_WORKSPACE_BUDGET)[:, :L]
+    return MBR(out_ids, out_len, index, risk, post, conf)

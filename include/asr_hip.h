@@ -182,6 +182,41 @@ int asr_ctc_collapse(void* stream, const int32_t* ids, const int32_t* lengths, i
                      int32_t* out, int32_t* out_len);
 int asr_edit_distance(void* stream, const int32_t* ref, const int32_t* ref_len, int ref_pitch, const int32_t* hyp,
                       const int32_t* hyp_len, int hyp_pitch, int pairs, int32_t* dist);
+/* Edit alignment and N-best consensus: the table of asr_edit_distance with the path kept.  The reference
+ * has neither (asr/error.py:7-24 returns one rate).  Lengths are clamped to [0, pitch]; ids beyond a length are never read.
+ * Several alignments reach the same distance; the one reported is pinned: from (i, j) = (len(r), len(h)) back to (0, 0),
+ * i == 0: insertion; j == 0: deletion; r[i-1] == h[j-1]: match; d[i][j] == d[i-1][j-1] + 1: substitution;
+ * d[i][j] == d[i-1][j] + 1: deletion; otherwise insertion.
+ *   asr_edit_align   per (reference, hypothesis) pair of `pairs` id rows:
+ *        counts     (pairs, 4)          distance, substitutions, deletions, insertions of the pinned path
+ *        ref_to_hyp (pairs, ref_pitch)  the hypothesis position aligned to reference position i (match or substitution), -1 where
+ *                                       it is deleted and at i >= len(r); may be NULL
+ *        hyp_to_ref (pairs, hyp_pitch)  likewise, -1 for an insertion and at j >= len(h); may be NULL
+ *        workspace  asr_edit_align_workspace_bytes(pairs, ref_pitch, hyp_pitch) = pairs * (ref_pitch + hyp_pitch - 1) *
+ *                   min(ref_pitch, hyp_pitch) bytes (one back-pointer byte per cell, stored diagonal by diagonal); with both
+ *                   maps NULL no back-pointers are kept and workspace may be NULL
+ *   asr_nbest_pairwise_distance   ids (B, N, pitch), lens (B, N) read in place -> dist (B, N, N), dist[b][i][j] the Levenshtein
+ *        distance of slots i and j of utterance b: symmetric, diagonal 0; one workgroup per unordered pair.  A slot with a
+ *        negative length is unused: its row and column are 0
+ *   asr_nbest_consensus   every used slot j of utterance b is aligned against slot pivot[b] (the reference) by the rule above;
+ *        conf (B, pitch) f32: conf[b][l] = sum over j in index order of post[b][j] where slot j's token aligned to position l
+ *        equals the pivot's; 0 at l >= the pivot's length, and for the whole row where pivot[b] is outside [0, N) (-1: no
+ *        pivot) or names an unused slot.  No atomics: bitwise reproducible.
+ *        workspace  asr_nbest_consensus_workspace_bytes(B, N, pitch) = B * N * 2 * pitch * pitch bytes (back-pointers, then one
+ *                   agreement byte per slot and position)
+ * The sweep holds three diagonals of pitch + 1 ints in LDS: ref_pitch (pitch) > 5460 is ASR_ERR_UNSUPPORTED, as for
+ * asr_edit_distance; so are hyp_pitch >= 2^19 (asr_edit_align packs the distance beside a 13-bit count), more than 2^31 - 1
+ * workgroups and, for asr_nbest_consensus, B > 65535.  NULL (but for the optional maps) or non-positive arguments:
+ * ASR_ERR_BAD_ARG; a short workspace: ASR_ERR_WORKSPACE.  The workspace queries run on the host and return 0 for an empty
+ * problem. */
+size_t asr_edit_align_workspace_bytes(int pairs, int ref_pitch, int hyp_pitch);
+int asr_edit_align(void* stream, const int32_t* ref, const int32_t* ref_len, int ref_pitch, const int32_t* hyp,
+                   const int32_t* hyp_len, int hyp_pitch, int pairs, int32_t* counts, int32_t* ref_to_hyp, int32_t* hyp_to_ref,
+                   void* workspace, size_t workspace_bytes);
+int asr_nbest_pairwise_distance(void* stream, const int32_t* ids, const int32_t* lens, int B, int N, int pitch, int32_t* dist);
+size_t asr_nbest_consensus_workspace_bytes(int B, int N, int pitch);
+int asr_nbest_consensus(void* stream, const int32_t* ids, const int32_t* lens, const int32_t* pivot, const float* post, int B,
+                        int N, int pitch, float* conf, void* workspace, size_t workspace_bytes);
 /* CTC prefix beam search: the N-best counterpart of the greedy decode above (xp.argmax at run/ctc/cnn/dev.py:102-106 and
  * run/ctc/cnn/test.py:102, then the collapse of asr/error.py:38-47); the reference has no beam decoder.  Log-space prefix beam
  * search over (T, B, V) f32 pre-softmax logits (the CTC loss's input), frames < lengths[b] (NULL: all T; later frames are never
