@@ -113,6 +113,12 @@ SIGNATURES = {
                                         + [c_int] * 5 + [c_void_p, c_size_t] + [c_void_p] * 6),
     "asr_ctc_align_workspace_bytes": (c_size_t, [c_int] * 5),
     "asr_ctc_align": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p] * 9 + [c_size_t]),
+    "asr_kws_workspace_bytes": (c_size_t, [c_int] * 3),
+    "asr_kws_state_bytes": (c_size_t, [c_int] * 3),
+    "asr_kws_state_reset": (c_int, [c_void_p] * 2 + [c_int] * 3 + [c_void_p]),
+    "asr_kws_detect": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 5
+                       + [c_size_t]),
+    "asr_kws_hits": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_float] + [c_void_p] * 5),
     "asr_gemm_nt": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p] + [c_int] * 4),
     "asr_gemm_nt_8ph_ok": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int]),
     "asr_gemm_nt_8ph": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int]),

@@ -1086,6 +1086,55 @@ def ctc_align(xs, label_unigram, label_bigram, x_len, l_len, blank):
     return frames, tok[0], tok[1], tok[2], tok[3], tok_logp, n_tok, score
 
 
+def kws_state(B, K, Lmax, device):
+    """the carried state of a keyword stream, reset for every utterance: asr_kws_state_bytes rounded UP to whole 8-byte words
+    (the size is 24 B K Lmax + 4 B bytes: not a multiple of 8 for odd B), int64 so that its float64 part is aligned"""
+    nbytes = _lib.lib().asr_kws_state_bytes(int(B), int(K), int(Lmax))
+    state = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.int64, device=device)
+    return kws_state_reset(state, B, K, Lmax, None)
+
+
+def kws_state_reset(state, B, K, Lmax, mask):
+    """asr_kws_state_reset: mask (B) int32 or None (all utterances)"""
+    check(_lib.lib().asr_kws_state_reset(stream(), ptr(state), int(B), int(K), int(Lmax), ptr(mask)), "asr_kws_state_reset")
+    return state
+
+
+def kws_detect(logits, lengths, blank, image, state=None):
+    """(T, B, V) f32 logits + the keyword image of asr/spot.py (uniq (U), node_tok (K, Lmax), kw_len (K) int32 on the device) ->
+    det (B, K, T) f32, det_start (B, K, T) int32, fill (B, T) f32 of asr_kws_detect; lengths (B) int32 or None; state: None (one
+    shot) or the tensor of kws_state"""
+    T, B, V = logits.shape
+    uniq, node_tok, kw_len = image["uniq"], image["node_tok"], image["kw_len"]
+    K, Lmax = node_tok.shape
+    U = uniq.numel()
+    dev = logits.device
+    nbytes = _lib.lib().asr_kws_workspace_bytes(T, B, U)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    det = torch.empty((B, K, T), dtype=F32, device=dev)
+    det_start = torch.empty((B, K, T), dtype=I32, device=dev)
+    fill = torch.empty((B, T), dtype=F32, device=dev)
+    rc = _lib.lib().asr_kws_detect(stream(), ptr(logits), ptr(lengths), T, B, V, int(blank), ptr(uniq), U, ptr(node_tok), ptr(kw_len),
+                                   K, Lmax, ptr(state), ptr(det), ptr(det_start), ptr(fill), ptr(ws), nbytes)
+    check(rc, "asr_kws_detect")
+    return det, det_start, fill
+
+
+def kws_hits(det, det_start, fill, lengths, max_hits, min_score):
+    """asr_kws_hits on the outputs of kws_detect -> hit_start, hit_end (B, K, max_hits) int32, hit_score, hit_logp (B, K, max_hits)
+    f32, n_hits (B, K) int32"""
+    B, K, T = det.shape
+    dev = det.device
+    H = int(max_hits)
+    hs, he = (torch.empty((B, K, H), dtype=I32, device=dev) for _ in range(2))
+    sc, lp = (torch.empty((B, K, H), dtype=F32, device=dev) for _ in range(2))
+    n = torch.empty((B, K), dtype=I32, device=dev)
+    rc = _lib.lib().asr_kws_hits(stream(), ptr(det), ptr(det_start), ptr(fill), ptr(lengths), B, K, T, H, float(min_score), ptr(hs),
+                                 ptr(he), ptr(sc), ptr(lp), ptr(n))
+    check(rc, "asr_kws_hits")
+    return hs, he, sc, lp, n
+
+
 def cmn_pspec(pspec, nframes):
     B, Fmax, nbins = pspec.shape
     check(_lib.lib().asr_cmn_pspec(stream(), ptr(pspec), ptr(nframes), B, Fmax, nbins), "asr_cmn_pspec")

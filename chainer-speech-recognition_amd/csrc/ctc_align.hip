@@ -24,6 +24,7 @@
 #include "common.hpp"
 #include "ctc_ws.hpp"
 #include "ctc_lattice.hpp"
+#include "ctc_rows.hpp"
 #include "../../include/asr_hip.h"
 
 namespace asr {
@@ -79,29 +80,8 @@ __global__ __launch_bounds__(256) void gather_kernel(const float* __restrict__ x
     const int xl = x_len ? min(x_len[b], T) : T;
     if (t >= xl) return;
     const float* x = xs + (size_t)row * V;
-    float m = -INFINITY;
-    const bool vec = ((V & 3) == 0) && ((((uintptr_t)x) & 15) == 0);
-    if (vec) {
-        const float4* x4 = reinterpret_cast<const float4*>(x);
-        for (int i = threadIdx.x; i < (V >> 2); i += blockDim.x) {
-            const float4 v = x4[i];
-            m = fmaxf(m, fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)));
-        }
-    } else {
-        for (int i = threadIdx.x; i < V; i += blockDim.x) m = fmaxf(m, x[i]);
-    }
-    m = block_max(m, scratch);
-    float sum = 0.f;
-    if (vec) {
-        const float4* x4 = reinterpret_cast<const float4*>(x);
-        for (int i = threadIdx.x; i < (V >> 2); i += blockDim.x) {
-            const float4 v = x4[i];
-            sum += __expf(v.x - m) + __expf(v.y - m) + __expf(v.z - m) + __expf(v.w - m);
-        }
-    } else {
-        for (int i = threadIdx.x; i < V; i += blockDim.x) sum += __expf(x[i] - m);
-    }
-    sum = block_sum(sum, scratch);
+    float m, sum;
+    asr::ctc::row_max_sumexp(x, V, scratch, m, sum);                 // shared with the keyword search (csrc/ctc_rows.hpp)
     if (threadIdx.x == 0) lse_out[row] = m + __logf(sum);
     const int* pl = path_label + (size_t)b * Sp;
     float* out = xg + ((size_t)b * T + t) * Sp;

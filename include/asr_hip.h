@@ -252,6 +252,52 @@ int asr_ctc_align(void* stream, const float* xs, const int32_t* label_unigram, c
                   const int32_t* l_len, int T, int B, int V, int Lmax, int blank, int32_t* frame_ids, int32_t* tok_ids,
                   int32_t* tok_pos, int32_t* tok_start, int32_t* tok_end, float* tok_logp, int32_t* n_tok, float* score,
                   void* workspace, size_t workspace_bytes);
+/* CTC keyword spotting: does utterance b contain keyword k, on which frames, and how sure is the model.  A
+ * free-boundary Viterbi search over the keyword's own lattice tok_1, blk_2, tok_2, .., blk_L, tok_L (no leading or trailing blank),
+ * K keywords by B utterances per call; the logits are read once whatever K is.  The reference has no keyword search.  CTC only.
+ * With xmax[t] the f32 maximum of row t and c(t, v) = (double)x[t][v] - (double)xmax[t], for t in [0, xl), xl = min(lengths[b], T)
+ * (NULL: T), every value -inf and every start -1 before the first frame:
+ *   tok_1[t] = c(t, w_1)   + best(tok_1[t-1], fresh start (0.0, start = t))
+ *   blk_i[t] = c(t, blank) + best(blk_i[t-1], tok_{i-1}[t-1])
+ *   tok_i[t] = c(t, w_i)   + best(tok_i[t-1], blk_i[t-1], tok_{i-1}[t-1] only if w_i != w_{i-1})
+ * in float64, one addition per step; `best` takes the first maximum in the order written and the start travels with it.
+ * Keyword image (asr/spot.py builds it on the host):
+ *   uniq (U) i32          the distinct token ids of all keywords (an id outside [0, V) reads as -inf)
+ *   node_tok (K, Lmax)    the index into uniq of token i of keyword k; -1 where padded, and everywhere in a keyword without a path
+ *   kw_len (K)            tokens of keyword k; a keyword with kw_len outside [1, Lmax] or a node_tok outside [0, U) below kw_len has
+ *                         no path: its det is -inf and its starts are -1 everywhere
+ * asr_kws_detect -- every element of every output is written on every call:
+ *   det (B, K, T) f32         (float)tok_L[t]: the best, over all starts s and all paths of the keyword on frames s..t that begin and
+ *                             end on a token, of log p(path) - log p(greedy path on s..t); <= 0; -inf for t >= xl
+ *   det_start (B, K, T) i32   the start frame s of that path; -1 where det is -inf
+ *   fill (B, T) f32           xmax[t] - lse[t], the greedy path's log-probability of the frame (lse as asr_ctc_align forms it); 0 for
+ *                             t >= xl
+ *   state                     NULL: one shot.  Otherwise asr_kws_state_bytes(B, K, Lmax) bytes, 8-byte aligned, initialised by
+ *                             asr_kws_state_reset (mask (B) i32: only the utterances with a non-zero entry; NULL: all): the call
+ *                             continues from the carried node values, starts and frame count of every utterance and stores them
+ *                             back; lengths are then the valid frames of this chunk and det_start counts the utterance's own frames
+ *                             since its last reset.  However the frames are cut, the outputs over the valid frames are bit for bit
+ *                             those of one call.
+ *   workspace                 asr_kws_workspace_bytes(T, B, U) bytes
+ * asr_kws_hits -- non-maximum suppression per (b, k), up to max_hits rounds: among the frames e < xl whose det is finite, >=
+ * min_score (-INFINITY: no threshold) and whose span [det_start[e], e] meets no recorded span, take the largest det (ties: the
+ * smaller start, then the larger e) and record it:
+ *   hit_start, hit_end (B, K, max_hits) i32   the span [start, end): end = e + 1;   unused slots -1
+ *   hit_score, hit_logp (B, K, max_hits) f32  det[e], and (float)((double)det[e] + the float64 sum of fill[start .. e], left to
+ *                                             right): the log-probability of the best path of the occurrence; unused slots -inf
+ *   n_hits (B, K) i32
+ * Lmax > 64 (one wave owns a lattice), max_hits > 4096 and more than 2^31 - 1 workgroups: ASR_ERR_UNSUPPORTED.  NULL (but for
+ * lengths, state, mask) or non-positive arguments: ASR_ERR_BAD_ARG.  All checks precede the first launch; no host synchronisation;
+ * bitwise reproducible.  The two queries run on the host and return 0 for an empty problem. */
+size_t asr_kws_workspace_bytes(int T, int B, int U);
+size_t asr_kws_state_bytes(int B, int K, int Lmax);
+int asr_kws_state_reset(void* stream, void* state, int B, int K, int Lmax, const int32_t* mask);
+int asr_kws_detect(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank, const int32_t* uniq,
+                   int U, const int32_t* node_tok, const int32_t* kw_len, int K, int Lmax, void* state, float* det,
+                   int32_t* det_start, float* fill, void* workspace, size_t workspace_bytes);
+int asr_kws_hits(void* stream, const float* det, const int32_t* det_start, const float* fill, const int32_t* lengths, int B, int K,
+                 int T, int max_hits, float min_score, int32_t* hit_start, int32_t* hit_end, float* hit_score, float* hit_logp,
+                 int32_t* n_hits);
 /* Back-off n-gram language model over token ids (order 1-4, natural log, ARPA semantics) and the beam search fused with it
  * (asr/lm.py builds and uploads the image).  The reference has no language model.
  * Image:
