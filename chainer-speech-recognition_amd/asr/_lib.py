@@ -119,6 +119,10 @@ SIGNATURES = {
     "asr_kws_detect": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 5
                        + [c_size_t]),
     "asr_kws_hits": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_float] + [c_void_p] * 5),
+    "asr_gram_kws_state_bytes": (c_size_t, [c_int] * 3),
+    "asr_gram_kws_state_reset": (c_int, [c_void_p] * 2 + [c_int] * 3 + [c_void_p]),
+    "asr_gram_kws_detect": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int]
+                            + [c_void_p] * 5 + [c_size_t]),
     "asr_gemm_nt": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p] + [c_int] * 4),
     "asr_gemm_nt_8ph_ok": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int]),
     "asr_gemm_nt_8ph": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int]),

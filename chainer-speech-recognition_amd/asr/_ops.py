@@ -1120,6 +1120,41 @@ def kws_detect(logits, lengths, blank, image, state=None):
     return det, det_start, fill
 
 
+def gram_kws_state(B, K, Lmax, device):
+    """kws_state for the Gram-CTC search: asr_gram_kws_state_bytes (36 B K Lmax + 4 B bytes: three nodes per position) rounded UP
+    to whole 8-byte words"""
+    nbytes = _lib.lib().asr_gram_kws_state_bytes(int(B), int(K), int(Lmax))
+    state = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.int64, device=device)
+    return gram_kws_state_reset(state, B, K, Lmax, None)
+
+
+def gram_kws_state_reset(state, B, K, Lmax, mask):
+    """asr_gram_kws_state_reset: mask (B) int32 or None (all utterances)"""
+    check(_lib.lib().asr_gram_kws_state_reset(stream(), ptr(state), int(B), int(K), int(Lmax), ptr(mask)),
+          "asr_gram_kws_state_reset")
+    return state
+
+
+def gram_kws_detect(logits, lengths, blank, image, state=None):
+    """kws_detect for a GramKeywordSet image (uniq (U), node_uni, node_big (K, Lmax), kw_len (K) int32 on the device) -> det,
+    det_start, fill of asr_gram_kws_detect; state: None (one shot) or the tensor of gram_kws_state"""
+    T, B, V = logits.shape
+    uniq, node_uni, node_big, kw_len = image["uniq"], image["node_uni"], image["node_big"], image["kw_len"]
+    K, Lmax = node_uni.shape
+    U = uniq.numel()
+    dev = logits.device
+    nbytes = _lib.lib().asr_kws_workspace_bytes(T, B, U)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    det = torch.empty((B, K, T), dtype=F32, device=dev)
+    det_start = torch.empty((B, K, T), dtype=I32, device=dev)
+    fill = torch.empty((B, T), dtype=F32, device=dev)
+    rc = _lib.lib().asr_gram_kws_detect(stream(), ptr(logits), ptr(lengths), T, B, V, int(blank), ptr(uniq), U, ptr(node_uni),
+                                        ptr(node_big), ptr(kw_len), K, Lmax, ptr(state), ptr(det), ptr(det_start), ptr(fill),
+                                        ptr(ws), nbytes)
+    check(rc, "asr_gram_kws_detect")
+    return det, det_start, fill
+
+
 def kws_hits(det, det_start, fill, lengths, max_hits, min_score):
     """asr_kws_hits on the outputs of kws_detect -> hit_start, hit_end (B, K, max_hits) int32, hit_score, hit_logp (B, K, max_hits)
     f32, n_hits (B, K) int32"""

@@ -20,6 +20,17 @@
 //                                    det of the kTile frames is collected one lane per frame and written as one coalesced store.
 //   hits   (B*K workgroups)          non-maximum suppression: block arg-max by (det desc, start asc, end desc), max_hits rounds
 //   reset  (B*K workgroups)          the carried state of a stream: values -inf, starts -1, frames consumed 0
+//
+// The Gram-CTC form (asr_gram_kws_detect) searches a phrase of characters c_1..c_L over every way of cutting it
+// into unigram and bigram tokens at once: position i has the nodes U_i (the token spelled c_i), G_i (the token spelled c_{i-1} c_i,
+// i >= 2) and B_i (the blank between positions i-1 and i, i >= 2) -- the edges of ctc_lattice.hpp's prep_kernel<true> with its two
+// guards, minus the outer blanks, plus a fresh start into U_1 and G_2:
+//   B_i[t] = c(t, blank) + best(B_i[t-1], U_{i-1}[t-1], G_{i-1}[t-1])
+//   U_i[t] = c(t, u_i)   + best(U_i[t-1], B_i[t-1], U_{i-1}[t-1] only if c_i != c_{i-1}, G_{i-1}[t-1])
+//   G_i[t] = c(t, g_i)   + best(G_i[t-1], B_{i-1}[t-1], U_{i-2}[t-1], G_{i-2}[t-1] only if g_i != g_{i-2})
+//   det[t] = (float)best(U_L[t], G_L[t])
+// rows, hits and the workspace are the ones above (uniq simply holds bigram token ids too); the sweep is gram_sweep_kernel: lane i-1
+// owns U_i, G_i and B_i, five values and five starts cross lanes per step, still without a barrier.
 #include "common.hpp"
 #include "ctc_rows.hpp"
 #include "../../include/asr_hip.h"
@@ -31,6 +42,7 @@ constexpr int kGroup = 4;        // keywords (waves) per sweep workgroup        
 constexpr int kTile = 32;        // frames per register tile of the sweep        (asr/spot.py: SWEEP_TILE)
 constexpr int kMaxLen = 64;      // one token and its blank per lane
 constexpr int kMaxHits = 4096;   // spans kept in LDS by the hits kernel
+constexpr int kGramTile = 32;    // frames per register tile of the Gram sweep   (asr/spot.py: GRAM_SWEEP_TILE)
 
 struct Workspace {
     float* xmax;     // (B, T)
@@ -54,18 +66,19 @@ static Workspace carve(void* ws, int T, int B, int U) {
     return w;
 }
 
-// the carried state: per (b, k) the float64 values of tok and blk (2 * Lmax), their int starts (2 * Lmax); per b the frames consumed
+// the carried state: per (b, k) the float64 values of the `nodes` nodes of every position (CTC: tok, blk; Gram-CTC: U, B, G), their
+// int starts; per b the frames consumed
 struct State {
-    double* val;     // (B, K, 2, Lmax)
-    int* start;      // (B, K, 2, Lmax)
+    double* val;     // (B, K, nodes, Lmax)
+    int* start;      // (B, K, nodes, Lmax)
     int* consumed;   // (B)
     size_t bytes;
 };
 
-static State carve_state(void* st, int B, int K, int Lmax) {
+static State carve_state(void* st, int B, int K, int Lmax, int nodes = 2) {
     State s;
     char* p = (char*)st;
-    const size_t n = (size_t)B * K * 2 * Lmax;
+    const size_t n = (size_t)B * K * nodes * Lmax;
     s.val = (double*)p;
     s.start = (int*)(p ? p + sizeof(double) * n : nullptr);
     s.consumed = (int*)(p ? p + (sizeof(double) + sizeof(int)) * n : nullptr);
@@ -227,13 +240,176 @@ __global__ __launch_bounds__(kGroup * 64) void sweep_kernel(const float* __restr
     }
 }
 
+// ------------------------------------------------------------------------------------------------ gram sweep
+// the first maximum of (a, b): b wins only if it is strictly larger, the start travels with the winner
+__device__ __forceinline__ void first_max(double a, int as, double b, int bs, double& m, int& s) {
+    m = __builtin_fmax(a, b);
+    s = b > a ? bs : as;
+}
+// `best` of four candidates in the order written, as a tree: the first maximum of (a, b), the first maximum of (c, d), and the
+// second pair wins only if it is strictly larger -- the same winner as the left-to-right scan, two max deep instead of three
+__device__ __forceinline__ void best4(double a, int as, double b, int bs, double c, int cs, double d, int ds, double& m, int& s) {
+    double l, r;
+    int ls, rs;
+    first_max(a, as, b, bs, l, ls);
+    first_max(c, cs, d, ds, r, rs);
+    first_max(l, ls, r, rs, m, s);
+}
+
+// One wave per (b, k) lattice; lane p owns position i = p + 1: U_i, G_i (p >= 1) and B_i (p >= 1).  From lane p - 1 come U, G and B,
+// from lane p - 2 come U and G.  What __shfl_up hands the lanes below its distance is the lane's OWN value, so:
+//   lane 0, distance 1   the U slot is the fresh start of U_1; its G and B slots are lane 0's own G and B, which do not exist and
+//                        are -inf from the reset on (their cost is -inf on every frame)
+//   lane 1, distance 2   the U slot is the fresh start of G_2, the G slot is masked to -inf (its own G_2 is live)
+//   lane 0, distance 2   feeds only G_1, which does not exist: whatever arrives is added to a cost of -inf
+// An absent node (no such token in the inventory) has cost -inf, so its value stays -inf; a node whose new value is -inf gets start
+// -1, which also keeps the starts of absent nodes and of the lanes >= L at -1 although a live neighbour hands them one.
+__global__ __launch_bounds__(kGroup * 64) void gram_sweep_kernel(const float* __restrict__ xmax, const float* __restrict__ xblank,
+                                                                 const float* __restrict__ xg, const int* __restrict__ x_len,
+                                                                 const int* __restrict__ node_uni, const int* __restrict__ node_big,
+                                                                 const int* __restrict__ kw_len, const int* __restrict__ base, int T,
+                                                                 int B, int U, int K, int Lmax, double* __restrict__ st_val,
+                                                                 int* __restrict__ st_start, float* __restrict__ det,
+                                                                 int* __restrict__ det_start) {
+    const int lane = threadIdx.x & 63;
+    const int groups = (K + kGroup - 1) / kGroup;
+    const int b = blockIdx.x / groups;
+    const int k = __builtin_amdgcn_readfirstlane((blockIdx.x - b * groups) * kGroup + (int)(threadIdx.x >> 6));
+    if (k >= K) return;                    // whole waves leave; nothing below waits for another wave
+    const int xl = x_len ? min(max(x_len[b], 0), T) : T;
+    const int L = __builtin_amdgcn_readfirstlane(kw_len[k]);
+    const bool okL = L >= 1 && L <= Lmax;
+    float* dk = det + ((size_t)b * K + k) * T;
+    int* sk = det_start + ((size_t)b * K + k) * T;
+    int done = 0;                          // frames of this call whose det is written
+
+    if (okL && xl > 0) {
+        const bool mine = lane < L;
+        const bool first = lane == 0, second = lane == 1;
+        int iu = mine ? node_uni[(size_t)k * Lmax + lane] : -1;
+        int ig = mine && !first ? node_big[(size_t)k * Lmax + lane] : -1;
+        iu = iu >= 0 && iu < U ? iu : -1;                            // absent nodes: one spelling
+        ig = ig >= 0 && ig < U ? ig : -1;
+        const bool has_u = iu >= 0, has_g = ig >= 0, has_b = mine && !first;
+        // the guards: uniq is one to one with the token ids, so equal indices are equal characters / equal bigrams; where a node
+        // is absent the guard is moot (one side of the edge is -inf).  The shuffles stand alone: behind a short-circuit they would
+        // run with the source lanes switched off.
+        const int iu1 = __shfl_up(iu, 1, 64), ig2 = __shfl_up(ig, 2, 64);
+        const bool same_u = !first && has_u && iu == iu1;                           // c_i == c_{i-1}
+        const bool same_g = lane >= 2 && has_g && ig == ig2;                        // g_i == g_{i-2}
+        const int t_base = base[b];
+        const size_t so = ((size_t)b * K + k) * 3 * Lmax + lane;
+        double uv = -INFINITY, bv = -INFINITY, gv = -INFINITY;
+        int us = -1, bs = -1, gs = -1;
+        if (st_val && lane < Lmax) {
+            uv = st_val[so];
+            bv = st_val[so + Lmax];
+            gv = st_val[so + 2 * Lmax];
+            us = st_start[so];
+            bs = st_start[so + Lmax];
+            gs = st_start[so + 2 * Lmax];
+        }
+        const float* gxu = xg + (size_t)b * T * U + (has_u ? iu : 0);
+        const float* gxg = xg + (size_t)b * T * U + (has_g ? ig : 0);
+        const float* mb = xmax + (size_t)b * T;
+        const float* bb = xblank + (size_t)b * T;
+        const int last = xl - 1;
+        float xcu[kGramTile], xcg[kGramTile], xnu[kGramTile], xng[kGramTile];
+#pragma unroll
+        for (int j = 0; j < kGramTile; ++j) {
+            xcu[j] = gxu[(size_t)min(j, last) * U];
+            xcg[j] = gxg[(size_t)min(j, last) * U];
+        }
+        float mc = mb[min(lane, last)], bc = bb[min(lane, last)];     // lane j holds frame t0 + j of the tile
+        const int Lm1 = L - 1;
+        for (int t0 = 0; t0 < xl; t0 += kGramTile) {
+            const int n = min(kGramTile, xl - t0);
+#pragma unroll
+            for (int j = 0; j < kGramTile; ++j) {                     // the next tile, clamped
+                xnu[j] = gxu[(size_t)min(t0 + kGramTile + j, last) * U];
+                xng[j] = gxg[(size_t)min(t0 + kGramTile + j, last) * U];
+            }
+            const float mn = mb[min(t0 + kGramTile + lane, last)], bn = bb[min(t0 + kGramTile + lane, last)];
+            const double cb_l = (double)bc - (double)mc;             // c(t, blank) of the lane's frame
+            float keep_v = -INFINITY;
+            int keep_s = -1;
+#pragma unroll
+            for (int j = 0; j < kGramTile; ++j) {
+                if (j < n) {                                         // uniform
+                    // the costs: formed beside the chain (they do not depend on the carried values)
+                    const double cm = (double)bcast_f(mc, j);
+                    const double cu = has_u ? (double)xcu[j] - cm : -INFINITY;
+                    const double cg = has_g ? (double)xcg[j] - cm : -INFINITY;
+                    const double cb = has_b ? bcast_d(cb_l, j) : -INFINITY;
+                    const int now = t_base + t0 + j;
+                    // the chain: neighbours across lanes, max, one add; the selects carry the starts
+                    double u1 = __shfl_up(uv, 1, 64), g1 = __shfl_up(gv, 1, 64), b1 = __shfl_up(bv, 1, 64);
+                    int u1s = __shfl_up(us, 1, 64), g1s = __shfl_up(gs, 1, 64), b1s = __shfl_up(bs, 1, 64);
+                    double u2 = __shfl_up(uv, 2, 64), g2 = __shfl_up(gv, 2, 64);
+                    int u2s = __shfl_up(us, 2, 64), g2s = __shfl_up(gs, 2, 64);
+                    u1 = first ? 0.0 : u1;                           // the fresh start of U_1
+                    u1s = first ? now : u1s;
+                    u2 = second ? 0.0 : u2;                          // the fresh start of G_2
+                    u2s = second ? now : u2s;
+                    g2 = lane < 2 ? -INFINITY : g2;                  // there is no G_0 (and no G_{-1})
+                    const double u1g = same_u ? -INFINITY : u1;
+                    const double g2g = same_g ? -INFINITY : g2;
+                    double r, nb, nu, ng;
+                    int rs, nbs, nus, ngs;
+                    first_max(u1, u1s, g1, g1s, r, rs);              // B_i: stay, U_{i-1}, G_{i-1}
+                    first_max(bv, bs, r, rs, nb, nbs);
+                    best4(uv, us, bv, bs, u1g, u1s, g1, g1s, nu, nus);
+                    best4(gv, gs, b1, b1s, u2, u2s, g2g, g2s, ng, ngs);
+                    uv = cu + nu;
+                    bv = cb + nb;
+                    gv = cg + ng;
+                    us = uv == -INFINITY ? -1 : nus;
+                    bs = bv == -INFINITY ? -1 : nbs;
+                    gs = gv == -INFINITY ? -1 : ngs;
+                    double dl;                                       // det: best(U_L, G_L), both in lane L - 1
+                    int dls;
+                    first_max(uv, us, gv, gs, dl, dls);
+                    const float dv = (float)bcast_d(dl, Lm1);
+                    const int dsv = __builtin_amdgcn_readlane(dls, Lm1);
+                    keep_v = lane == j ? dv : keep_v;
+                    keep_s = lane == j ? dsv : keep_s;
+                }
+            }
+            if (lane < n) {
+                dk[t0 + lane] = keep_v;
+                sk[t0 + lane] = keep_s;
+            }
+#pragma unroll
+            for (int j = 0; j < kGramTile; ++j) {
+                xcu[j] = xnu[j];
+                xcg[j] = xng[j];
+            }
+            mc = mn;
+            bc = bn;
+        }
+        if (st_val && lane < Lmax) {
+            st_val[so] = uv;
+            st_val[so + Lmax] = bv;
+            st_val[so + 2 * Lmax] = gv;
+            st_start[so] = us;
+            st_start[so + Lmax] = bs;
+            st_start[so + 2 * Lmax] = gs;
+        }
+        done = xl;
+    }
+    for (int t = done + lane; t < T; t += 64) {                      // frames past the length; every frame of a phrase without a path
+        dk[t] = -INFINITY;
+        sk[t] = -1;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ reset
 __global__ __launch_bounds__(128) void reset_kernel(double* __restrict__ val, int* __restrict__ start, int* __restrict__ consumed,
-                                                    const int* __restrict__ mask, int K, int Lmax) {
+                                                    const int* __restrict__ mask, int K, int per) {      // per = nodes * Lmax
     const int bk = blockIdx.x, b = bk / K;
     if (mask && mask[b] == 0) return;
-    const size_t o = (size_t)bk * 2 * Lmax;
-    for (int i = threadIdx.x; i < 2 * Lmax; i += blockDim.x) {
+    const size_t o = (size_t)bk * per;
+    for (int i = threadIdx.x; i < per; i += blockDim.x) {
         val[o + i] = -INFINITY;
         start[o + i] = -1;
     }
@@ -336,7 +512,8 @@ extern "C" int asr_kws_state_reset(void* stream_, void* state, int B, int K, int
     if (!state || B <= 0 || K <= 0 || Lmax <= 0) return ASR_ERR_BAD_ARG;
     if (Lmax > kMaxLen || too_many((long long)B * K)) return ASR_ERR_UNSUPPORTED;
     State s = carve_state(state, B, K, Lmax);
-    hipLaunchKernelGGL(reset_kernel, dim3(B * K), dim3(128), 0, (hipStream_t)stream_, s.val, s.start, s.consumed, mask, K, Lmax);
+    hipLaunchKernelGGL(reset_kernel, dim3(B * K), dim3(128), 0, (hipStream_t)stream_, s.val, s.start, s.consumed, mask, K,
+                       2 * Lmax);
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }
@@ -362,7 +539,44 @@ extern "C" int asr_kws_detect(void* stream_, const float* logits, const int32_t*
     return ASR_OK;
 }
 
-extern "C" int asr_kws_hits(void* stream_, const float* det, const int32_t* det_start, const float* fill, const int32_t* lengths,
+extern "C" size_t asr_gram_kws_state_bytes(int B, int K, int Lmax) {
+    if (B <= 0 || K <= 0 || Lmax <= 0) return 0;
+    return carve_state(nullptr, B, K, Lmax, 3).bytes;
+}
+
+extern "C" int asr_gram_kws_state_reset(void* stream_, void* state, int B, int K, int Lmax, const int32_t* mask) {
+    if (!state || B <= 0 || K <= 0 || Lmax <= 0) return ASR_ERR_BAD_ARG;
+    if (Lmax > kMaxLen || too_many((long long)B * K)) return ASR_ERR_UNSUPPORTED;
+    State s = carve_state(state, B, K, Lmax, 3);
+    hipLaunchKernelGGL(reset_kernel, dim3(B * K), dim3(128), 0, (hipStream_t)stream_, s.val, s.start, s.consumed, mask, K,
+                       3 * Lmax);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+extern "C" int asr_gram_kws_detect(void* stream_, const float* logits, const int32_t* lengths, int T, int B, int V, int blank,
+                                   const int32_t* uniq, int U, const int32_t* node_uni, const int32_t* node_big,
+                                   const int32_t* kw_len, int K, int Lmax, void* state, float* det, int32_t* det_start, float* fill,
+                                   void* workspace, size_t workspace_bytes) {
+    if (!logits || !uniq || !node_uni || !node_big || !kw_len || !det || !det_start || !fill || !workspace) return ASR_ERR_BAD_ARG;
+    if (T <= 0 || B <= 0 || V <= 0 || U <= 0 || K <= 0 || Lmax <= 0 || blank < 0 || blank >= V) return ASR_ERR_BAD_ARG;
+    const long long groups = (K + kGroup - 1) / kGroup;
+    if (Lmax > kMaxLen || too_many((long long)T * B) || too_many((long long)B * groups)) return ASR_ERR_UNSUPPORTED;
+    Workspace w = carve(workspace, T, B, U);
+    if (workspace_bytes < w.bytes) return ASR_ERR_WORKSPACE;
+    State s = carve_state(state, B, K, Lmax, 3);
+    hipStream_t stream = (hipStream_t)stream_;
+    hipLaunchKernelGGL(rows_kernel, dim3(T * B), dim3(256), 0, stream, logits, lengths, uniq, T, B, V, U, blank,
+                       state ? s.consumed : nullptr, w.xmax, w.xblank, w.xg, w.base, fill);
+    ASR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(gram_sweep_kernel, dim3((unsigned)(B * groups)), dim3(kGroup * 64), 0, stream, w.xmax, w.xblank, w.xg, lengths,
+                       node_uni, node_big, kw_len, w.base, T, B, U, K, Lmax, state ? s.val : nullptr, state ? s.start : nullptr,
+                       det, det_start);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+extern "C" int asr_kws_hits(void* stream_,const float* det, const int32_t* det_start, const float* fill, const int32_t* lengths,
                             int B, int K, int T, int max_hits, float min_score, int32_t* hit_start, int32_t* hit_end,
                             float* hit_score, float* hit_logp, int32_t* n_hits) {
     if (!det || !det_start || !fill || !hit_start || !hit_end || !hit_score || !hit_logp || !n_hits) return ASR_ERR_BAD_ARG;

@@ -254,7 +254,8 @@ int asr_ctc_align(void* stream, const float* xs, const int32_t* label_unigram, c
                   void* workspace, size_t workspace_bytes);
 /* CTC keyword spotting: does utterance b contain keyword k, on which frames, and how sure is the model.  A
  * free-boundary Viterbi search over the keyword's own lattice tok_1, blk_2, tok_2, .., blk_L, tok_L (no leading or trailing blank),
- * K keywords by B utterances per call; the logits are read once whatever K is.  The reference has no keyword search.  CTC only.
+ * K keywords by B utterances per call; the logits are read once whatever K is.  The reference has no keyword search.  This is the
+ * CTC form over token ids; asr_gram_kws_detect below searches a spelled phrase over every Gram-CTC decomposition.
  * With xmax[t] the f32 maximum of row t and c(t, v) = (double)x[t][v] - (double)xmax[t], for t in [0, xl), xl = min(lengths[b], T)
  * (NULL: T), every value -inf and every start -1 before the first frame:
  *   tok_1[t] = c(t, w_1)   + best(tok_1[t-1], fresh start (0.0, start = t))
@@ -298,6 +299,37 @@ int asr_kws_detect(void* stream, const float* logits, const int32_t* lengths, in
 int asr_kws_hits(void* stream, const float* det, const int32_t* det_start, const float* fill, const int32_t* lengths, int B, int K,
                  int T, int max_hits, float min_score, int32_t* hit_start, int32_t* hit_end, float* hit_score, float* hit_logp,
                  int32_t* n_hits);
+/* Gram-CTC keyword spotting over spelled strings: the phrase is a string of characters c_1..c_L (unigram
+ * ids), and one lattice holds every way of cutting it into unigram and bigram tokens.  With u_i the token spelled (c_i) and g_i
+ * (i >= 2) the token spelled (c_{i-1}, c_i), either of which the inventory may lack, position i has the nodes U_i, G_i (i >= 2)
+ * and B_i (the blank between positions i-1 and i, i >= 2); no leading or trailing blank.  c(t, v), xl, the float64 max-plus step
+ * and the (-inf, -1) before the first frame are those of asr_kws_detect; an absent node keeps (-inf, -1):
+ *   U_1[t] = c(t, u_1)   + best(U_1[t-1], fresh start (0.0, start = t))
+ *   G_2[t] = c(t, g_2)   + best(G_2[t-1], fresh start (0.0, start = t))
+ *   B_i[t] = c(t, blank) + best(B_i[t-1], U_{i-1}[t-1], G_{i-1}[t-1])                                         i >= 2
+ *   U_i[t] = c(t, u_i)   + best(U_i[t-1], B_i[t-1], U_{i-1}[t-1] only if c_i != c_{i-1}, G_{i-1}[t-1])        i >= 2
+ *   G_i[t] = c(t, g_i)   + best(G_i[t-1], B_{i-1}[t-1], U_{i-2}[t-1], G_{i-2}[t-1] only if g_i != g_{i-2})    i >= 3
+ *   det[t] = (float)best(U_L[t], G_L[t]), det_start[t] the winner's start
+ * `best` takes the first maximum in the order written (a later candidate wins only if strictly larger), the start travels with
+ * the winner, and a node whose new value is -inf gets start -1.  These are the edges of the Gram-CTC loss lattice with its two
+ * guards, minus the outer blanks, plus the fresh starts.  det is the best, over all starts, all decompositions and all paths of a
+ * decomposition that begin and end on a token, of log p(path) - log p(greedy path): exactly 0.0 where the greedy path spells the
+ * phrase with any mix of unigram and bigram tokens.
+ * Image (asr/spot.py: GramKeywordSet builds it on the host):
+ *   uniq (U) i32                    the distinct token ids of all phrases, unigram and bigram tokens alike
+ *   node_uni, node_big (K, Lmax)    the index into uniq of u_i and of g_i; an index outside [0, U) means the node is absent;
+ *                                   node_big[k][0] is always absent.  The guards compare these indices (where a node is absent
+ *                                   the guard is moot)
+ *   kw_len (K)                      characters of phrase k; outside [1, Lmax] the phrase has no path: det -inf, starts -1
+ * det, det_start, fill, lengths, state, workspace (asr_kws_workspace_bytes(T, B, U)) and every refusal are as in asr_kws_detect;
+ * the state holds three nodes per position (36 bytes) and has its own query and reset.  asr_kws_hits takes the outputs as they
+ * are. */
+size_t asr_gram_kws_state_bytes(int B, int K, int Lmax);
+int asr_gram_kws_state_reset(void* stream, void* state, int B, int K, int Lmax, const int32_t* mask);
+int asr_gram_kws_detect(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank,
+                        const int32_t* uniq, int U, const int32_t* node_uni, const int32_t* node_big, const int32_t* kw_len, int K,
+                        int Lmax, void* state, float* det, int32_t* det_start, float* fill, void* workspace,
+                        size_t workspace_bytes);
 /* Back-off n-gram language model over token ids (order 1-4, natural log, ARPA semantics) and the beam search fused with it
  * (asr/lm.py builds and uploads the image).  The reference has no language model.
  * Image:
