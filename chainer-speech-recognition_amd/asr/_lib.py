@@ -111,6 +111,18 @@ SIGNATURES = {
                                          + [c_int] * 4 + [c_float, c_float, c_int, c_int] + [c_void_p, c_size_t] * 2),
     "asr_gram_ctc_beam_stream_result": (c_int, [c_void_p] * 2 + [c_int, c_void_p, c_void_p] + [c_int] * 5 + [c_float, c_float]
                                         + [c_int] * 5 + [c_void_p, c_size_t] + [c_void_p] * 6),
+    "asr_gram_ctc_beam_bias_workspace_bytes": (c_size_t, [c_int] * 5),
+    "asr_gram_ctc_beam_search_bias": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
+                                      + [c_int] * 5 + [c_float, c_float, c_void_p, c_size_t] + [c_void_p] * 7 + [c_int] * 2
+                                      + [c_void_p, c_int, c_void_p]),
+    "asr_gram_ctc_beam_bias_stream_state_bytes": (c_size_t, [c_int] * 5),
+    "asr_gram_ctc_beam_bias_stream_reset": (c_int, [c_void_p] * 2 + [c_size_t] + [c_int] * 5 + [c_void_p]),
+    "asr_gram_ctc_beam_bias_stream_advance": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_float, c_void_p, c_void_p, c_int, c_void_p,
+                                                      c_void_p] + [c_int] * 4 + [c_void_p] * 2 + [c_int] * 2 + [c_void_p, c_int]
+                                              + [c_float, c_float, c_int, c_int] + [c_void_p, c_size_t] * 2),
+    "asr_gram_ctc_beam_bias_stream_result": (c_int, [c_void_p] * 2 + [c_int, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 2
+                                             + [c_int] * 2 + [c_void_p, c_int] + [c_float, c_float] + [c_int] * 5
+                                             + [c_void_p, c_size_t] + [c_void_p] * 7),
     "asr_ctc_align_workspace_bytes": (c_size_t, [c_int] * 5),
     "asr_ctc_align": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p] * 9 + [c_size_t]),
     "asr_kws_workspace_bytes": (c_size_t, [c_int] * 3),

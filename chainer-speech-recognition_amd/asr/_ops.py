@@ -1064,6 +1064,77 @@ def gram_ctc_beam_stream_result(state, B, beam_width, max_frames, blank, Lcap, i
     return (ids, out_len) + scores, frames
 
 
+def gram_ctc_beam_search_bias(logits, lengths, blank, beam_width, top_k, gram, graph, image=None, alpha=0.0, beta=0.0, bos=-1, eos=-1,
+                              min_logp=None):
+    """gram_ctc_beam_search (image None) or gram_ctc_beam_search_lm ranked with the phrase bonus of `graph` on top
+    (asr_gram_ctc_beam_search_bias) -> (ids (B, beam_width, 2T), lengths, scores, ctc_scores, lm_scores, bias_scores); `graph`: the
+    device image of an asr.bias.ContextGraph over the unigram ids of `gram`, `image`: that of an asr.lm.NGramLM over them.  The
+    table is not checked here (asr.error.gram_beam_decode_biased does)."""
+    T, B, V = logits.shape
+    dev = logits.device
+    _check_gram(gram, V, dev)
+    ptr(logits)                                   # a CPU tensor is refused here, before anything asks for the device's stream
+    nbytes = _lib.lib().asr_gram_ctc_beam_bias_workspace_bytes(T, B, V, int(beam_width), int(top_k))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    ids, out_len, (scores, ctc, lm, bias) = _nbest_out(B, beam_width, 2 * T, dev, 4)
+    rc = _lib.lib().asr_gram_ctc_beam_search_bias(stream(), ptr(logits), ptr(lengths), T, B, V, int(blank), int(beam_width),
+                                                  int(top_k), _min_logp(min_logp), ptr(gram),
+                                                  *(_NO_LM if image is None else _lm_args(image)), int(bos), int(eos), float(alpha),
+                                                  float(beta), ptr(ws), nbytes, ptr(ids), ptr(out_len), ptr(scores), ptr(ctc),
+                                                  ptr(lm), *_graph_args(graph), ptr(bias))
+    check(rc, "asr_gram_ctc_beam_search_bias")
+    return ids, out_len, scores, ctc, lm, bias
+
+
+def gram_ctc_beam_bias_stream_state_bytes(B, beam_width, max_frames, with_lm, with_bias):
+    """bytes of the device-resident state of a streaming Gram-CTC beam search with or without a graph
+    (asr_gram_ctc_beam_bias_stream_state_bytes; host only); without one, gram_ctc_beam_stream_state_bytes"""
+    return _lib.lib().asr_gram_ctc_beam_bias_stream_state_bytes(int(B), int(beam_width), int(max_frames), int(bool(with_lm)),
+                                                                int(bool(with_bias)))
+
+
+def gram_ctc_beam_bias_stream_reset(state, B, beam_width, max_frames, with_lm, with_bias, mask=None):
+    """gram_ctc_beam_stream_reset for a state of gram_ctc_beam_bias_stream_state_bytes: asr_gram_ctc_beam_bias_stream_reset"""
+    rc = _lib.lib().asr_gram_ctc_beam_bias_stream_reset(stream(), ptr(state), state.numel(), int(B), int(beam_width), int(max_frames),
+                                                        int(bool(with_lm)), int(bool(with_bias)), ptr(mask))
+    check(rc, "asr_gram_ctc_beam_bias_stream_reset")
+
+
+def gram_ctc_beam_bias_stream_advance(state, logits, lengths, blank, beam_width, top_k, gram, frames_before, max_frames, image=None,
+                                      graph=None, alpha=0.0, beta=0.0, bos=-1, min_logp=None):
+    """gram_ctc_beam_stream_advance with `graph`, the device image of an asr.bias.ContextGraph over the unigram ids of `gram`, or
+    None (asr_gram_ctc_beam_bias_stream_advance)"""
+    Tc, B, V = logits.shape
+    _check_gram(gram, V, logits.device)
+    nbytes = _lib.lib().asr_gram_ctc_beam_stream_workspace_bytes(Tc, B, V, int(beam_width), int(top_k))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=logits.device)
+    rc = _lib.lib().asr_gram_ctc_beam_bias_stream_advance(stream(), ptr(logits), ptr(lengths), Tc, B, V, int(blank), int(beam_width),
+                                                          int(top_k), _min_logp(min_logp), ptr(gram),
+                                                          *(_NO_LM if image is None else _lm_args(image)), int(bos),
+                                                          *(_NO_GRAPH if graph is None else _graph_args(graph)), float(alpha),
+                                                          float(beta), int(frames_before), int(max_frames), ptr(state),
+                                                          state.numel(), ptr(ws), nbytes)
+    check(rc, "asr_gram_ctc_beam_bias_stream_advance")
+
+
+def gram_ctc_beam_bias_stream_result(state, B, beam_width, max_frames, blank, Lcap, image=None, graph=None, alpha=0.0, beta=0.0,
+                                     bos=-1, eos=-1):
+    """gram_ctc_beam_stream_result with `graph` (asr_gram_ctc_beam_bias_stream_result) -> ((ids (B, beam_width, Lcap), lengths,
+    scores[, ctc_scores, lm_scores[, bias_scores]]) as the one-shot search of the same variant returns them, frames (B) int32)"""
+    dev = state.device
+    n = 1 if image is None and graph is None else (3 if graph is None else 4)
+    ids, out_len, scores = _nbest_out(B, beam_width, Lcap, dev, n)
+    frames = torch.empty((B,), dtype=I32, device=dev)
+    extra = [ptr(s) for s in scores[1:]] + [None] * (4 - n)
+    rc = _lib.lib().asr_gram_ctc_beam_bias_stream_result(stream(), *(_NO_LM if image is None else _lm_args(image)), int(bos), int(eos),
+                                                         *(_NO_GRAPH if graph is None else _graph_args(graph)), float(alpha),
+                                                         float(beta), int(B), int(beam_width), int(max_frames), int(blank),
+                                                         int(Lcap), ptr(state), state.numel(), ptr(ids), ptr(out_len),
+                                                         ptr(scores[0]), *extra, ptr(frames))
+    check(rc, "asr_gram_ctc_beam_bias_stream_result")
+    return (ids, out_len) + scores, frames
+
+
 def ctc_align(xs, label_unigram, label_bigram, x_len, l_len, blank):
     """(T, B, V) f32 logits + labels (B, Lmax) int32 (label_bigram None: CTC, else Gram-CTC) -> the forced alignment
     (frame_ids (B, T), tok_ids, tok_pos, tok_start, tok_end (B, Lmax) int32, tok_logp (B, Lmax) f32, n_tok (B) int32,

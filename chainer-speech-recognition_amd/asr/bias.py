@@ -4,7 +4,8 @@ Data preparation only, like ``asr/lm.py``: this module builds the automaton with
 "default-to-root" image that ``include/asr_hip.h`` describes (one open-addressing table of transitions and the array `ret`) and
 uploads it once.  Every bonus is looked up and summed inside ``libasr_hip`` (csrc/ctxgraph.hpp: asr_ctx_score,
 asr_ctc_beam_search_bias); there is no scoring path on the CPU here (the float64 restatement is tests/ctx_bias_reference.py,
-test infrastructure).  The reference has no biasing; ``asr.error.beam_decode_biased`` is the caller.
+test infrastructure).  The reference has no biasing; ``asr.error.beam_decode_biased`` is the caller, and for a Gram-CTC model
+``asr.error.gram_beam_decode_biased``, with the graph over the unigram ids that the spelling table uses.
 """
 import math
 
@@ -47,7 +48,10 @@ class ContextGraph:
     @classmethod
     def from_text(cls, lines, token_to_id, V=None, weights=None, boost=1.0, blank=0):
         """one phrase per line, its characters mapped through `token_to_id` (the project's vocab_token_to_id); a phrase with a
-        character outside the vocabulary is dropped and counted in `.dropped`; empty lines are skipped"""
+        character outside the vocabulary is dropped and counted in `.dropped`; empty lines are skipped.  For a Gram-CTC
+        inventory (``asr.error.gram_beam_decode_biased``, ``GramBeamStream(graph=...)``) the graph runs over the unigram ids
+        that the table spells with: pass the unigram part of the vocabulary, ``from_text(lines, unigram_token_to_id, V=V)``
+        with V the size of the logits' inventory, as ``NGramLM.from_arpa`` is used for ``gram_beam_decode_lm``."""
         V = (max(token_to_id.values()) + 1) if V is None else int(V)
         phrases, kept, dropped = [], [], 0
         for i, line in enumerate(lines):

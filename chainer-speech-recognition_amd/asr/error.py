@@ -265,10 +265,41 @@ def gram_beam_decode_lm(logits, gram, lm, lm_weight, length_bonus, beam_width=16
                                         length_bonus, lm.bos_id, lm.eos_id if use_eos else -1, min_logp)
 
 
+def gram_beam_decode_biased(logits, gram, graph, lm=None, lm_weight=0.0, length_bonus=0.0, beam_width=16, top_k=16, blank=0,
+                            lengths=None, min_logp=None, use_eos=True):
+    """``gram_beam_decode`` (`lm` None) or ``gram_beam_decode_lm`` with contextual phrase biasing in the ranking while the beam is
+    open, ``beam_decode_biased`` for the Gram-CTC inventory.  `graph` is an ``asr.bias.ContextGraph`` over the unigram ids that
+    the table spells with, built for the logits' V and blank (``ContextGraph.from_text(lines, unigram_token_to_id, V=V)``; moved to
+    the logits' device on first use); a phrase with an id that no row of `gram` spells never matches.  A bigram token advances
+    the automaton by its two characters in string order, so the bonus of a string does not depend on how it was cut into tokens.
+    Strings are kept and sorted by log p_gram_ctc(s | x) + lm_weight * log p_lm(s) + length_bonus * |s| + bias(s), bias(s) the
+    sum of weight * length over every occurrence of every phrase in s.  `gram` and `lm` are validated as in
+    ``gram_beam_decode_lm``.
+    -> (ids (B, beam_width, 2T), lengths, scores (the combined score), ctc_scores, lm_scores, bias_scores), the last four
+    (B, beam_width) f32; ids, lengths and the score to rank by go into ``mbr_decode`` unchanged.  Unused slots: length 0, scores and ctc_scores
+    -inf, lm_scores and bias_scores 0.  Without `lm`, lm_scores is all 0 and `lm_weight`, `length_bonus` and `use_eos` have no
+    effect."""
+    if graph.V != logits.shape[2] or graph.blank != blank:
+        raise ValueError("the context graph was built for %d ids with blank %d, the logits have %d with blank %d"
+                         % (graph.V, graph.blank, logits.shape[2], blank))
+    table = _gram_table(gram, logits.shape[2], blank, logits.device)
+    if lm is not None and lm.vlm < logits.shape[2]:
+        raise ValueError("the language model covers %d ids, fewer than the %d of the logits" % (lm.vlm, logits.shape[2]))
+    if lengths is not None:
+        lengths = lengths.to(logits.device, torch.int32).contiguous()
+    graph = graph.to(logits.device)
+    if lm is None:
+        return _ops.gram_ctc_beam_search_bias(logits.contiguous(), lengths, blank, beam_width, top_k, table, graph.image, None, 0.0,
+                                              0.0, -1, -1, min_logp)
+    lm = lm.to(logits.device)
+    return _ops.gram_ctc_beam_search_bias(logits.contiguous(), lengths, blank, beam_width, top_k, table, graph.image, lm.image,
+                                          lm_weight, length_bonus, lm.bos_id, lm.eos_id if use_eos else -1, min_logp)
+
+
 class GramBeamStream(_Stream):
-    """``gram_beam_decode`` / ``gram_beam_decode_lm`` (`lm`) fed chunk by chunk: the beam of strings of `B` utterances lives on the
-    device between the calls.  However the frames are cut into chunks, ``result()`` after a chunk is bit for bit what the one-shot
-    function returns for the frames fed so far.
+    """``gram_beam_decode`` / ``gram_beam_decode_lm`` (`lm`) / ``gram_beam_decode_biased`` (`graph`, with or without `lm`) fed chunk
+    by chunk: the beam of strings of `B` utterances lives on the device between the calls.  However the frames are cut into
+    chunks, ``result()`` after a chunk is bit for bit what the one-shot function returns for the frames fed so far.
 
         s = GramBeamStream(B, V, max_frames, gram, beam_width=16, top_k=16, lm=lm, lm_weight=0.5, length_bonus=1.0)
         for chunk in chunks:                    # (Tc, B, V) f32 logits on the device
@@ -276,21 +307,33 @@ class GramBeamStream(_Stream):
             ids, lens, scores, ctc, lms = s.result()
 
     `gram` is validated once, here, as ``gram_beam_decode`` validates it; `lm` as in ``gram_beam_decode_lm`` (``lm.vlm < V`` raises
-    ValueError).  ``reset``, partial resets, the frame count and `max_frames` behave as in ``BeamStream``; the prefix table holds
-    two characters per frame.  Nothing here synchronises with the host."""
+    ValueError); `graph` as in ``gram_beam_decode_biased`` (built for another V or blank raises ValueError), and with it
+    ``result()`` returns the 6-tuple.  ``reset``, partial resets, the frame count and `max_frames` behave as in ``BeamStream``;
+    the prefix table holds two characters per frame.  Nothing here synchronises with the host."""
 
     def __init__(self, B, V, max_frames, gram, beam_width=16, top_k=16, blank=0, min_logp=None, lm=None, lm_weight=0.0,
-                 length_bonus=0.0, device=None):
+                 length_bonus=0.0, device=None, graph=None):
         if B <= 0 or V <= 0 or max_frames <= 0:
             raise ValueError("B, V and max_frames must be positive")
         if lm is not None and lm.vlm < V:
             raise ValueError("the language model covers %d ids, fewer than the %d of the logits" % (lm.vlm, V))
+        if graph is not None and (graph.V != V or graph.blank != blank):
+            raise ValueError("the context graph was built for %d ids with blank %d, the stream has %d with blank %d"
+                             % (graph.V, graph.blank, V, blank))
         super().__init__(B, V, max_frames, beam_width, top_k, blank, min_logp, lm, lm_weight, length_bonus, device)
         self.gram = _gram_table(gram, self.V, self.blank, self.device)
-        self._new_state(_ops.gram_ctc_beam_stream_state_bytes(B, beam_width, max_frames, lm is not None))
+        self.graph = None if graph is None else graph.to(self.device)
+        if graph is None:
+            self._new_state(_ops.gram_ctc_beam_stream_state_bytes(B, beam_width, max_frames, lm is not None))
+        else:
+            self._new_state(_ops.gram_ctc_beam_bias_stream_state_bytes(B, beam_width, max_frames, lm is not None, True))
 
     def reset(self, mask=None):
         """start every utterance over, or those with mask[b] != 0 (`mask`: (B) integers, host or device)"""
+        if self.graph is not None:
+            _ops.gram_ctc_beam_bias_stream_reset(self.state, self.B, self.beam_width, self.max_frames, self.lm is not None, True,
+                                                 self._reset_mask(mask))
+            return
         _ops.gram_ctc_beam_stream_reset(self.state, self.B, self.beam_width, self.max_frames, self.lm is not None,
                                         self._reset_mask(mask))
 
@@ -300,16 +343,30 @@ class GramBeamStream(_Stream):
         chunk = self._chunk(logits, lengths)
         if chunk is None:
             return
+        if self.graph is not None:
+            _ops.gram_ctc_beam_bias_stream_advance(self.state, chunk[0], chunk[1], self.blank, self.beam_width, self.top_k, self.gram,
+                                                   self.fed, self.max_frames, None if self.lm is None else self.lm.image,
+                                                   self.graph.image, self.lm_weight, self.length_bonus,
+                                                   -1 if self.lm is None else self.lm.bos_id, self.min_logp)
+            self.fed += chunk[0].shape[0]
+            return
         _ops.gram_ctc_beam_stream_advance(self.state, chunk[0], chunk[1], self.blank, self.beam_width, self.top_k, self.gram,
                                           self.fed, self.max_frames, None if self.lm is None else self.lm.image, self.lm_weight,
                                           self.length_bonus, -1 if self.lm is None else self.lm.bos_id, self.min_logp)
         self.fed += chunk[0].shape[0]
 
     def result(self, use_eos=True):
-        """the N-best strings of the frames fed so far: the tuple of ``gram_beam_decode`` (3) or ``gram_beam_decode_lm`` (5) with
-        ids of shape (B, beam_width, 2 x frames fed); the search goes on unchanged.  Sets ``frames`` (B) int32 on the device: the
-        frames every utterance has consumed."""
+        """the N-best strings of the frames fed so far: the tuple of ``gram_beam_decode`` (3), ``gram_beam_decode_lm`` (5) or
+        ``gram_beam_decode_biased`` (6) with ids of shape (B, beam_width, 2 x frames fed); the search goes on unchanged.  Sets
+        ``frames`` (B) int32 on the device: the frames every utterance has consumed."""
         eos = self.lm.eos_id if self.lm is not None and use_eos else -1
+        if self.graph is not None:
+            out, self.frames = _ops.gram_ctc_beam_bias_stream_result(self.state, self.B, self.beam_width, self.max_frames, self.blank,
+                                                                     max(2 * self.fed, 1),
+                                                                     None if self.lm is None else self.lm.image, self.graph.image,
+                                                                     self.lm_weight, self.length_bonus,
+                                                                     -1 if self.lm is None else self.lm.bos_id, eos)
+            return (out[0][:, :, :2 * self.fed],) + out[1:]
         out, self.frames = _ops.gram_ctc_beam_stream_result(self.state, self.B, self.beam_width, self.max_frames, self.blank,
                                                             max(2 * self.fed, 1), None if self.lm is None else self.lm.image,
                                                             self.lm_weight, self.length_bonus,

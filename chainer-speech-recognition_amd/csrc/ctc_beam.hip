@@ -18,7 +18,8 @@
 //               beam_kernel<LM, BIAS>: with a language model (section 17) and / or contextual phrase biasing (section 22) in the
 //               ranking; beam_kernel<false, false> is the search described here.
 // gram_beam_kernel : the same frame loop for the Gram-CTC inventory, over spelled strings (the end of this file).
-//               gram_beam_kernel<LM, MODE>: with a character language model (section 20); resumable like beam_kernel (section 26).
+//               gram_beam_kernel<LM, BIAS, MODE>: with a character language model (section 20) and / or phrase biasing over the
+//               spelled characters (section 32); resumable like beam_kernel (section 26).
 // Integer atomics only, on LDS histograms: the same inputs give bitwise the same outputs on every launch.
 #include "common.hpp"
 #include "ngram.hpp"
@@ -1363,6 +1364,34 @@ struct GFuseLds<true> {
     float elm[MAX_EXT];                                          // lm(s + a) or lm(s + a + b) of the frame's extensions
 };
 
+// The phrase-biasing side of asr_gram_ctc_beam_search_bias: gram_beam_kernel<., true> adds bias_open(s), the
+// arguments being section 22's Bias<true>; gram_beam_kernel<., false> carries none of this.  Per string: bias_open and the
+// automaton state, both fixed when the string enters the beam.  Per extension the same two, kept from phase B for phases C1 and F:
+// a bigram extension takes two dependent steps, and a survivor that repeated them in phase F would wait for both again.
+template <bool BIAS>
+struct GBiasLds {};
+
+template <>
+struct GBiasLds<true> {
+    float open[2][MAX_BEAM];                                     // bias_open(s) of the beam's strings
+    int state[2][MAX_BEAM];                                      // their automaton states
+    float eopen[MAX_EXT];                                        // bias_open(s + a) or bias_open(s + a + b) of the frame's extensions
+    int estate[MAX_EXT];                                         // and the state after them
+};
+
+// The model's bonus alpha * lm + beta * len in the two roundings that gram_beam_kernel<true, false, .> is compiled to (with
+// -ffp-contract=fast the choice is the compiler's, site by site): both products rounded before the sum in phases B and C2 and in
+// the final order, alpha * lm fused into the sum in phase C1.  With a graph without phrases gram_beam_kernel<true, true, .> must
+// rank and score exactly as that kernel does, for weights whose products round as well, so it states the choice at every site
+// instead of leaving it open (tests/test_gram_ctx_bias_gpu.py compares the two on bytes with alpha = 0.7, beta = 0.4).
+__device__ inline float bonus_rounded(float alpha, float lm, float beta, float len) {
+    float p = alpha * lm, q = beta * len;
+    asm volatile("" : "+v"(p), "+v"(q));                         // the products exist as f32 values: nothing can fuse them
+    return p + q;
+}
+
+__device__ inline float bonus_fused(float alpha, float lm, float beta, float len) { return __builtin_fmaf(alpha, lm, beta * len); }
+
 // the k-th newest character of the string in beam slot j as a model context: (bos) stands right before the string, nothing
 // before that; the identity fields c1 .. c3 keep their -1
 __device__ inline int lm_ctx(const GBeam& g, int j, int k, int bos) {
@@ -1395,11 +1424,19 @@ struct GState {
     int2* table;                                     // (B, 2 * max_frames * W) prefix table
 };
 
-// F = max_frames; variant = GRAM_VARIANT | with_lm
-__host__ __device__ inline size_t gram_state_layout(int B, int W, int F, int variant, char* base, GState* s) {
+// With a graph the state also holds GBiasLds' open and state, (B, W) each, between lm and the table.  They travel in a struct
+// of their own, after the other kernel arguments, so that the kernels without a graph keep their argument block.
+struct GBiasState {
+    float* open;
+    int* state;
+};
+
+// F = max_frames; variant = GRAM_VARIANT | with_lm | with_bias << 1
+__host__ __device__ inline size_t gram_state_layout(int B, int W, int F, int variant, char* base, GState* s,
+                                                    GBiasState* bs = nullptr) {
     GState sizing;
     GState& w = s ? *s : sizing;
-    w = GState{};                                    // lm stays null without a model
+    w = GState{};                                    // the fields of a side the variant does not have stay null
     const size_t slots = (size_t)B * W;
     size_t off = 0;
     take(w.hdr, base, off, (size_t)B * HDR_WORDS * 4);
@@ -1417,6 +1454,12 @@ __host__ __device__ inline size_t gram_state_layout(int B, int W, int F, int var
     take(w.gtok, base, off, slots * 4);
     take(w.node, base, off, slots * 4);
     if (variant & 1) take(w.lm, base, off, slots * 4);
+    GBiasState g{};
+    if (variant & 2) {
+        take(g.open, base, off, slots * 4);
+        take(g.state, base, off, slots * 4);
+    }
+    if (bs) *bs = g;
     take(w.table, base, off, slots * F * 16);
     return off;
 }
@@ -1433,16 +1476,24 @@ struct GStrm : GStrmArgs {};                         // kernel arguments
 template <>
 struct GStrm<ONESHOT> {};
 
+template <bool ON>
+struct GBiasStrm {};                                 // kernel arguments: ON = BIAS && MODE != ONESHOT
+
+template <>
+struct GBiasStrm<true> : GBiasState {};
+
 // ADVANCE: x, lengths and T are the chunk's (Tc frames, lengths[b] of them valid), ws and cgr hold the chunk's candidate rows and
 // their spellings and the outputs are unused.  RESULT: x, lengths, ws and cgr are unused, T is the ids' row pitch (Lcap).
-template <bool LM, int MODE>
+template <bool LM, bool BIAS, int MODE>
 __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restrict__ x, const int32_t* __restrict__ lengths, int T,
                                                             int B, int V, int W, int K, int blank, Ws ws,
                                                             const int2* __restrict__ cgr, int32_t* __restrict__ out_ids,
                                                             int32_t* __restrict__ out_len, float* __restrict__ out_score,
-                                                            Fuse<LM> fz, GStrm<MODE> sz) {
+                                                            Fuse<LM> fz, GStrm<MODE> sz, Bias<BIAS> bz,
+                                                            GBiasStrm<BIAS && MODE != ONESHOT> bs) {
     __shared__ GBeam bm[2];
     __shared__ GFuseLds<LM> fl;
+    __shared__ GBiasLds<BIAS> bl;
     __shared__ float tot[MAX_ENTRIES];                 // scores of the frame's entries in canonical order
     __shared__ unsigned short mt[MAX_EXT];             // an extension that took in a second one of the same string: that one's index
     __shared__ float btot[MAX_BEAM], bpu[MAX_BEAM], bpg[MAX_BEAM];     // pb + pu + pg, pb + pu, pb + pg of the beam
@@ -1485,6 +1536,11 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
             r.gtok[tid] = gtok;
             r.node[tid] = sz.s.node[i];
             if constexpr (LM) fl.lm[0][tid] = sz.s.lm[i];
+            if constexpr (BIAS) {
+                const int s = bs.state[i];             // a state that other code wrote into cannot lead outside ret
+                bl.open[0][tid] = bs.open[i];
+                bl.state[0][tid] = (unsigned)s < (unsigned)bz.g.n_states ? s : 0;
+            }
             // the logits of the tokens behind pu and pg in the chunk's first frame: the values the one-shot loop loads one frame
             // ahead.  Behind a token of -1 that loop holds 0.f (the root's is never written) and never reads it (section 26).
             if constexpr (MODE == ADVANCE) {
@@ -1506,6 +1562,10 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
         r.utok[0] = r.gtok[0] = -1;
         r.node[0] = -1;
         if constexpr (LM) fl.lm[0][0] = 0.f;
+        if constexpr (BIAS) {
+            bl.open[0][0] = 0.f;
+            bl.state[0][0] = 0;
+        }
     }
     int q_n = 0, q_id = 0;
     int2 q_g = make_int2(-1, -1);
@@ -1568,18 +1628,23 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
         // B: extension scores; for every stay the beam slots of s[:-1] and s[:-2] and the candidates that lead from them to s
         const int E = m + m * n;
         ngram::Step st1, st2;
+        ctx::Step cs;
         // the look-ups of extension q: one step for a unigram candidate, two for a bigram candidate (both contexts are known from
-        // the parent's last characters and a, so the second does not wait for the first), none for one that spells nothing
+        // the parent's last characters and a, so the second does not wait for the first), none for one that spells nothing.
+        // The automaton's step on a starts here too; its step on b needs the state after a and is issued once that is known.
         auto issue = [&](int q) {
-            if constexpr (LM) {
+            if constexpr (LM || BIAS) {
                 const int j = q / n, r = q - j * n, a = ca[r], b2 = cb[r];
                 if (a < 0) return;
-                const int x0 = lm_ctx(o, j, 0, fz.bos), x1 = lm_ctx(o, j, 1, fz.bos), x2 = lm_ctx(o, j, 2, fz.bos);
-                st1 = ngram::step_issue(fz.lm, x0, x1, x2, a);
-                if (b2 >= 0) st2 = ngram::step_issue(fz.lm, a, x0, x1, b2);
+                if constexpr (BIAS) cs = ctx::step_issue(bz.g, bl.state[cur][j], a);
+                if constexpr (LM) {
+                    const int x0 = lm_ctx(o, j, 0, fz.bos), x1 = lm_ctx(o, j, 1, fz.bos), x2 = lm_ctx(o, j, 2, fz.bos);
+                    st1 = ngram::step_issue(fz.lm, x0, x1, x2, a);
+                    if (b2 >= 0) st2 = ngram::step_issue(fz.lm, a, x0, x1, b2);
+                }
             }
         };
-        if constexpr (LM) {
+        if constexpr (LM || BIAS) {
             // thread k takes extension k (and k + 256, ...): the first one's loads are in flight during the matching loops below
             if (tid < m * n) issue(tid);
         } else {
@@ -1604,7 +1669,7 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
             const int r2 = p / n, r = p - r2 * n;
             if (cb[r2] >= 0 && ca[r] == cb[r2] && ca[r] >= 0 && cb[r] < 0) cmate[r2] = r;
         }
-        if constexpr (LM) {
+        if constexpr (LM && !BIAS) {
             for (int q = tid; q < m * n; q += THREADS) {
                 const int j = q / n, r = q - j * n, a = ca[r], b2 = cb[r];
                 mt[q] = NO_MATE;
@@ -1614,6 +1679,29 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
                 if (b2 >= 0) nl += ngram::step_finish(fz.lm, st2);
                 fl.elm[q] = nl;
                 tot[m + q] = ext_val(j, r) + (fz.alpha * nl + fz.beta * (float)(o.len[j] + (b2 < 0 ? 1 : 2)));
+            }
+        }
+        if constexpr (BIAS) {
+            for (int q = tid; q < m * n; q += THREADS) {
+                const int j = q / n, r = q - j * n, a = ca[r], b2 = cb[r];
+                mt[q] = NO_MATE;
+                if (a < 0) { tot[m + q] = -INFINITY; continue; }
+                if (q >= THREADS) issue(q);
+                // the automaton first: the step on b leaves as soon as the state after a is known and flies during the model's
+                int s1;
+                float bo = bl.open[cur][j] + ctx::step_finish(bz.g, cs, &s1);    // the steps in string order: (open + a) + b
+                if (b2 >= 0) cs = ctx::step_issue(bz.g, s1, b2);
+                float v = ext_val(j, r);
+                if constexpr (LM) {
+                    float nl = fl.lm[cur][j] + ngram::step_finish(fz.lm, st1);
+                    if (b2 >= 0) nl += ngram::step_finish(fz.lm, st2);
+                    fl.elm[q] = nl;
+                    v += bonus_rounded(fz.alpha, nl, fz.beta, (float)(o.len[j] + (b2 < 0 ? 1 : 2)));
+                }
+                if (b2 >= 0) bo += ctx::step_finish(bz.g, cs, &s1);
+                bl.eopen[q] = bo;
+                bl.estate[q] = s1;
+                tot[m + q] = v + bo;
             }
         }
         __syncthreads();
@@ -1626,13 +1714,18 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
             const int qu = j * n + cmate[r2], qg = j2 * n + r2;
             const int lo = min(qu, qg), hi = max(qu, qg);
             float s;
-            if constexpr (LM) {
+            if constexpr (LM && !BIAS) {
                 // the acoustic parts again (phase B's sums, bit for bit), merged, then the string's bonus: both routes carry
                 // the same lm and length
                 s = lae(ext_val(j, cmate[r2]), ext_val(j2, r2)) + (fz.alpha * fl.elm[lo] + fz.beta * (float)(o.len[j] + 1));
+            } else if constexpr (LM) {
+                s = lae(ext_val(j, cmate[r2]), ext_val(j2, r2)) + bonus_fused(fz.alpha, fl.elm[lo], fz.beta, (float)(o.len[j] + 1));
+            } else if constexpr (BIAS) {
+                s = lae(ext_val(j, cmate[r2]), ext_val(j2, r2));
             } else {
                 s = lae(tot[m + qu], tot[m + qg]);
             }
+            if constexpr (BIAS) s += bl.eopen[lo];       // both routes carry the same bias_open and state as well
             tot[m + lo] = s;
             tot[m + hi] = -INFINITY;
             mt[lo] = (unsigned short)hi;
@@ -1655,8 +1748,10 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
             spb[i] = npb;
             spu[i] = npu;
             spg[i] = npg;
-            if constexpr (LM) tot[i] = lae3(npb, npu, npg) + (fz.alpha * fl.lm[cur][i] + fz.beta * (float)o.len[i]);
+            if constexpr (LM && !BIAS) tot[i] = lae3(npb, npu, npg) + (fz.alpha * fl.lm[cur][i] + fz.beta * (float)o.len[i]);
+            else if constexpr (LM) tot[i] = lae3(npb, npu, npg) + bonus_rounded(fz.alpha, fl.lm[cur][i], fz.beta, (float)o.len[i]);
             else tot[i] = lae3(npb, npu, npg);
+            if constexpr (BIAS) tot[i] += bl.open[cur][i];
         }
         __syncthreads();
         // D, E: beam_kernel's, line for line (see the note there)
@@ -1768,17 +1863,25 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
                 nx.xu[rank] = ku ? xnext[e] : (cu[e] >= 0 ? xnext[2 * m + cu[e]] : 0.f);
                 nx.xg[rank] = kg ? xnext[m + e] : (cg[e] >= 0 ? xnext[2 * m + cg[e]] : 0.f);
                 if constexpr (LM) fl.lm[cur ^ 1][rank] = fl.lm[cur][e];
+                if constexpr (BIAS) {
+                    bl.open[cur ^ 1][rank] = bl.open[cur][e];
+                    bl.state[cur ^ 1][rank] = bl.state[cur][e];
+                }
             } else {
                 const int q2 = e - m, j = q2 / n, r = q2 - j * n, a = ca[r], b2 = cb[r];
                 const int mate = mt[q2];
                 // the other extension of the pair, if any: (jm, rm); f is then the sum and the parts are phase B's again
                 const int jm = mate == NO_MATE ? -1 : mate / n, rm = mate == NO_MATE ? -1 : mate - jm * n;
-                // (with the language model f is the ranking score, and the own part is phase B's sum again as well)
-                const float own = !LM && jm < 0 ? f : ext_val(j, r);
+                // (with the language model or the bias f is the ranking score, and the own part is phase B's sum again as well)
+                const float own = !LM && !BIAS && jm < 0 ? f : ext_val(j, r);
                 const float oth = jm < 0 ? -INFINITY : ext_val(jm, rm);
                 const int id = 2 * ((f0 + t) * W + rank);
                 nx.pb[rank] = -INFINITY;
                 if constexpr (LM) fl.lm[cur ^ 1][rank] = fl.elm[q2];
+                if constexpr (BIAS) {
+                    bl.open[cur ^ 1][rank] = bl.eopen[q2];
+                    bl.state[cur ^ 1][rank] = bl.estate[q2];
+                }
                 if (b2 < 0) {                           // s + a
                     nx.pu[rank] = own;
                     nx.pg[rank] = oth;
@@ -1841,6 +1944,10 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
             sz.s.gtok[i] = o.gtok[tid];
             sz.s.node[i] = o.node[tid];
             if constexpr (LM) sz.s.lm[i] = fl.lm[cur][tid];
+            if constexpr (BIAS) {
+                bs.open[i] = bl.open[cur][tid];
+                bs.state[i] = bl.state[cur][tid];
+            }
         }
         stream_end(sz.s.hdr + (size_t)b * HDR_WORDS, m, f0 + len_b);
         return;
@@ -1850,15 +1957,27 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
     int table_n = 0;
     if constexpr (MODE == RESULT) table_n = 2 * sz.max_frames * W;
     int32_t* ids = out_ids + (size_t)b * W * T2;
-    if constexpr (LM) {
-        // the end term, then the final order: score descending, ties to the earlier slot (as beam_kernel<true>)
-        float ctc = 0.f, lmv = 0.f, sc = 0.f;
+    if constexpr (LM || BIAS) {
+        // the end terms, then the final order: score descending, ties to the earlier slot (as beam_kernel<true, .>)
+        float* o_ctc;
+        float* o_lm;
+        if constexpr (BIAS) { o_ctc = bz.out_ctc; o_lm = bz.out_lm; }
+        else { o_ctc = fz.out_ctc; o_lm = fz.out_lm; }
+        float ctc = 0.f, lmv = 0.f, bv = 0.f, sc = 0.f;
         if (tid < m) {
             ctc = lae3(o.pb[tid], o.pu[tid], o.pg[tid]);
-            lmv = fl.lm[cur][tid];
-            if (fz.eos >= 0)
-                lmv += ngram::step(fz.lm, lm_ctx(o, tid, 0, fz.bos), lm_ctx(o, tid, 1, fz.bos), lm_ctx(o, tid, 2, fz.bos), fz.eos);
-            sc = ctc + (fz.alpha * lmv + fz.beta * (float)o.len[tid]);
+            sc = ctc;
+            if constexpr (LM) {
+                lmv = fl.lm[cur][tid];
+                if (fz.eos >= 0)
+                    lmv += ngram::step(fz.lm, lm_ctx(o, tid, 0, fz.bos), lm_ctx(o, tid, 1, fz.bos), lm_ctx(o, tid, 2, fz.bos), fz.eos);
+                if constexpr (BIAS) sc = ctc + bonus_rounded(fz.alpha, lmv, fz.beta, (float)o.len[tid]);
+                else sc = ctc + (fz.alpha * lmv + fz.beta * (float)o.len[tid]);
+            }
+            if constexpr (BIAS) {
+                bv = bl.open[cur][tid] + bz.g.ret[bl.state[cur][tid]];        // the advance of an unfinished match goes back
+                sc += bv;
+            }
             sv_tot[tid] = sc;
         }
         __syncthreads();
@@ -1866,8 +1985,9 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
             const int rank = rank_of(sv_tot, m, sc, tid);
             sv_pos[rank] = tid;
             out_score[b * W + rank] = sc;
-            fz.out_ctc[b * W + rank] = ctc;
-            fz.out_lm[b * W + rank] = lmv;
+            o_ctc[b * W + rank] = ctc;
+            o_lm[b * W + rank] = lmv;
+            if constexpr (BIAS) bz.out_bias[b * W + rank] = bv;
         }
         __syncthreads();
         fill_blank(ids, T2, W, m, o.len, sv_pos, blank);
@@ -1879,8 +1999,9 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
             } else {
                 out_len[b * W + tid] = 0;
                 out_score[b * W + tid] = -INFINITY;
-                fz.out_ctc[b * W + tid] = -INFINITY;
-                fz.out_lm[b * W + tid] = 0.f;
+                o_ctc[b * W + tid] = -INFINITY;
+                o_lm[b * W + tid] = 0.f;
+                if constexpr (BIAS) bz.out_bias[b * W + tid] = 0.f;
             }
         }
         return;
@@ -1941,8 +2062,9 @@ extern "C" int asr_gram_ctc_beam_search(void* stream, const float* logits, const
     if (rc != ASR_OK) return rc;
     rc = launch_gram_rows(stream, lengths, T, B, K, ws, gram, cgr);
     if (rc != ASR_OK) return rc;
-    hipLaunchKernelGGL((gram_beam_kernel<false, ONESHOT>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V,
-                       beam_width, K, blank, ws, (const int2*)cgr, out_ids, out_len, out_score, Fuse<false>{}, GStrm<ONESHOT>{});
+    hipLaunchKernelGGL((gram_beam_kernel<false, false, ONESHOT>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T,
+                       B, V, beam_width, K, blank, ws, (const int2*)cgr, out_ids, out_len, out_score, Fuse<false>{}, GStrm<ONESHOT>{},
+                       Bias<false>{}, GBiasStrm<false>{});
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }
@@ -1973,8 +2095,62 @@ extern "C" int asr_gram_ctc_beam_search_lm(void* stream, const float* logits, co
     if (rc != ASR_OK) return rc;
     rc = launch_gram_rows(stream, lengths, T, B, K, ws, gram, cgr);
     if (rc != ASR_OK) return rc;
-    hipLaunchKernelGGL((gram_beam_kernel<true, ONESHOT>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V,
-                       beam_width, K, blank, ws, (const int2*)cgr, out_ids, out_len, out_score, fz, GStrm<ONESHOT>{});
+    hipLaunchKernelGGL((gram_beam_kernel<true, false, ONESHOT>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T,
+                       B, V, beam_width, K, blank, ws, (const int2*)cgr, out_ids, out_len, out_score, fz, GStrm<ONESHOT>{}, Bias<false>{},
+                       GBiasStrm<false>{});
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+// ------------------------------------------------------------------------------ Gram-CTC: phrase biasing
+extern "C" size_t asr_gram_ctc_beam_bias_workspace_bytes(int T, int B, int V, int beam_width, int top_k) {
+    return asr_gram_ctc_beam_workspace_bytes(T, B, V, beam_width, top_k);
+}
+
+extern "C" int asr_gram_ctc_beam_search_bias(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank,
+                                             int beam_width, int top_k, float min_logp, const int32_t* gram, const float* uni, int vlm,
+                                             const int32_t* keys, const float* vals, int slots, int max_probe, int order, int bos,
+                                             int eos, float alpha, float beta, void* workspace, size_t workspace_bytes,
+                                             int32_t* out_ids, int32_t* out_len, float* out_score, float* out_ctc, float* out_lm,
+                                             const int32_t* g_keys, const int32_t* g_vals, int g_slots, int g_max_probe,
+                                             const float* g_ret, int g_n_states, float* out_bias) {
+    const int lim = oneshot_check(logits, workspace, out_ids, out_len, out_score, T, B, V, blank, beam_width, top_k, 2);
+    if (lim == ASR_ERR_BAD_ARG || !out_ctc || !out_lm || !out_bias) return ASR_ERR_BAD_ARG;
+    const bool with_lm = uni != nullptr;
+    Fuse<true> fz;
+    int rc;
+    if (with_lm) {
+        if (vlm < V || bos >= vlm || eos >= vlm) return ASR_ERR_BAD_ARG;
+        rc = make_lm(uni, vlm, keys, vals, slots, max_probe, order, &fz.lm);
+        if (rc != ASR_OK) return rc;
+    }
+    Bias<true> bz;
+    rc = make_graph(g_keys, g_vals, g_slots, g_max_probe, g_ret, g_n_states, &bz.g);
+    if (rc != ASR_OK) return rc;
+    if (!gram) return ASR_ERR_UNSUPPORTED;
+    if (lim != ASR_OK) return lim;
+    const int K = min(top_k, V - 1);
+    Ws ws;
+    int2* cgr;
+    const size_t need = gram_ws_layout(T, B, beam_width, K, (char*)workspace, &ws, &cgr);
+    if (workspace_bytes < need) return ASR_ERR_WORKSPACE;
+    bz.out_ctc = out_ctc;
+    bz.out_lm = out_lm;
+    bz.out_bias = out_bias;
+    rc = launch_cand(stream, logits, lengths, T, B, V, blank, K, min_logp, ws);
+    if (rc != ASR_OK) return rc;
+    rc = launch_gram_rows(stream, lengths, T, B, K, ws, gram, cgr);
+    if (rc != ASR_OK) return rc;
+    if (with_lm) {
+        fill_fuse(&fz, bos, eos, alpha, beta, out_ctc, out_lm);
+        hipLaunchKernelGGL((gram_beam_kernel<true, true, ONESHOT>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T,
+                           B, V, beam_width, K, blank, ws, (const int2*)cgr, out_ids, out_len, out_score, fz, GStrm<ONESHOT>{}, bz,
+                           GBiasStrm<false>{});
+    } else {
+        hipLaunchKernelGGL((gram_beam_kernel<false, true, ONESHOT>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T,
+                           B, V, beam_width, K, blank, ws, (const int2*)cgr, out_ids, out_len, out_score, Fuse<false>{}, GStrm<ONESHOT>{},
+                           bz, GBiasStrm<false>{});
+    }
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }
@@ -1985,7 +2161,7 @@ namespace beam {
 
 // the header and the root beam (what gram_beam_kernel<., ONESHOT> starts from) of every utterance, or of those with mask[b] != 0
 __global__ __launch_bounds__(256) void gram_stream_reset_kernel(GState s, int B, int W, int F, int variant,
-                                                                const int32_t* __restrict__ mask) {
+                                                                const int32_t* __restrict__ mask, GBiasState bs) {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= B || (mask && mask[b] == 0)) return;
     int* h = s.hdr + (size_t)b * HDR_WORDS;
@@ -2007,48 +2183,80 @@ __global__ __launch_bounds__(256) void gram_stream_reset_kernel(GState s, int B,
     s.utok[i] = s.gtok[i] = -1;
     s.node[i] = -1;
     if (variant & 1) s.lm[i] = 0.f;
+    if (variant & 2) {
+        bs.open[i] = 0.f;
+        bs.state[i] = 0;
+    }
+}
+
+template <bool LM, bool BIAS, int MODE>
+static void launch_gram(hipStream_t st, const float* x, const int32_t* lengths, int T, int B, int V, int W, int K, int blank,
+                        const Ws& ws, const int2* cgr, int32_t* out_ids, int32_t* out_len, float* out_score, const Fuse<true>& fz,
+                        const Bias<true>& bz, const GStrm<MODE>& sz, const GBiasState& bs) {
+    Fuse<LM> f;
+    Bias<BIAS> g;
+    GBiasStrm<BIAS && MODE != ONESHOT> gs;
+    if constexpr (LM) f = fz;
+    if constexpr (BIAS) g = bz;
+    if constexpr (BIAS && MODE != ONESHOT) static_cast<GBiasState&>(gs) = bs;
+    hipLaunchKernelGGL((gram_beam_kernel<LM, BIAS, MODE>), dim3(B), dim3(THREADS), 0, st, x, lengths, T, B, V, W, K, blank, ws, cgr,
+                       out_ids, out_len, out_score, f, sz, g, gs);
 }
 
 template <int MODE>
 static void launch_gram_stream(hipStream_t st, const float* x, const int32_t* lengths, int T, int B, int V, int W, int K, int blank,
                                const Ws& ws, const int2* cgr, int32_t* out_ids, int32_t* out_len, float* out_score,
-                               const Fuse<true>& fz, const GStrm<MODE>& sz) {
-    if (sz.variant & 1)
-        hipLaunchKernelGGL((gram_beam_kernel<true, MODE>), dim3(B), dim3(THREADS), 0, st, x, lengths, T, B, V, W, K, blank, ws, cgr,
-                           out_ids, out_len, out_score, fz, sz);
-    else
-        hipLaunchKernelGGL((gram_beam_kernel<false, MODE>), dim3(B), dim3(THREADS), 0, st, x, lengths, T, B, V, W, K, blank, ws, cgr,
-                           out_ids, out_len, out_score, Fuse<false>{}, sz);
+                               const Fuse<true>& fz, const Bias<true>& bz, const GStrm<MODE>& sz, const GBiasState& bs) {
+    switch (sz.variant & 3) {
+        case 0: launch_gram<false, false, MODE>(st, x, lengths, T, B, V, W, K, blank, ws, cgr, out_ids, out_len, out_score, fz, bz, sz, bs); break;
+        case 1: launch_gram<true, false, MODE>(st, x, lengths, T, B, V, W, K, blank, ws, cgr, out_ids, out_len, out_score, fz, bz, sz, bs); break;
+        case 2: launch_gram<false, true, MODE>(st, x, lengths, T, B, V, W, K, blank, ws, cgr, out_ids, out_len, out_score, fz, bz, sz, bs); break;
+        default: launch_gram<true, true, MODE>(st, x, lengths, T, B, V, W, K, blank, ws, cgr, out_ids, out_len, out_score, fz, bz, sz, bs);
+    }
 }
 
 // the Gram-CTC stream's variant word (GState's header, gram_state_layout)
-static int gram_variant(bool with_lm) { return GRAM_VARIANT | (with_lm ? 1 : 0); }
+static int gram_variant(bool with_lm, bool with_bias) { return GRAM_VARIANT | (with_lm ? 1 : 0) | (with_bias ? 2 : 0); }
 
-// the checks on dimensions, state size and the model arguments that advance and result share; fills fz->lm and sz->s
+// the checks on dimensions, state size and the model / graph arguments that advance and result share; fills fz->lm, bz->g and sz->s
 static int gram_stream_open(int B, int W, int F, const float* uni, int vlm, const int32_t* keys, const float* vals, int slots,
-                            int max_probe, int order, int bos, void* state, size_t state_bytes, Fuse<true>* fz, GStrmArgs* sz) {
+                            int max_probe, int order, int bos, const int32_t* g_keys, const int32_t* g_vals, int g_slots,
+                            int g_max_probe, const float* g_ret, int g_n_states, void* state, size_t state_bytes, Fuse<true>* fz,
+                            Bias<true>* bz, GStrmArgs* sz, GBiasState* bs) {
     const int lim = stream_dims(state != nullptr, B, W, F, 2);
     if (lim == ASR_ERR_BAD_ARG) return lim;
-    const bool with_lm = uni != nullptr;
+    const bool with_lm = uni != nullptr, with_bias = g_ret != nullptr;
     if (with_lm) {
         if (bos >= vlm) return ASR_ERR_BAD_ARG;
         const int rc = make_lm(uni, vlm, keys, vals, slots, max_probe, order, &fz->lm);
         if (rc != ASR_OK) return rc;
     }
+    if (with_bias) {
+        const int rc = make_graph(g_keys, g_vals, g_slots, g_max_probe, g_ret, g_n_states, &bz->g);
+        if (rc != ASR_OK) return rc;
+    } else if (g_keys || g_vals || g_slots != 0 || g_n_states != 0) {
+        return ASR_ERR_BAD_ARG;                      // a graph without its ret: section 22's check, not "no graph"
+    }
     if (lim != ASR_OK) return lim;
     sz->max_frames = F;
-    sz->variant = gram_variant(with_lm);
+    sz->variant = gram_variant(with_lm, with_bias);
     sz->out_frames = nullptr;
-    if (state_bytes < gram_state_layout(B, W, F, sz->variant, (char*)state, &sz->s)) return ASR_ERR_WORKSPACE;
+    if (state_bytes < gram_state_layout(B, W, F, sz->variant, (char*)state, &sz->s, bs)) return ASR_ERR_WORKSPACE;
     return ASR_OK;
 }
 
 }  // namespace beam
 }  // namespace asr
 
-extern "C" size_t asr_gram_ctc_beam_stream_state_bytes(int B, int beam_width, int max_frames, int with_lm) {
+// The family with a graph.  Without one (with_bias == 0, g_ret == NULL) it is the family of section 26, size
+// for size and byte for byte, so those entries are these with no graph.
+extern "C" size_t asr_gram_ctc_beam_bias_stream_state_bytes(int B, int beam_width, int max_frames, int with_lm, int with_bias) {
     if (stream_dims(true, B, beam_width, max_frames, 2) == ASR_ERR_BAD_ARG) return 0;
-    return gram_state_layout(B, beam_width, max_frames, gram_variant(with_lm), nullptr, nullptr);
+    return gram_state_layout(B, beam_width, max_frames, gram_variant(with_lm, with_bias), nullptr, nullptr);
+}
+
+extern "C" size_t asr_gram_ctc_beam_stream_state_bytes(int B, int beam_width, int max_frames, int with_lm) {
+    return asr_gram_ctc_beam_bias_stream_state_bytes(B, beam_width, max_frames, with_lm, 0);
 }
 
 extern "C" size_t asr_gram_ctc_beam_stream_workspace_bytes(int Tc, int B, int V, int beam_width, int top_k) {
@@ -2056,32 +2264,41 @@ extern "C" size_t asr_gram_ctc_beam_stream_workspace_bytes(int Tc, int B, int V,
     return gram_ws_layout(Tc, B, 0, min(top_k, V - 1), nullptr, nullptr, nullptr);    // candidate rows and spellings; no table
 }
 
-extern "C" int asr_gram_ctc_beam_stream_reset(void* stream, void* state, size_t state_bytes, int B, int beam_width, int max_frames,
-                                              int with_lm, const int32_t* mask) {
+extern "C" int asr_gram_ctc_beam_bias_stream_reset(void* stream, void* state, size_t state_bytes, int B, int beam_width,
+                                                   int max_frames, int with_lm, int with_bias, const int32_t* mask) {
     const int rc = stream_dims(state != nullptr, B, beam_width, max_frames, 2);
     if (rc != ASR_OK) return rc;
-    const int variant = gram_variant(with_lm);
+    const int variant = gram_variant(with_lm, with_bias);
     GState s;
-    if (state_bytes < gram_state_layout(B, beam_width, max_frames, variant, (char*)state, &s)) return ASR_ERR_WORKSPACE;
+    GBiasState bs;
+    if (state_bytes < gram_state_layout(B, beam_width, max_frames, variant, (char*)state, &s, &bs)) return ASR_ERR_WORKSPACE;
     hipLaunchKernelGGL(gram_stream_reset_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, s, B,
-                       beam_width, max_frames, variant, mask);
+                       beam_width, max_frames, variant, mask, bs);
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }
 
-extern "C" int asr_gram_ctc_beam_stream_advance(void* stream, const float* logits, const int32_t* lengths, int Tc, int B, int V,
-                                                int blank, int beam_width, int top_k, float min_logp, const int32_t* gram,
-                                                const float* uni, int vlm, const int32_t* keys, const float* vals, int slots,
-                                                int max_probe, int order, int bos, float alpha, float beta, int frames_before,
-                                                int max_frames, void* state, size_t state_bytes, void* workspace,
-                                                size_t workspace_bytes) {
+extern "C" int asr_gram_ctc_beam_stream_reset(void* stream, void* state, size_t state_bytes, int B, int beam_width, int max_frames,
+                                              int with_lm, const int32_t* mask) {
+    return asr_gram_ctc_beam_bias_stream_reset(stream, state, state_bytes, B, beam_width, max_frames, with_lm, 0, mask);
+}
+
+extern "C" int asr_gram_ctc_beam_bias_stream_advance(void* stream, const float* logits, const int32_t* lengths, int Tc, int B, int V,
+                                                     int blank, int beam_width, int top_k, float min_logp, const int32_t* gram,
+                                                     const float* uni, int vlm, const int32_t* keys, const float* vals, int slots,
+                                                     int max_probe, int order, int bos, const int32_t* g_keys,
+                                                     const int32_t* g_vals, int g_slots, int g_max_probe, const float* g_ret,
+                                                     int g_n_states, float alpha, float beta, int frames_before, int max_frames,
+                                                     void* state, size_t state_bytes, void* workspace, size_t workspace_bytes) {
     if (!logits || !workspace || Tc <= 0 || V <= 0 || blank < 0 || blank >= V || top_k <= 0 || frames_before < 0)
         return ASR_ERR_BAD_ARG;
     if (uni && vlm < V) return ASR_ERR_BAD_ARG;
     Fuse<true> fz{};
+    Bias<true> bz{};
     GStrm<ADVANCE> sz{};
-    int rc = gram_stream_open(B, beam_width, max_frames, uni, vlm, keys, vals, slots, max_probe, order, bos, state, state_bytes,
-                              &fz, &sz);
+    GBiasState bs{};
+    int rc = gram_stream_open(B, beam_width, max_frames, uni, vlm, keys, vals, slots, max_probe, order, bos, g_keys, g_vals, g_slots,
+                              g_max_probe, g_ret, g_n_states, state, state_bytes, &fz, &bz, &sz, &bs);
     if (rc != ASR_OK) return rc;
     if (!gram) return ASR_ERR_UNSUPPORTED;
     if (top_k > MAX_TOPK || beam_width * top_k > MAX_EXT) return ASR_ERR_UNSUPPORTED;
@@ -2096,7 +2313,48 @@ extern "C" int asr_gram_ctc_beam_stream_advance(void* stream, const float* logit
     rc = launch_gram_rows(stream, lengths, Tc, B, K, ws, gram, cgr);
     if (rc != ASR_OK) return rc;
     launch_gram_stream<ADVANCE>((hipStream_t)stream, logits, lengths, Tc, B, V, beam_width, K, blank, ws, (const int2*)cgr, nullptr,
-                                nullptr, nullptr, fz, sz);
+                                nullptr, nullptr, fz, bz, sz, bs);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+extern "C" int asr_gram_ctc_beam_stream_advance(void* stream, const float* logits, const int32_t* lengths, int Tc, int B, int V,
+                                                int blank, int beam_width, int top_k, float min_logp, const int32_t* gram,
+                                                const float* uni, int vlm, const int32_t* keys, const float* vals, int slots,
+                                                int max_probe, int order, int bos, float alpha, float beta, int frames_before,
+                                                int max_frames, void* state, size_t state_bytes, void* workspace,
+                                                size_t workspace_bytes) {
+    return asr_gram_ctc_beam_bias_stream_advance(stream, logits, lengths, Tc, B, V, blank, beam_width, top_k, min_logp, gram, uni, vlm,
+                                                 keys, vals, slots, max_probe, order, bos, nullptr, nullptr, 0, 0, nullptr, 0, alpha,
+                                                 beta, frames_before, max_frames, state, state_bytes, workspace, workspace_bytes);
+}
+
+extern "C" int asr_gram_ctc_beam_bias_stream_result(void* stream, const float* uni, int vlm, const int32_t* keys, const float* vals,
+                                                    int slots, int max_probe, int order, int bos, int eos, const int32_t* g_keys,
+                                                    const int32_t* g_vals, int g_slots, int g_max_probe, const float* g_ret,
+                                                    int g_n_states, float alpha, float beta, int B, int beam_width, int max_frames,
+                                                    int blank, int Lcap, const void* state, size_t state_bytes, int32_t* out_ids,
+                                                    int32_t* out_len, float* out_score, float* out_ctc, float* out_lm,
+                                                    float* out_bias, int32_t* out_frames) {
+    if (!out_ids || !out_len || !out_score || !out_frames || Lcap <= 0 || blank < 0) return ASR_ERR_BAD_ARG;
+    if ((uni || g_ret) && (!out_ctc || !out_lm)) return ASR_ERR_BAD_ARG;
+    if (g_ret && !out_bias) return ASR_ERR_BAD_ARG;
+    if (uni && eos >= vlm) return ASR_ERR_BAD_ARG;
+    Fuse<true> fz{};
+    Bias<true> bz{};
+    GStrm<RESULT> sz{};
+    GBiasState bs{};
+    const int rc = gram_stream_open(B, beam_width, max_frames, uni, vlm, keys, vals, slots, max_probe, order, bos, g_keys, g_vals,
+                                    g_slots, g_max_probe, g_ret, g_n_states, const_cast<void*>(state), state_bytes, &fz, &bz, &sz,
+                                    &bs);
+    if (rc != ASR_OK) return rc;
+    sz.out_frames = out_frames;
+    fill_fuse(&fz, bos, eos, alpha, beta, out_ctc, out_lm);
+    bz.out_ctc = out_ctc;
+    bz.out_lm = out_lm;
+    bz.out_bias = out_bias;
+    launch_gram_stream<RESULT>((hipStream_t)stream, nullptr, nullptr, Lcap, B, 0, beam_width, 0, blank, Ws{}, nullptr, out_ids,
+                               out_len, out_score, fz, bz, sz, bs);
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }
@@ -2106,17 +2364,7 @@ extern "C" int asr_gram_ctc_beam_stream_result(void* stream, const float* uni, i
                                                int beam_width, int max_frames, int blank, int Lcap, const void* state,
                                                size_t state_bytes, int32_t* out_ids, int32_t* out_len, float* out_score,
                                                float* out_ctc, float* out_lm, int32_t* out_frames) {
-    if (!out_ids || !out_len || !out_score || !out_frames || Lcap <= 0 || blank < 0) return ASR_ERR_BAD_ARG;
-    if (uni && (!out_ctc || !out_lm || eos >= vlm)) return ASR_ERR_BAD_ARG;
-    Fuse<true> fz{};
-    GStrm<RESULT> sz{};
-    const int rc = gram_stream_open(B, beam_width, max_frames, uni, vlm, keys, vals, slots, max_probe, order, bos,
-                                    const_cast<void*>(state), state_bytes, &fz, &sz);
-    if (rc != ASR_OK) return rc;
-    sz.out_frames = out_frames;
-    fill_fuse(&fz, bos, eos, alpha, beta, out_ctc, out_lm);
-    launch_gram_stream<RESULT>((hipStream_t)stream, nullptr, nullptr, Lcap, B, 0, beam_width, 0, blank, Ws{}, nullptr, out_ids,
-                               out_len, out_score, fz, sz);
-    ASR_LAUNCH_CHECK();
-    return ASR_OK;
+    return asr_gram_ctc_beam_bias_stream_result(stream, uni, vlm, keys, vals, slots, max_probe, order, bos, eos, nullptr, nullptr, 0, 0,
+                                                nullptr, 0, alpha, beta, B, beam_width, max_frames, blank, Lcap, state, state_bytes,
+                                                out_ids, out_len, out_score, out_ctc, out_lm, nullptr, out_frames);
 }

@@ -550,6 +550,65 @@ int asr_gram_ctc_beam_stream_result(void* stream, const float* uni, int vlm, con
                                     int max_probe, int order, int bos, int eos, float alpha, float beta, int B, int beam_width,
                                     int max_frames, int blank, int Lcap, const void* state, size_t state_bytes, int32_t* out_ids,
                                     int32_t* out_len, float* out_score, float* out_ctc, float* out_lm, int32_t* out_frames);
+/* Gram-CTC beam search with contextual phrase biasing: asr_gram_ctc_beam_search_lm (uni != NULL) or
+ * asr_gram_ctc_beam_search (uni == NULL: the other model arguments are ignored and out_lm is all 0) with the automaton of the
+ * asr_ctx_score block above running beside every string.
+ * Graph: that image over the unigram ids that `gram` spells with (the table's values, not the token ids), as the model of
+ *   asr_gram_ctc_beam_search_lm; the caller builds it with V the logits' V and the logits' blank.  A phrase that contains an id which
+ *   no row of gram spells can never match; that is allowed.
+ * bias_open(S) and state(S) are functions of the string alone: state(()) is the root, bias_open(()) = 0, and
+ *   bias_open(S + c) = bias_open(S) + delta(state(S), c)  in f32 with the look-up stated above (hit at (s, c); else hit at (0, c)
+ *   paying ret[s] + delta0; else the root paying ret[s]; a next outside [0, n_states) counts as the root).  A bigram extension (a, b)
+ *   takes two dependent steps in string order, (bias_open(S) + delta(s, a)) + delta(s1, b) with s1 the state after a, so every route
+ *   to a string (and a string pruned and created again) gives the same f32 value and the same state.
+ * Ranking, in every frame and after all merges of the frame:  (total + (alpha * lm + beta * len)) + bias_open  resp.
+ *   total + bias_open  in f32, total, lm and len as in asr_gram_ctc_beam_search_lm.  Merging (two extensions of one string; a stay
+ *   with the extensions that spell it), canonical positions, tie rules, dropped (-1, -1) candidates and the prefix table are the
+ *   parents'; a merged entry keeps the stay's values; pb / pu / pg stay pure Gram-CTC quantities.
+ * After the last frame bias(S) = bias_open(S) + ret[state(S)], the sum of weight * length over every occurrence of every phrase in
+ *   S; the eos term goes into lm as in the parent; the beam is sorted by  out_score = (out_ctc + (alpha * out_lm + beta * len)) +
+ *   out_bias  resp.  out_ctc + out_bias,  ties to the earlier slot.
+ *   out_ids (B, beam_width, 2T), out_len, out_score, out_ctc, out_lm as asr_gram_ctc_beam_search_lm
+ *   out_bias (B, beam_width) f32 bias(S), unused 0
+ *   workspace asr_gram_ctc_beam_bias_workspace_bytes(T, B, V, beam_width, top_k) bytes
+ * Every element of every output is written on every call.  With a graph without phrases (n_states 1, slots 0) the outputs equal the
+ * parent entry's bit for bit and out_bias is all 0.  With a table without bigram rows whose unigram ids are the token ids, the first
+ * T columns, out_len and the four scores are asr_ctc_beam_search_bias's.  Errors are the union of the parents', all checked before
+ * the first launch: the limits and model checks of asr_gram_ctc_beam_search_lm (gram == NULL: ASR_ERR_UNSUPPORTED) and the
+ * graph-argument checks of asr_ctc_beam_search_bias (ASR_ERR_BAD_ARG; NULL out_ctc, out_lm or out_bias too).  Frames past
+ * lengths[b] are never read.  No host synchronisation.  Bitwise reproducible.
+ * Streaming: the asr_gram_ctc_beam_stream_* contract with a graph.  advance and result take the six graph arguments after bos
+ * resp. eos; g_ret == NULL: no graph (the other graph arguments must then be NULL / 0).  result also takes out_bias (with a graph;
+ * NULL otherwise), and out_ctc / out_lm are written with a model or a graph.  The per-call workspace is
+ * asr_gram_ctc_beam_stream_workspace_bytes.  With with_bias == 0 the size, the header's variant word and every byte of the state
+ * are those of the asr_gram_ctc_beam_stream_* entries, and a state can move between the two families.  With a graph the variant word
+ * gains a bias bit and the state gains bias_open and the automaton state per string, beside lm.  A variant mismatch (a state reset
+ * without the bias bit given to a call with a graph, or the reverse; a CTC stream's state) is handled as there: advance leaves the
+ * utterance alone, result writes the unused-slot values and out_frames -1.  Error codes: those of asr_gram_ctc_beam_stream_* and
+ * the graph-argument checks above. */
+size_t asr_gram_ctc_beam_bias_workspace_bytes(int T, int B, int V, int beam_width, int top_k);
+int asr_gram_ctc_beam_search_bias(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank,
+                                  int beam_width, int top_k, float min_logp, const int32_t* gram, const float* uni, int vlm,
+                                  const int32_t* keys, const float* vals, int slots, int max_probe, int order, int bos, int eos,
+                                  float alpha, float beta, void* workspace, size_t workspace_bytes, int32_t* out_ids,
+                                  int32_t* out_len, float* out_score, float* out_ctc, float* out_lm, const int32_t* g_keys,
+                                  const int32_t* g_vals, int g_slots, int g_max_probe, const float* g_ret, int g_n_states,
+                                  float* out_bias);
+size_t asr_gram_ctc_beam_bias_stream_state_bytes(int B, int beam_width, int max_frames, int with_lm, int with_bias);
+int asr_gram_ctc_beam_bias_stream_reset(void* stream, void* state, size_t state_bytes, int B, int beam_width, int max_frames,
+                                        int with_lm, int with_bias, const int32_t* mask);
+int asr_gram_ctc_beam_bias_stream_advance(void* stream, const float* logits, const int32_t* lengths, int Tc, int B, int V, int blank,
+                                          int beam_width, int top_k, float min_logp, const int32_t* gram, const float* uni, int vlm,
+                                          const int32_t* keys, const float* vals, int slots, int max_probe, int order, int bos,
+                                          const int32_t* g_keys, const int32_t* g_vals, int g_slots, int g_max_probe,
+                                          const float* g_ret, int g_n_states, float alpha, float beta, int frames_before,
+                                          int max_frames, void* state, size_t state_bytes, void* workspace, size_t workspace_bytes);
+int asr_gram_ctc_beam_bias_stream_result(void* stream, const float* uni, int vlm, const int32_t* keys, const float* vals, int slots,
+                                         int max_probe, int order, int bos, int eos, const int32_t* g_keys, const int32_t* g_vals,
+                                         int g_slots, int g_max_probe, const float* g_ret, int g_n_states, float alpha, float beta,
+                                         int B, int beam_width, int max_frames, int blank, int Lcap, const void* state,
+                                         size_t state_bytes, int32_t* out_ids, int32_t* out_len, float* out_score, float* out_ctc,
+                                         float* out_lm, float* out_bias, int32_t* out_frames);
 
 /* ---------------------------------------------------------------------------------------- dense projections
  * bf16 MFMA GEMMs (f32 accumulate).  Replace the BLAS/cuDNN calls behind chainer.links.Linear, the 1x1
