@@ -160,19 +160,101 @@ def bigru_sum(x_tbi, params, H, ndir=2):
 
 
 # ---------------------------------------------------------------------------------------------- optimiser
-def clip_decay_adam(p, g, m, v, step, alpha=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, decay=1e-5, clip=1.0):
+def gradient_factor(sqnorm, clip, grad_scale=1.0):
+    """What every gradient element is multiplied by before the decay is added: grad_scale (1 / world size after a sum
+    all-reduce, 1 / loss scale) times GradientClipping's min(1, clip / ||grad_scale g||).  clip = 0: no clipping; a zero
+    norm never clips (clip / 0 is not < 1)."""
+    norm = float(np.sqrt(sqnorm)) * abs(grad_scale)
+    if clip > 0 and norm > 0 and clip / norm < 1:
+        return grad_scale * (clip / norm)
+    return grad_scale
+
+
+def clip_decay_adam(p, g, m, v, step, alpha=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, decay=1e-5, clip=1.0, grad_scale=1.0):
     """GradientClipping(clip) -> WeightDecay(decay) -> Chainer-v2 Adam (run/ctc/cnn/train.py:142-147; Chainer is an
     absent third-party: formulas recalled from chainer/optimizers/adam.py v2, PARITY UNPINNED)."""
-    norm = np.sqrt((g.astype(np.float64) ** 2).sum())
-    rate = clip / norm
-    if clip > 0 and rate < 1:
-        g = g * rate
+    g = g.astype(np.float64)
+    g = g * gradient_factor((g ** 2).sum(), clip, grad_scale)
     g = g + decay * p
     m = m + (1 - beta1) * (g - m)
     v = v + (1 - beta2) * (g * g - v)
     lr = alpha * np.sqrt(1 - beta2 ** step) / (1 - beta1 ** step)
     p = p - lr * m / (np.sqrt(v) + eps)
     return p, m, v
+
+
+def clip_decay_sgd(p, g, v, kind, lr, momentum, decay, clip, grad_scale=1.0):
+    """GradientClipping(clip) -> WeightDecay(decay) -> one of the three rules asr/optimizers.py:43-52 offers beside Adam
+    (Chainer is an absent third party: formulas recalled from chainer/optimizers/{sgd,momentum_sgd,nesterov_ag}.py v2,
+    PARITY UNPINNED; tests/test_oracle_misc.py pins kinds 0 and 1 to torch.optim.SGD and kind 2 to a hand-worked example):
+      kind 0  SGD          p -= lr g
+      kind 1  MomentumSGD  v = mu v - lr g;  p += v
+      kind 2  NesterovAG   v = mu v - lr g;  p += mu^2 v - (1 + mu) lr g      (the NEW v)
+    v may be None for kind 0 and comes back as it went in.  All float64."""
+    g = g.astype(np.float64)
+    g = g * gradient_factor((g ** 2).sum(), clip, grad_scale)
+    g = g + decay * p
+    if kind == 0:
+        return p - lr * g, v
+    v = momentum * v - lr * g
+    if kind == 1:
+        return p + v, v
+    if kind == 2:
+        return p + momentum * momentum * v - (1 + momentum) * lr * g, v
+    raise ValueError(kind)
+
+
+LOSS_SCALE_MIN, LOSS_SCALE_MAX = 2.0 ** -24, 2.0 ** 24
+
+
+def step_control(g, state, clip, grad_scale, alpha, beta1, beta2, abort=False, reserved_index=-1, loss_scale=None):
+    """What asr_step_control(_scaled) decides for one step: include/asr_hip.h, "optimiser step", in float64 and Python ints.
+
+    g: the flat gradient; state = (applied steps so far, give-up drops so far = ctl[6]); abort: an abort word is raised;
+    loss_scale: None or [S, applied steps since S changed, growth interval (0 = static), overflows so far].
+    Returns (ctl[0..6], applied steps afterwards, the loss-scale quadruple afterwards or None):
+      ctl[0] drop (1 / 0)   ctl[1] gradient factor   ctl[2] Adam's alpha_t   ctl[3] t   ctl[4] squared norm
+      ctl[5] dropped because a recurrence gave up   ctl[6] such drops, ever.
+    The step is dropped when the squared norm is not finite as a float32 (the device's format), an abort word is raised or the
+    reserved element is not finite; the last two are a recurrence giving up and leave the loss scale alone.  Any other drop is
+    an overflow: counted, and a dynamic scale is halved (not below 2^-24); `interval` applied steps in a row double it (not
+    above 2^24).  The gradient factor carries 1 / S of the scale the backward pass was seeded with, and is left unclipped on a
+    dropped step.  t counts applied steps only; alpha_t = alpha sqrt(1 - beta2^t) / (1 - beta1^t) with t clamped to >= 1.
+    The hyperparameters are used as given: a caller that compares with the device passes the float32 values widened."""
+    applied, gave_up_count = int(state[0]), float(state[1])
+    g = np.asarray(g, dtype=np.float64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        sq = float((g ** 2).sum())
+        finite = bool(np.isfinite(np.float32(sq)))
+    drop = not finite
+    gave_up = bool(abort)
+    if reserved_index >= 0 and not np.isfinite(g[reserved_index]):
+        gave_up = True
+    if gave_up:
+        drop = True
+    ls = None
+    if loss_scale is not None:
+        ls = [float(x) for x in loss_scale]
+        grad_scale = grad_scale / ls[0]
+        if drop and not gave_up:
+            if ls[2] > 0:
+                ls[0] = max(ls[0] * 0.5, LOSS_SCALE_MIN)
+            ls[1] = 0.0
+            ls[3] += 1.0
+        elif not drop:
+            ls[1] += 1.0
+            if ls[2] > 0 and ls[1] >= ls[2]:
+                ls[0] = min(ls[0] * 2.0, LOSS_SCALE_MAX)
+                ls[1] = 0.0
+    rate = grad_scale if drop else gradient_factor(sq, clip, grad_scale)
+    if not drop:
+        applied += 1
+    t = max(applied, 1)
+    alpha_t = alpha * np.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t)
+    if gave_up:
+        gave_up_count += 1.0
+    ctl = [1.0 if drop else 0.0, float(rate), float(alpha_t), float(applied), sq, 1.0 if gave_up else 0.0, gave_up_count]
+    return ctl, applied, ls
 
 
 def batch_normalization(x, gamma, beta, avg_mean, avg_var, eps=2e-5, decay=0.9, train=True):
