@@ -123,6 +123,11 @@ SIGNATURES = {
     "asr_gram_ctc_beam_bias_stream_result": (c_int, [c_void_p] * 2 + [c_int, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 2
                                              + [c_int] * 2 + [c_void_p, c_int] + [c_float, c_float] + [c_int] * 5
                                              + [c_void_p, c_size_t] + [c_void_p] * 7),
+    "asr_beam_stream_commit_workspace_bytes": (c_size_t, [c_int] * 4),
+    "asr_ctc_beam_stream_commit": (c_int, [c_void_p] * 2 + [c_size_t] + [c_int] * 5 + [c_void_p, c_int, c_void_p, c_int, c_int]
+                                   + [c_void_p, c_size_t, c_void_p, c_int] + [c_void_p] * 4),
+    "asr_gram_ctc_beam_stream_commit": (c_int, [c_void_p] * 2 + [c_size_t] + [c_int] * 5 + [c_void_p, c_int, c_void_p, c_int, c_int]
+                                        + [c_void_p, c_size_t, c_void_p, c_int] + [c_void_p] * 4),
     "asr_ctc_align_workspace_bytes": (c_size_t, [c_int] * 5),
     "asr_ctc_align": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p] * 9 + [c_size_t]),
     "asr_kws_workspace_bytes": (c_size_t, [c_int] * 3),

@@ -1135,6 +1135,33 @@ def gram_ctc_beam_bias_stream_result(state, B, beam_width, max_frames, blank, Lc
     return (ids, out_len) + scores, frames
 
 
+def beam_stream_commit_workspace_bytes(B, beam_width, max_frames, per_frame):
+    """bytes of the per-call scratch of beam_stream_commit (asr_beam_stream_commit_workspace_bytes; host only)"""
+    return _lib.lib().asr_beam_stream_commit_workspace_bytes(int(B), int(beam_width), int(max_frames), int(per_frame))
+
+
+def beam_stream_commit(state, gram, B, beam_width, max_frames, with_lm, with_bias, prefix=None, prefix_len=None, compact=True,
+                       max_rows=None, out_pitch=1):
+    """commit a prefix of the beam kept in `state` and compact its prefix table (asr_ctc_beam_stream_commit, or with `gram`
+    asr_gram_ctc_beam_stream_commit on a state of gram_ctc_beam_bias_stream_state_bytes); `prefix` (B, n) int32 with `prefix_len`
+    (B) int32, or None for the longest common prefix; `max_rows`: None for max_frames -> (tokens (B, out_pitch) int32 zero-padded,
+    counts, committed, rows, status (B) int32)"""
+    dev = state.device
+    per_frame = 2 if gram else 1
+    nbytes = _lib.lib().asr_beam_stream_commit_workspace_bytes(int(B), int(beam_width), int(max_frames), per_frame)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    out_pitch = max(int(out_pitch), 1)
+    tokens = torch.zeros((B, out_pitch), dtype=I32, device=dev)
+    counts, committed, rows, status = (torch.empty((B,), dtype=I32, device=dev) for _ in range(4))
+    name = "asr_gram_ctc_beam_stream_commit" if gram else "asr_ctc_beam_stream_commit"
+    rc = getattr(_lib.lib(), name)(stream(), ptr(state), state.numel(), int(B), int(beam_width), int(max_frames), int(bool(with_lm)),
+                                   int(bool(with_bias)), ptr(prefix), 0 if prefix is None else prefix.shape[1], ptr(prefix_len),
+                                   int(bool(compact)), int(max_frames if max_rows is None else max_rows), ptr(ws), nbytes,
+                                   ptr(tokens), out_pitch, ptr(counts), ptr(committed), ptr(rows), ptr(status))
+    check(rc, name)
+    return tokens, counts, committed, rows, status
+
+
 def ctc_align(xs, label_unigram, label_bigram, x_len, l_len, blank):
     """(T, B, V) f32 logits + labels (B, Lmax) int32 (label_bigram None: CTC, else Gram-CTC) -> the forced alignment
     (frame_ids (B, T), tok_ids, tok_pos, tok_start, tok_end (B, Lmax) int32, tok_logp (B, Lmax) f32, n_tok (B) int32,

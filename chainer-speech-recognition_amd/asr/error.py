@@ -104,7 +104,10 @@ def beam_decode_biased(logits, graph, lm=None, lm_weight=0.0, length_bonus=0.0, 
 
 class _Stream:
     """What ``BeamStream`` and ``GramBeamStream`` share: the dimensions and options, the device, the frame counts (`fed` on the
-    host, `frames` on the device) and the argument checks of ``reset`` and ``advance``."""
+    host, `frames` on the device), the argument checks of ``reset`` and ``advance``, and ``commit``, which lets a stream run
+    for any number of frames."""
+
+    _GRAM = False                                 # the Gram-CTC stream: two table nodes (characters) per frame and beam slot
 
     def __init__(self, B, V, max_frames, beam_width, top_k, blank, min_logp, lm, lm_weight, length_bonus, device):
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -114,20 +117,100 @@ class _Stream:
         self.lm_weight, self.length_bonus = (float(lm_weight), float(length_bonus)) if lm is not None else (0.0, 0.0)
         self.fed = 0                              # frames fed since the last full reset: the capacity every slot has used
         self.frames = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
+        self.committed = [[] for _ in range(self.B)]          # per utterance: the tokens ``commit`` has made final
+        self.frames_base = torch.zeros((self.B,), dtype=torch.int32, device=self.device)   # frames - the table rows in use
 
     def _new_state(self, nbytes):
         self.state = torch.zeros(max(nbytes, 1), dtype=torch.uint8, device=self.device)
         self.reset()
 
     def _reset_mask(self, mask):
-        """`mask` of ``reset`` as a (B) int32 device tensor; None (a full reset) also starts the frame count over"""
+        """`mask` of ``reset`` as a (B) int32 device tensor; None (a full reset) also starts the frame count over.  Once tokens
+        have been committed the masked slots' ``committed`` lists are emptied here, for which a mask given as a device tensor
+        is copied to the host (a synchronisation; a mask given as a list or a host array costs none)."""
         if mask is None:
             self.fed = 0
+            self.committed = [[] for _ in range(self.B)]
+            self.frames_base.zero_()
             return None
+        host = mask
         mask = torch.as_tensor(mask).to(self.device, torch.int32).contiguous()
         if tuple(mask.shape) != (self.B,):
             raise ValueError("mask must have one entry per utterance (%d)" % self.B)
+        self.frames_base.masked_fill_(mask != 0, 0)   # (a commit of no tokens compacts as well: not only where tokens are committed)
+        if any(self.committed):                   # (only a stream that has committed tokens looks at the mask on the host)
+            for b, on in enumerate(torch.as_tensor(host).tolist()):
+                if on:
+                    self.committed[b] = []
         return mask
+
+    def _set_frames(self, rows):
+        """``frames`` from result's out_frames, which counts table rows once something has been committed"""
+        self.frames = torch.where(rows < 0, rows, rows + self.frames_base)
+
+    def commit(self, prefix=None, lengths=None, compact=True):
+        """Make a prefix final and free the table rows behind it.  `prefix` (B, n) token ids (characters for the Gram-CTC stream)
+        with `lengths` (B) or None (all n), host or device: per utterance the hypotheses whose tokens after the committed ones
+        do not start with it are dropped, the prefix is appended to ``self.committed[b]``, and ``result()`` returns what comes
+        after it from then on.  `prefix` None, or a negative length: the longest common prefix of the live hypotheses, which
+        drops nothing.  An utterance none of whose hypotheses starts with its prefix is refused and stays as it is.
+        `compact` False only reports.  -> (tokens (B, width) int32: the first counts[b] of a row are what this call committed,
+        the rest is 0, and width = max(the table's tokens per slot in use, n, 1), i.e. what an auto commit could commit;
+        counts (B); status (B): 1 applied, 0 refused, -1 another stream's state) on the device.  Unlike the other methods this
+        one synchronises with the host: it reads the counts to keep ``committed`` and the capacity check of ``advance``, which
+        counts table rows in use after a commit.  (``reset(mask)`` with a device mask does too, once tokens are committed.)"""
+        per = 2 if self._GRAM else 1
+        pitch = per * self.fed
+        if prefix is not None:
+            prefix = torch.as_tensor(prefix).to(self.device, torch.int32)
+            if prefix.dim() != 2 or prefix.shape[0] != self.B:
+                raise ValueError("prefix must be (%d, n), got %s" % (self.B, tuple(prefix.shape)))
+            n = prefix.shape[1]
+            if lengths is None:
+                lengths = torch.full((self.B,), n, dtype=torch.int32, device=self.device)
+            else:
+                lengths = torch.as_tensor(lengths).to(self.device, torch.int32).clamp(max=n).contiguous()
+                if tuple(lengths.shape) != (self.B,):
+                    raise ValueError("lengths must have one entry per utterance (%d)" % self.B)
+            if n == 0:                            # nothing to compare: a row of one unused token keeps the pitch positive
+                prefix = torch.zeros((self.B, 1), dtype=torch.int32, device=self.device)
+            prefix = prefix.contiguous()
+            pitch = max(pitch, n)
+        before = self.state[:self.B * 32].view(torch.int32).view(self.B, 8)[:, 6].clone()       # the header's rows in use
+        tokens, counts, _, rows, status = _ops.beam_stream_commit(self.state, self._GRAM, self.B, self.beam_width, self.max_frames,
+                                                                   self.lm is not None, self.graph is not None, prefix, lengths,
+                                                                   compact, None, pitch)
+        if compact:
+            self.frames_base += torch.where(status == 1, before - rows, torch.zeros_like(rows))
+            host_tokens, host_counts = tokens.cpu().tolist(), counts.cpu().tolist()
+            for b in range(self.B):
+                self.committed[b].extend(host_tokens[b][:host_counts[b]])
+            self.fed = max(int(rows.max()), 0)
+        return tokens, counts, status
+
+    def commit_best(self, hold=8):
+        """the usual policy: commit the best hypothesis of every utterance without its last `hold` tokens -> ``commit``'s tuple"""
+        out = self.result()
+        return self.commit(out[0][:, 0], (out[1][:, 0] - int(hold)).clamp(min=0))
+
+    def full_result(self, use_eos=True):
+        """``result()`` with ``self.committed`` put back in front of every hypothesis: the tuple an uncommitted stream returns, as
+        long as every commit was of the common prefix; ids (B, beam_width, longest committed + the tails' width)"""
+        out = self.result(use_eos)
+        ids, lens, scores = out[0], out[1], out[2]
+        counts = [len(c) for c in self.committed]
+        width = max(counts)
+        if width == 0:
+            return out
+        live = scores > -float("inf")
+        full = torch.full((self.B, self.beam_width, width + ids.shape[2]), self.blank, dtype=ids.dtype, device=self.device)
+        for b, done in enumerate(self.committed):
+            full[b, :, len(done):len(done) + ids.shape[2]] = ids[b]
+            if done:
+                full[b, :, :len(done)] = torch.tensor(done, dtype=ids.dtype, device=self.device)
+        full = torch.where(live[:, :, None], full, torch.full_like(full, self.blank))
+        lens = torch.where(live, lens + torch.tensor(counts, dtype=lens.dtype, device=self.device)[:, None], lens)
+        return (full, lens) + tuple(out[2:])
 
     def _chunk(self, logits, lengths):
         """the arguments of ``advance``, checked -> (logits, lengths) on the device, or None for an empty chunk"""
@@ -157,9 +240,16 @@ class BeamStream(_Stream):
             ids, lens, scores, ctc, lms = s.result()
 
     ``reset()`` starts all utterances over; ``reset(mask)`` only those with mask[b] != 0, so a serving loop can put a new
-    utterance into a batch slot while the others go on.  The prefix table holds `max_frames` frames per utterance and is not
-    compacted: the frames fed are counted on the host from the last full reset, a partial reset does not lower that count, and
-    feeding beyond `max_frames` raises ValueError.  Nothing here synchronises with the host."""
+    utterance into a batch slot while the others go on.  The prefix table holds `max_frames` frames per utterance: the frames
+    fed are counted on the host from the last full reset, a partial reset does not lower that count, and feeding beyond
+    `max_frames` raises ValueError.  Nothing here synchronises with the host, except ``commit`` and, once tokens have been
+    committed, ``reset(mask)`` with a mask that is a device tensor (a list or a host array costs nothing).
+
+    A stream longer than `max_frames` commits as it goes: ``commit(prefix)`` makes a prefix of the hypotheses final, drops the
+    hypotheses that disagree with it and frees the table rows behind it, and ``commit_best(hold)`` does so with the best
+    hypothesis minus its last `hold` tokens.  From then on ``result()`` returns tails, the tokens after ``self.committed[b]``,
+    with the scores of the whole hypotheses; ``full_result()`` puts the committed tokens back in front; the capacity check counts
+    the table rows in use, and ``frames`` still counts the frames consumed."""
 
     def __init__(self, B, V, max_frames, beam_width=16, top_k=16, blank=0, min_logp=None, lm=None, lm_weight=0.0, length_bonus=0.0,
                  graph=None, device=None):
@@ -197,8 +287,9 @@ class BeamStream(_Stream):
         device: the frames every utterance has consumed."""
         image, graph = self._images()
         eos = self.lm.eos_id if self.lm is not None and use_eos else -1
-        out, self.frames = _ops.ctc_beam_stream_result(self.state, self.B, self.beam_width, self.max_frames, self.blank,
-                                                       max(self.fed, 1), image, graph, self.lm_weight, self.length_bonus, eos)
+        out, rows = _ops.ctc_beam_stream_result(self.state, self.B, self.beam_width, self.max_frames, self.blank,
+                                                max(self.fed, 1), image, graph, self.lm_weight, self.length_bonus, eos)
+        self._set_frames(rows)
         return (out[0][:, :, :self.fed],) + out[1:]
 
 
@@ -309,7 +400,10 @@ class GramBeamStream(_Stream):
     `gram` is validated once, here, as ``gram_beam_decode`` validates it; `lm` as in ``gram_beam_decode_lm`` (``lm.vlm < V`` raises
     ValueError); `graph` as in ``gram_beam_decode_biased`` (built for another V or blank raises ValueError), and with it
     ``result()`` returns the 6-tuple.  ``reset``, partial resets, the frame count and `max_frames` behave as in ``BeamStream``;
-    the prefix table holds two characters per frame.  Nothing here synchronises with the host."""
+    the prefix table holds two characters per frame.  Nothing here synchronises with the host, except ``commit``, which works
+    as in ``BeamStream`` with characters for tokens."""
+
+    _GRAM = True
 
     def __init__(self, B, V, max_frames, gram, beam_width=16, top_k=16, blank=0, min_logp=None, lm=None, lm_weight=0.0,
                  length_bonus=0.0, device=None, graph=None):
@@ -361,16 +455,18 @@ class GramBeamStream(_Stream):
         ``frames`` (B) int32 on the device: the frames every utterance has consumed."""
         eos = self.lm.eos_id if self.lm is not None and use_eos else -1
         if self.graph is not None:
-            out, self.frames = _ops.gram_ctc_beam_bias_stream_result(self.state, self.B, self.beam_width, self.max_frames, self.blank,
-                                                                     max(2 * self.fed, 1),
-                                                                     None if self.lm is None else self.lm.image, self.graph.image,
-                                                                     self.lm_weight, self.length_bonus,
-                                                                     -1 if self.lm is None else self.lm.bos_id, eos)
+            out, rows = _ops.gram_ctc_beam_bias_stream_result(self.state, self.B, self.beam_width, self.max_frames, self.blank,
+                                                              max(2 * self.fed, 1),
+                                                              None if self.lm is None else self.lm.image, self.graph.image,
+                                                              self.lm_weight, self.length_bonus,
+                                                              -1 if self.lm is None else self.lm.bos_id, eos)
+            self._set_frames(rows)
             return (out[0][:, :, :2 * self.fed],) + out[1:]
-        out, self.frames = _ops.gram_ctc_beam_stream_result(self.state, self.B, self.beam_width, self.max_frames, self.blank,
-                                                            max(2 * self.fed, 1), None if self.lm is None else self.lm.image,
-                                                            self.lm_weight, self.length_bonus,
-                                                            -1 if self.lm is None else self.lm.bos_id, eos)
+        out, rows = _ops.gram_ctc_beam_stream_result(self.state, self.B, self.beam_width, self.max_frames, self.blank,
+                                                     max(2 * self.fed, 1), None if self.lm is None else self.lm.image,
+                                                     self.lm_weight, self.length_bonus,
+                                                     -1 if self.lm is None else self.lm.bos_id, eos)
+        self._set_frames(rows)
         return (out[0][:, :, :2 * self.fed],) + out[1:]
 
 

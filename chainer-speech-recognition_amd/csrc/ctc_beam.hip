@@ -310,8 +310,9 @@ struct BiasLds<true> {
 // beam_kernel<., ., ONESHOT> carries none of this and is the one-shot search as it was.
 constexpr int ONESHOT = 0, ADVANCE = 1, RESULT = 2;
 constexpr int STATE_MAGIC = 0x43424d53;
-constexpr int HDR_WORDS = 8;      // per utterance: magic, B, beam_width, max_frames, variant, m, frames consumed, 0
-constexpr int H_MAGIC = 0, H_B = 1, H_W = 2, H_F = 3, H_VARIANT = 4, H_M = 5, H_FRAMES = 6;
+constexpr int HDR_WORDS = 8;      // per utterance: magic, B, beam_width, max_frames, variant, m, table rows in use, tokens committed
+constexpr int H_MAGIC = 0, H_B = 1, H_W = 2, H_F = 3, H_VARIANT = 4, H_M = 5, H_FRAMES = 6, H_COMMITTED = 7;
+// H_FRAMES is the frames consumed until the first commit (commit_kernel below); H_COMMITTED is 0 until then
 
 struct State {
     int* hdr;                                        // (B, HDR_WORDS)
@@ -416,12 +417,19 @@ __device__ inline void stream_end(int* hdr, int m, int frames) {
 
 // The two halves of every N-best tail; the caller's own writes for the slot sit between them.
 // fill_blank: in the utterance's ids, rows of `pitch`, the positions from a hypothesis' length on get blank; row i < m is beam slot
-// order[i] (slot i with no order), the rows from m on are all blank.
-__device__ inline void fill_blank(int32_t* ids, int pitch, int W, int m, const int* len, const int* order, int blank) {
+// order[i] (slot i with no order), the rows from m on are all blank.  `c`: the utterance's committed tokens, which the rows leave out.
+__device__ inline void fill_blank(int32_t* ids, int pitch, int W, int m, const int* len, const int* order, int blank, int c) {
     for (size_t k = threadIdx.x; k < (size_t)W * pitch; k += THREADS) {
         const int i = (int)(k / pitch), p = (int)(k - (size_t)i * pitch);
-        if (p >= (i < m ? len[order ? order[i] : i] : 0)) ids[k] = blank;
+        if (p >= (i < m ? len[order ? order[i] : i] - c : 0)) ids[k] = blank;
     }
+}
+
+// RESULT after a commit: the tokens a hypothesis of length `len` has beyond the utterance's `c` committed ones, which is what its
+// chain in the prefix table holds and what result returns; c is 0 in the other modes and in a stream that never committed.
+template <int MODE>
+__device__ inline int tail_len(int len, int c) {
+    return MODE == RESULT ? max(len - c, 0) : len;
 }
 
 // walk_chain: one hypothesis of length L walks its prefix table chain from node nd back to the root and writes its row of ids.
@@ -810,8 +818,11 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
     }
     // the N-best, sorted by score: the ids by fill_blank and walk_chain (RESULT: a hypothesis longer than the row pitch is cut there, and its
     // length is reported in full)
-    int table_n = 0;
-    if constexpr (MODE == RESULT) table_n = sz.max_frames * W;
+    int table_n = 0, cm = 0;                           // cm: the committed tokens (RESULT only)
+    if constexpr (MODE == RESULT) {
+        table_n = sz.max_frames * W;
+        if (m > 0) cm = max(sz.s.hdr[(size_t)b * HDR_WORDS + H_COMMITTED], 0);
+    }
     int32_t* ids = out_ids + (size_t)b * W * T;
     if constexpr (LM || BIAS) {
         // the end terms, then the final order: score descending, ties to the earlier slot
@@ -844,10 +855,10 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
             if constexpr (BIAS) bz.out_bias[b * W + rank] = bv;
         }
         __syncthreads();
-        fill_blank(ids, T, W, m, o.len, sv_pos, blank);
+        fill_blank(ids, T, W, m, o.len, sv_pos, blank, cm);
         if (tid < W) {
             if (tid < m) {
-                const int h = sv_pos[tid], L = o.len[h];
+                const int h = sv_pos[tid], L = tail_len<MODE>(o.len[h], cm);
                 out_len[b * W + tid] = L;
                 walk_chain<MODE>(ids + (size_t)tid * T, T, L, o.node[h], nodes, table_n);
             } else {
@@ -860,10 +871,10 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
         }
         return;
     }
-    fill_blank(ids, T, W, m, o.len, nullptr, blank);
+    fill_blank(ids, T, W, m, o.len, nullptr, blank, cm);
     if (tid < W) {
         if (tid < m) {
-            const int L = o.len[tid];
+            const int L = tail_len<MODE>(o.len[tid], cm);
             out_len[b * W + tid] = L;
             out_score[b * W + tid] = lae(o.pb[tid], o.pnb[tid]);
             walk_chain<MODE>(ids + (size_t)tid * T, T, L, o.node[tid], nodes, table_n);
@@ -1954,8 +1965,11 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
     }
     // the N-best strings, sorted by score: the ids by fill_blank and walk_chain (RESULT: a string longer than the row pitch is cut there, and its
     // length is reported in full)
-    int table_n = 0;
-    if constexpr (MODE == RESULT) table_n = 2 * sz.max_frames * W;
+    int table_n = 0, cm = 0;                           // cm: the committed characters (RESULT only)
+    if constexpr (MODE == RESULT) {
+        table_n = 2 * sz.max_frames * W;
+        if (m > 0) cm = max(sz.s.hdr[(size_t)b * HDR_WORDS + H_COMMITTED], 0);
+    }
     int32_t* ids = out_ids + (size_t)b * W * T2;
     if constexpr (LM || BIAS) {
         // the end terms, then the final order: score descending, ties to the earlier slot (as beam_kernel<true, .>)
@@ -1990,10 +2004,10 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
             if constexpr (BIAS) bz.out_bias[b * W + rank] = bv;
         }
         __syncthreads();
-        fill_blank(ids, T2, W, m, o.len, sv_pos, blank);
+        fill_blank(ids, T2, W, m, o.len, sv_pos, blank, cm);
         if (tid < W) {
             if (tid < m) {
-                const int h = sv_pos[tid], L = o.len[h];
+                const int h = sv_pos[tid], L = tail_len<MODE>(o.len[h], cm);
                 out_len[b * W + tid] = L;
                 walk_chain<MODE>(ids + (size_t)tid * T2, T2, L, o.node[h], nodes, table_n);
             } else {
@@ -2006,10 +2020,10 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
         }
         return;
     }
-    fill_blank(ids, T2, W, m, o.len, nullptr, blank);
+    fill_blank(ids, T2, W, m, o.len, nullptr, blank, cm);
     if (tid < W) {
         if (tid < m) {
-            const int L = o.len[tid];
+            const int L = tail_len<MODE>(o.len[tid], cm);
             out_len[b * W + tid] = L;
             out_score[b * W + tid] = lae3(o.pb[tid], o.pu[tid], o.pg[tid]);
             walk_chain<MODE>(ids + (size_t)tid * T2, T2, L, o.node[tid], nodes, table_n);
@@ -2367,4 +2381,244 @@ extern "C" int asr_gram_ctc_beam_stream_result(void* stream, const float* uni, i
     return asr_gram_ctc_beam_bias_stream_result(stream, uni, vlm, keys, vals, slots, max_probe, order, bos, eos, nullptr, nullptr, 0, 0,
                                                 nullptr, 0, alpha, beta, B, beam_width, max_frames, blank, Lcap, state, state_bytes,
                                                 out_ids, out_len, out_score, out_ctc, out_lm, nullptr, out_frames);
+}
+
+// ------------------------------------------------------------------------------ commit: a stream of any length
+// asr_ctc_beam_stream_commit / asr_gram_ctc_beam_stream_commit.  The caller names a prefix P of the tokens beyond the committed
+// ones; the hypotheses that do not start with it leave the beam, P is reported as final, and the prefix table is rewritten to
+// hold only what the kept hypotheses have after P, one private chain per beam slot, so that it needs as many rows as the longest
+// such tail has tokens (Gram-CTC: half as many) and not as many as frames were fed.  The semantics are stated in
+// include/asr_hip.h.  One kernel serves both families and every variant: it knows the header, len, node and the table, and gets
+// the other per-slot arrays as a list of pointers, because all it does with them is move entries to the front.
+namespace asr {
+namespace beam {
+
+constexpr int MAX_ARR4 = 12, MAX_ARR8 = 3;
+
+struct CommitArrays {
+    int* a4[MAX_ARR4];                                // the (B, W) arrays of 4-byte entries except node (len is one of them)
+    unsigned long long* a8[MAX_ARR8];                 // those of 8-byte entries
+    int n4, n8;
+};
+
+struct CommitOut {
+    int32_t* ids;                                     // (B, pitch): the tokens this call committed (the first min(n, pitch) of a row)
+    int pitch;
+    int32_t* len;                                     // (B) their count n
+    int32_t* committed;                               // (B) the utterance's committed count after the call
+    int32_t* rows;                                    // (B) the table rows in use after the call
+    int32_t* status;                                  // (B) 1 applied, 0 refused, -1 header mismatch
+};
+
+// stage: (B, W, cap) int32 with cap = per_frame * F: the tails of the live hypotheses, walked out of the table before it is rewritten
+__global__ __launch_bounds__(THREADS) void commit_kernel(int* __restrict__ hdr_all, int* len_all, int* __restrict__ node_all,
+                                                         int2* __restrict__ table, CommitArrays arr, int B, int W, int F, int variant,
+                                                         int per_frame, const int32_t* __restrict__ prefix_ids, int prefix_pitch,
+                                                         const int32_t* __restrict__ prefix_len, int compact, int max_rows,
+                                                         int32_t* __restrict__ stage_all, CommitOut out) {
+    __shared__ int s_L[MAX_BEAM], s_k[MAX_BEAM], s_src[MAX_BEAM], s_l[MAX_BEAM];
+    __shared__ int wsum[4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int* hdr = hdr_all + (size_t)b * HDR_WORDS;
+    if (!state_matches(hdr, B, W, F, variant)) {
+        if (tid == 0) {
+            out.len[b] = 0;
+            out.committed[b] = -1;
+            out.rows[b] = -1;
+            out.status[b] = -1;
+        }
+        return;
+    }
+    const int cap = per_frame * F, table_n = cap * W;
+    const int m = min(max(hdr[H_M], 0), W), rows0 = min(max(hdr[H_FRAMES], 0), F), c = max(hdr[H_COMMITTED], 0);
+    int2* nodes = table + (size_t)b * table_n;
+    int32_t* stage = stage_all + (size_t)b * table_n;
+    int* len = len_all + (size_t)b * W;
+    int* node = node_all + (size_t)b * W;
+    // 1. every live hypothesis walks its chain into its staging row: the tokens beyond the committed ones, L of them
+    int L = 0;
+    if (tid < m) {
+        L = min(max(len[tid] - c, 0), cap);
+        int32_t* row = stage + (size_t)tid * cap;
+        int nd = node[tid], p = L - 1;
+        for (; p >= 0; --p) {
+            if ((unsigned)nd >= (unsigned)table_n) break;        // a state that other code wrote into: the chain ends here
+            const int2 e = nodes[nd];
+            row[p] = e.y;
+            nd = e.x;
+        }
+        for (; p >= 0; --p) row[p] = -1;
+        s_L[tid] = L;
+    }
+    __threadfence_block();
+    __syncthreads();
+    // 2. the prefix: the caller's, or the longest one that all live hypotheses share
+    int n = prefix_ids ? prefix_len[b] : -1;
+    const bool automatic = n < 0;
+    bool keep = tid < m;
+    if (automatic) {
+        if (tid < m) {
+            const int32_t* mine = stage + (size_t)tid * cap;
+            const int lim = min(L, s_L[0]);
+            int k = 0;
+            while (k < lim && mine[k] == stage[k]) ++k;
+            s_k[tid] = k;
+        }
+        __syncthreads();
+        n = m > 0 ? s_k[0] : 0;
+        for (int i = 1; i < m; ++i) n = min(n, s_k[i]);
+    } else if (n > prefix_pitch) {
+        keep = false;                                            // a prefix longer than its row: refused
+    } else if (tid < m) {
+        const int32_t* mine = stage + (size_t)tid * cap;
+        const int32_t* P = prefix_ids + (size_t)b * prefix_pitch;
+        keep = L >= n;
+        for (int k = 0; keep && k < n; ++k) keep = mine[k] == P[k];
+    }
+    // 3. the kept hypotheses' places, the longest tail and the rows it needs
+    int total;
+    const int pos = block_excl_scan(keep ? 1 : 0, wsum, &total);
+    if (tid < MAX_BEAM) s_l[tid] = 0;
+    __syncthreads();
+    if (keep) {
+        s_src[pos] = tid;
+        s_l[pos] = L - n;
+    }
+    __syncthreads();
+    int maxl = 0;
+    for (int i = 0; i < total; ++i) maxl = max(maxl, s_l[i]);
+    const int rows = (maxl + per_frame - 1) / per_frame;
+    if (total == 0 || rows > min(max_rows, F)) {
+        if (tid == 0) {
+            out.len[b] = 0;
+            out.committed[b] = c;
+            out.rows[b] = rows0;
+            out.status[b] = 0;
+        }
+        return;
+    }
+    {
+        const int32_t* first = stage + (size_t)s_src[0] * cap;
+        for (int k = tid; k < min(n, out.pitch); k += THREADS) out.ids[(size_t)b * out.pitch + k] = first[k];
+        if (tid == 0) {
+            out.len[b] = n;
+            out.committed[b] = c + n;
+            out.rows[b] = rows;
+            out.status[b] = 1;
+        }
+    }
+    if (!compact) return;
+    // 4. the per-slot arrays: every entry is read before any is written, then the kept ones go to the front in their order and
+    // the slots they leave behind, up to the old m, get 0, so that the bytes of the state depend on what is kept alone
+#pragma unroll
+    for (int a = 0; a < MAX_ARR4; ++a) {
+        if (a < arr.n4) {
+            int* p = arr.a4[a] + (size_t)b * W;
+            const int v = tid < m ? p[tid] : 0;
+            __syncthreads();
+            if (keep) p[pos] = v;
+            if (tid >= total && tid < m) p[tid] = 0;
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < MAX_ARR8; ++a) {
+        if (a < arr.n8) {
+            unsigned long long* p = arr.a8[a] + (size_t)b * W;
+            const unsigned long long v = tid < m ? p[tid] : 0;
+            __syncthreads();
+            if (keep) p[pos] = v;
+            if (tid >= total && tid < m) p[tid] = 0;
+        }
+    }
+    // (pos < total <= the slots that get 0, and every slot below `total` is one kept entry's target: no slot is written twice)
+    // 5. the table: tail position j of kept slot q is node j * W + q; the rows that were in use hold nothing else.  The chains were
+    // read in step 1 and only the staging rows are read here.
+    __threadfence();
+    __syncthreads();
+    const int fill = max(rows0, rows) * per_frame;
+    for (int k = tid; k < fill * W; k += THREADS) {
+        const int j = k / W, q = k - j * W;
+        int2 e = make_int2(0, 0);
+        if (q < total && j < s_l[q]) e = make_int2(j > 0 ? k - W : -1, stage[(size_t)s_src[q] * cap + n + j]);
+        nodes[k] = e;
+    }
+    if (tid < m) node[tid] = tid < total ? (s_l[tid] > 0 ? (s_l[tid] - 1) * W + tid : -1) : 0;
+    if (tid == 0) {
+        hdr[H_M] = total;
+        hdr[H_FRAMES] = rows;
+        hdr[H_COMMITTED] = c + n;
+    }
+}
+
+// the staging rows of commit_kernel
+static size_t commit_ws_bytes(int B, int W, int F, int per_frame) { return align256((size_t)B * W * F * per_frame * 4); }
+
+// what the two commit entries check besides their state, in the order of the other streaming entries
+static int commit_check(int lim, const int32_t* prefix_ids, int prefix_pitch, const int32_t* prefix_len, int max_rows,
+                        const void* workspace, const CommitOut& out) {
+    if (lim == ASR_ERR_BAD_ARG) return lim;
+    if (!workspace || !out.ids || !out.len || !out.committed || !out.rows || !out.status || out.pitch <= 0 || max_rows < 0)
+        return ASR_ERR_BAD_ARG;
+    if (prefix_ids && (!prefix_len || prefix_pitch <= 0)) return ASR_ERR_BAD_ARG;
+    return lim;
+}
+
+}  // namespace beam
+}  // namespace asr
+
+extern "C" size_t asr_beam_stream_commit_workspace_bytes(int B, int beam_width, int max_frames, int per_frame) {
+    if ((per_frame != 1 && per_frame != 2) || stream_dims(true, B, beam_width, max_frames, per_frame) != ASR_OK) return 0;
+    return commit_ws_bytes(B, beam_width, max_frames, per_frame);
+}
+
+extern "C" int asr_ctc_beam_stream_commit(void* stream, void* state, size_t state_bytes, int B, int beam_width, int max_frames,
+                                          int with_lm, int with_bias, const int32_t* prefix_ids, int prefix_pitch,
+                                          const int32_t* prefix_len, int compact, int max_rows, void* workspace,
+                                          size_t workspace_bytes, int32_t* out_ids, int out_pitch, int32_t* out_len,
+                                          int32_t* out_committed, int32_t* out_rows, int32_t* out_status) {
+    const CommitOut out{out_ids, out_pitch, out_len, out_committed, out_rows, out_status};
+    const int rc = commit_check(stream_dims(state != nullptr, B, beam_width, max_frames, 1), prefix_ids, prefix_pitch, prefix_len,
+                                max_rows, workspace, out);
+    if (rc != ASR_OK) return rc;
+    const int variant = ctc_variant(with_lm, with_bias);
+    State s;
+    if (state_bytes < state_layout(B, beam_width, max_frames, variant, (char*)state, &s)) return ASR_ERR_WORKSPACE;
+    if (workspace_bytes < commit_ws_bytes(B, beam_width, max_frames, 1)) return ASR_ERR_WORKSPACE;
+    CommitArrays arr{};
+    for (void* p : {(void*)s.pb, (void*)s.pnb, (void*)s.len, (void*)s.last, (void*)s.plast, (void*)s.lm, (void*)s.c0, (void*)s.c1,
+                    (void*)s.c2, (void*)s.open, (void*)s.state})
+        if (p) arr.a4[arr.n4++] = (int*)p;
+    arr.a8[arr.n8++] = s.hash;
+    arr.a8[arr.n8++] = s.phash;
+    hipLaunchKernelGGL(commit_kernel, dim3(B), dim3(THREADS), 0, (hipStream_t)stream, s.hdr, s.len, s.node, s.table, arr, B, beam_width,
+                       max_frames, variant, 1, prefix_ids, prefix_pitch, prefix_len, compact, max_rows, (int32_t*)workspace, out);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+extern "C" int asr_gram_ctc_beam_stream_commit(void* stream, void* state, size_t state_bytes, int B, int beam_width, int max_frames,
+                                               int with_lm, int with_bias, const int32_t* prefix_ids, int prefix_pitch,
+                                               const int32_t* prefix_len, int compact, int max_rows, void* workspace,
+                                               size_t workspace_bytes, int32_t* out_ids, int out_pitch, int32_t* out_len,
+                                               int32_t* out_committed, int32_t* out_rows, int32_t* out_status) {
+    const CommitOut out{out_ids, out_pitch, out_len, out_committed, out_rows, out_status};
+    const int rc = commit_check(stream_dims(state != nullptr, B, beam_width, max_frames, 2), prefix_ids, prefix_pitch, prefix_len,
+                                max_rows, workspace, out);
+    if (rc != ASR_OK) return rc;
+    const int variant = gram_variant(with_lm, with_bias);
+    GState s;
+    GBiasState bs;
+    if (state_bytes < gram_state_layout(B, beam_width, max_frames, variant, (char*)state, &s, &bs)) return ASR_ERR_WORKSPACE;
+    if (workspace_bytes < commit_ws_bytes(B, beam_width, max_frames, 2)) return ASR_ERR_WORKSPACE;
+    CommitArrays arr{};
+    for (void* p : {(void*)s.pb, (void*)s.pu, (void*)s.pg, (void*)s.len, (void*)s.c1, (void*)s.c2, (void*)s.c3, (void*)s.utok,
+                    (void*)s.gtok, (void*)s.lm, (void*)bs.open, (void*)bs.state})
+        if (p) arr.a4[arr.n4++] = (int*)p;
+    arr.a8[arr.n8++] = s.h0;
+    arr.a8[arr.n8++] = s.h1;
+    arr.a8[arr.n8++] = s.h2;
+    hipLaunchKernelGGL(commit_kernel, dim3(B), dim3(THREADS), 0, (hipStream_t)stream, s.hdr, s.len, s.node, s.table, arr, B, beam_width,
+                       max_frames, variant, 2, prefix_ids, prefix_pitch, prefix_len, compact, max_rows, (int32_t*)workspace, out);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
 }

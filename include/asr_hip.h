@@ -609,6 +609,51 @@ int asr_gram_ctc_beam_bias_stream_result(void* stream, const float* uni, int vlm
                                          int B, int beam_width, int max_frames, int blank, int Lcap, const void* state,
                                          size_t state_bytes, int32_t* out_ids, int32_t* out_len, float* out_score, float* out_ctc,
                                          float* out_lm, float* out_bias, int32_t* out_frames);
+/* Commit: streams of any length.  The prefix table of a stream holds max_frames rows and advance never frees
+ * one; a commit makes a prefix of the hypotheses final, drops the hypotheses that disagree with it, and rewrites the table so that
+ * it holds only what comes after that prefix.  A caller that commits "the best hypothesis minus its last few tokens" every few
+ * chunks feeds a stream of any length through a table of a few dozen rows.  Both families, every variant; per_frame below is 1 for
+ * the CTC stream and 2 for the Gram-CTC stream (a token there is a character).
+ *   Every utterance has a committed count c: header word 7 of its state, 0 after reset.  Every live hypothesis has len tokens, and
+ *   its first c are the committed ones.  commit(P), P a string of n >= 0 tokens per utterance (prefix_ids (B, prefix_pitch),
+ *   prefix_len (B)), does per utterance:
+ *   prune    exactly the hypotheses whose tokens [c, c + n) equal P are kept.
+ *   refuse   if none would be kept, if n > prefix_pitch, or if the kept tails need more than min(max_rows, max_frames) rows, the
+ *            utterance's state is left as it is and status is 0.
+ *   beam     the kept entries move to the front of every per-slot array in their order (the searches rank ties to the lower slot,
+ *            so the order is part of the search state) and the occupancy becomes their number.  len, the hashes, the model
+ *            contexts and the automaton states stay absolute: every score and every later ranking has the bits it would have
+ *            had.  The slots the beam leaves behind get 0.
+ *   compact  the tail of kept slot i is its l_i = len[i] - c - n tokens after P; tail position j becomes node j * beam_width + i
+ *            with parent (j - 1) * beam_width + i (-1 for j = 0), node[i] = (l_i - 1) * beam_width + i or -1, and the rest of
+ *            the rows that were in use gets 0.  The header's frames word becomes rows = ceil(max_i l_i / per_frame), and the next
+ *            advance allocates from that row on.  So after the first commit that word means "table rows in use" (it is what
+ *            result's out_frames reports and what advance's frames_before must bound); for a stream that never committed it
+ *            equals the frames consumed.  c += n.
+ *   auto     prefix_len[b] < 0, or prefix_ids == NULL for every utterance: P is the longest common prefix of all live hypotheses
+ *            beyond c.  Nothing is pruned, and whatever the stream returns afterwards is, after prepending the committed tokens,
+ *            bit for bit what it would have returned without the call.
+ *   compact == 0 makes the call read-only: the outputs say what it would commit, the state is not written.
+ * Outputs per utterance: out_status 1 applied, 0 refused, -1 header mismatch (the state is left alone, out_committed and out_rows
+ * are -1); out_ids (B, out_pitch) the first min(n, out_pitch) tokens this call committed (the rest of a row is not written), out_len
+ * their count n (0 unless applied); out_committed the new c; out_rows the rows in use after the call.
+ * After a commit, result returns tails: out_ids holds the tokens after the c committed ones and out_len = len - c; the scores are
+ * those of the whole hypotheses.  With c = 0 this is the result described above.
+ *   workspace asr_beam_stream_commit_workspace_bytes(B, beam_width, max_frames, per_frame) bytes: the live tails, staged
+ * Errors as in the other streaming entries (NULL state, workspace or output, out_pitch <= 0, max_rows < 0, prefix_ids without
+ * prefix_len or with prefix_pitch <= 0: ASR_ERR_BAD_ARG; then the limits: ASR_ERR_UNSUPPORTED; a short state or workspace:
+ * ASR_ERR_WORKSPACE), all before the launch.  One launch, no atomics, nothing allocated, copied to the host or synchronised; the
+ * same inputs give the same state bytes.  The Gram-CTC entry's state is that of asr_gram_ctc_beam_bias_stream_state_bytes. */
+size_t asr_beam_stream_commit_workspace_bytes(int B, int beam_width, int max_frames, int per_frame);
+int asr_ctc_beam_stream_commit(void* stream, void* state, size_t state_bytes, int B, int beam_width, int max_frames, int with_lm,
+                               int with_bias, const int32_t* prefix_ids, int prefix_pitch, const int32_t* prefix_len, int compact,
+                               int max_rows, void* workspace, size_t workspace_bytes, int32_t* out_ids, int out_pitch,
+                               int32_t* out_len, int32_t* out_committed, int32_t* out_rows, int32_t* out_status);
+int asr_gram_ctc_beam_stream_commit(void* stream, void* state, size_t state_bytes, int B, int beam_width, int max_frames, int with_lm,
+                                    int with_bias, const int32_t* prefix_ids, int prefix_pitch, const int32_t* prefix_len,
+                                    int compact, int max_rows, void* workspace, size_t workspace_bytes, int32_t* out_ids,
+                                    int out_pitch, int32_t* out_len, int32_t* out_committed, int32_t* out_rows,
+                                    int32_t* out_status);
 
 /* ---------------------------------------------------------------------------------------- dense projections
  * bf16 MFMA GEMMs (f32 accumulate).  Replace the BLAS/cuDNN calls behind chainer.links.Linear, the 1x1
