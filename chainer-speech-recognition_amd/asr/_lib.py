@@ -38,6 +38,14 @@ c_void_p, c_int, c_float, c_size_t = ctypes.c_void_p, ctypes.c_int, ctypes.c_flo
 c_double = ctypes.c_double
 c_longlong = ctypes.c_longlong
 
+# the argument runs that the beam search entries share (include/asr_hip.h names them the same way everywhere)
+_LM = [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int]       # uni, vlm, keys, vals, slots, max_probe, order
+_GRAPH = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int]           # g_keys, g_vals, g_slots, g_max_probe, g_ret, g_n_states
+_SEARCH = [c_void_p] * 3 + [c_int] * 6 + [c_float]     # stream, logits, lengths, T, B, V, blank, beam_width, top_k, min_logp
+_FUSE = [c_int, c_int, c_float, c_float]               # bos, eos, alpha, beta
+_ADVANCE = [c_float, c_float, c_int, c_int]            # alpha, beta, frames_before, max_frames
+_WS = [c_void_p, c_size_t]                             # a buffer and its bytes: workspace, state
+
 # name -> (restype, argtypes).  Mirrors include/asr_hip.h one to one; tests/test_abi.py checks both ways.
 SIGNATURES = {
     "asr_version": (c_int, []),
@@ -82,47 +90,34 @@ SIGNATURES = {
     "asr_nbest_consensus_workspace_bytes": (c_size_t, [c_int] * 3),
     "asr_nbest_consensus": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p, c_void_p, c_size_t]),
     "asr_ctc_beam_workspace_bytes": (c_size_t, [c_int] * 5),
-    "asr_ctc_beam_search": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_float, c_void_p, c_size_t] + [c_void_p] * 3),
-    "asr_ngram_score": (c_int, [c_void_p] * 2 + [c_int, c_void_p, c_void_p] + [c_int] * 3 + [c_void_p] * 2 + [c_int] * 4 + [c_void_p] * 2),
+    "asr_ctc_beam_search": (c_int, _SEARCH + _WS + [c_void_p] * 3),
+    "asr_ngram_score": (c_int, [c_void_p] + _LM + [c_void_p] * 2 + [c_int] * 4 + [c_void_p] * 2),
     "asr_ctc_beam_lm_workspace_bytes": (c_size_t, [c_int] * 5),
-    "asr_ctc_beam_search_lm": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_float, c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 5
-                               + [c_float, c_float, c_void_p, c_size_t] + [c_void_p] * 5),
-    "asr_ctx_score": (c_int, [c_void_p] * 3 + [c_int] * 2 + [c_void_p] + [c_int] * 2 + [c_void_p] * 2 + [c_int] * 3 + [c_void_p] * 2),
+    "asr_ctc_beam_search_lm": (c_int, _SEARCH + _LM + _FUSE + _WS + [c_void_p] * 5),
+    "asr_ctx_score": (c_int, [c_void_p] + _GRAPH + [c_int] + [c_void_p] * 2 + [c_int] * 3 + [c_void_p] * 2),
     "asr_ctc_beam_bias_workspace_bytes": (c_size_t, [c_int] * 5),
-    "asr_ctc_beam_search_bias": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_float, c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 5
-                                 + [c_float, c_float, c_void_p, c_size_t] + [c_void_p] * 7 + [c_int] * 2 + [c_void_p, c_int, c_void_p]),
+    "asr_ctc_beam_search_bias": (c_int, _SEARCH + _LM + _FUSE + _WS + [c_void_p] * 5 + _GRAPH + [c_void_p]),
     "asr_ctc_beam_stream_state_bytes": (c_size_t, [c_int] * 5),
     "asr_ctc_beam_stream_workspace_bytes": (c_size_t, [c_int] * 5),
     "asr_ctc_beam_stream_reset": (c_int, [c_void_p] * 2 + [c_size_t] + [c_int] * 6 + [c_void_p]),
-    "asr_ctc_beam_stream_advance": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_float, c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 3
-                                    + [c_void_p] * 2 + [c_int] * 2 + [c_void_p, c_int, c_float, c_float, c_int, c_int]
-                                    + [c_void_p, c_size_t] * 2),
-    "asr_ctc_beam_stream_result": (c_int, [c_void_p] * 2 + [c_int, c_void_p, c_void_p] + [c_int] * 3 + [c_void_p] * 2 + [c_int] * 2
-                                   + [c_void_p, c_int, c_float, c_float] + [c_int] * 6 + [c_void_p, c_size_t] + [c_void_p] * 7),
+    "asr_ctc_beam_stream_advance": (c_int, _SEARCH + _LM + _GRAPH + _ADVANCE + _WS * 2),
+    "asr_ctc_beam_stream_result": (c_int, [c_void_p] + _LM + _GRAPH + [c_float] * 2 + [c_int] * 6 + _WS + [c_void_p] * 7),
     "asr_gram_ctc_beam_workspace_bytes": (c_size_t, [c_int] * 5),
-    "asr_gram_ctc_beam_search": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_float, c_void_p, c_void_p, c_size_t] + [c_void_p] * 3),
+    "asr_gram_ctc_beam_search": (c_int, _SEARCH + [c_void_p] + _WS + [c_void_p] * 3),
     "asr_gram_ctc_beam_lm_workspace_bytes": (c_size_t, [c_int] * 5),
-    "asr_gram_ctc_beam_search_lm": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
-                                    + [c_int] * 5 + [c_float, c_float, c_void_p, c_size_t] + [c_void_p] * 5),
+    "asr_gram_ctc_beam_search_lm": (c_int, _SEARCH + [c_void_p] + _LM + _FUSE + _WS + [c_void_p] * 5),
     "asr_gram_ctc_beam_stream_state_bytes": (c_size_t, [c_int] * 4),
     "asr_gram_ctc_beam_stream_workspace_bytes": (c_size_t, [c_int] * 5),
     "asr_gram_ctc_beam_stream_reset": (c_int, [c_void_p] * 2 + [c_size_t] + [c_int] * 4 + [c_void_p]),
-    "asr_gram_ctc_beam_stream_advance": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
-                                         + [c_int] * 4 + [c_float, c_float, c_int, c_int] + [c_void_p, c_size_t] * 2),
-    "asr_gram_ctc_beam_stream_result": (c_int, [c_void_p] * 2 + [c_int, c_void_p, c_void_p] + [c_int] * 5 + [c_float, c_float]
-                                        + [c_int] * 5 + [c_void_p, c_size_t] + [c_void_p] * 6),
+    "asr_gram_ctc_beam_stream_advance": (c_int, _SEARCH + [c_void_p] + _LM + [c_int] + _ADVANCE + _WS * 2),
+    "asr_gram_ctc_beam_stream_result": (c_int, [c_void_p] + _LM + [c_int] * 2 + [c_float] * 2 + [c_int] * 5 + _WS + [c_void_p] * 6),
     "asr_gram_ctc_beam_bias_workspace_bytes": (c_size_t, [c_int] * 5),
-    "asr_gram_ctc_beam_search_bias": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
-                                      + [c_int] * 5 + [c_float, c_float, c_void_p, c_size_t] + [c_void_p] * 7 + [c_int] * 2
-                                      + [c_void_p, c_int, c_void_p]),
+    "asr_gram_ctc_beam_search_bias": (c_int, _SEARCH + [c_void_p] + _LM + _FUSE + _WS + [c_void_p] * 5 + _GRAPH + [c_void_p]),
     "asr_gram_ctc_beam_bias_stream_state_bytes": (c_size_t, [c_int] * 5),
     "asr_gram_ctc_beam_bias_stream_reset": (c_int, [c_void_p] * 2 + [c_size_t] + [c_int] * 5 + [c_void_p]),
-    "asr_gram_ctc_beam_bias_stream_advance": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_float, c_void_p, c_void_p, c_int, c_void_p,
-                                                      c_void_p] + [c_int] * 4 + [c_void_p] * 2 + [c_int] * 2 + [c_void_p, c_int]
-                                              + [c_float, c_float, c_int, c_int] + [c_void_p, c_size_t] * 2),
-    "asr_gram_ctc_beam_bias_stream_result": (c_int, [c_void_p] * 2 + [c_int, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 2
-                                             + [c_int] * 2 + [c_void_p, c_int] + [c_float, c_float] + [c_int] * 5
-                                             + [c_void_p, c_size_t] + [c_void_p] * 7),
+    "asr_gram_ctc_beam_bias_stream_advance": (c_int, _SEARCH + [c_void_p] + _LM + [c_int] + _GRAPH + _ADVANCE + _WS * 2),
+    "asr_gram_ctc_beam_bias_stream_result": (c_int, [c_void_p] + _LM + [c_int] * 2 + _GRAPH + [c_float] * 2 + [c_int] * 5 + _WS
+                                             + [c_void_p] * 7),
     "asr_beam_stream_commit_workspace_bytes": (c_size_t, [c_int] * 4),
     "asr_ctc_beam_stream_commit": (c_int, [c_void_p] * 2 + [c_size_t] + [c_int] * 5 + [c_void_p, c_int, c_void_p, c_int, c_int]
                                    + [c_void_p, c_size_t, c_void_p, c_int] + [c_void_p] * 4),

@@ -831,19 +831,128 @@ def _check_gram(gram, V, dev):
         raise ValueError("gram must be a contiguous (V, 2) int32 tensor on the logits' device")
 
 
+_NO_LM = (None, 0, None, None, 0, 0, 0)
+_NO_GRAPH = (None, None, 0, 0, None, 0)
+
+
+def _lm_args(image):
+    """(uni, vlm, keys, vals, slots, max_probe, order) of a device image of asr.lm.NGramLM.to(device)"""
+    return (ptr(image["uni"]), int(image["uni"].shape[0]), ptr(image["keys"]), ptr(image["vals"]), int(image["slots"]),
+            int(image["max_probe"]), int(image["order"]))
+
+
+def _graph_args(image):
+    """(keys, vals, slots, max_probe, ret, n_states) of a device image of asr.bias.ContextGraph.to(device)"""
+    return (ptr(image["keys"]), ptr(image["vals"]), int(image["slots"]), int(image["max_probe"]), ptr(image["ret"]),
+            int(image["n_states"]))
+
+
+def _lm_or_none(image):
+    return _NO_LM if image is None else _lm_args(image)
+
+
+def _graph_or_none(graph):
+    return _NO_GRAPH if graph is None else _graph_args(graph)
+
+
+# ---- the beam searches.  One implementation per kind of entry; the public names below it are forwards that say which C entry
+# they reach.  The C arguments come in the runs that _lib names: the search's, [gram], the model's, the graph's, the buffers.
+def _beam_search(kind, logits, lengths, blank, beam_width, top_k, min_logp, gram=None, image=None, graph=None, alpha=0.0, beta=0.0,
+                 bos=-1, eos=-1):
+    """the one-shot search asr_[gram_]ctc_beam_search`kind` (Gram-CTC with `gram`): kind "" returns (ids, lengths, scores), "_lm"
+    (the model `image`) adds ctc_scores and lm_scores, "_bias" (`graph`, and `image` or None) adds bias_scores as well"""
+    T, B, V = logits.shape
+    dev = logits.device
+    if gram is not None:
+        _check_gram(gram, V, dev)
+    name = "asr_gram_ctc_beam" if gram is not None else "asr_ctc_beam"
+    nbytes = getattr(_lib.lib(), name + kind + "_workspace_bytes")(T, B, V, int(beam_width), int(top_k))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    ids, out_len, scores = _nbest_out(B, beam_width, (2 if gram is not None else 1) * T, dev, {"": 1, "_lm": 3, "_bias": 4}[kind])
+    args = [stream(), ptr(logits), ptr(lengths), T, B, V, int(blank), int(beam_width), int(top_k), _min_logp(min_logp)]
+    if gram is not None:
+        args.append(ptr(gram))
+    if kind:
+        args += _lm_args(image) if kind == "_lm" else _lm_or_none(image)
+        args += [int(bos), int(eos), float(alpha), float(beta)]
+    args += [ptr(ws), nbytes, ptr(ids), ptr(out_len)] + [ptr(s) for s in scores[:3]]
+    if kind == "_bias":
+        args += _graph_args(graph) + (ptr(scores[3]),)
+    check(getattr(_lib.lib(), name + "_search" + kind)(*args), name + "_search" + kind)
+    return (ids, out_len) + scores
+
+
+# The three families of streaming entries: CTC's, Gram-CTC's without a graph argument, and Gram-CTC's with one.  Only CTC's
+# reset takes bos (Gram-CTC's advance and result do), only CTC's result takes eos after the weights, and "gram" has no with_bias,
+# no graph and no out_bias.
+_STREAM = {"ctc": "asr_ctc_beam_stream_", "gram": "asr_gram_ctc_beam_stream_", "gram_bias": "asr_gram_ctc_beam_bias_stream_"}
+
+
+def _stream_flags(fam, with_lm, with_bias):
+    return [int(bool(with_lm))] + ([] if fam == "gram" else [int(bool(with_bias))])
+
+
+def _stream_state_bytes(fam, B, beam_width, max_frames, with_lm, with_bias=False):
+    return getattr(_lib.lib(), _STREAM[fam] + "state_bytes")(int(B), int(beam_width), int(max_frames),
+                                                             *_stream_flags(fam, with_lm, with_bias))
+
+
+def _stream_workspace_bytes(fam, Tc, B, V, beam_width, top_k):
+    name = _STREAM["ctc" if fam == "ctc" else "gram"] + "workspace_bytes"           # one size with or without a graph
+    return getattr(_lib.lib(), name)(int(Tc), int(B), int(V), int(beam_width), int(top_k))
+
+
+def _stream_reset(fam, state, B, beam_width, max_frames, with_lm, with_bias, bos, mask):
+    name = _STREAM[fam] + "reset"
+    rc = getattr(_lib.lib(), name)(stream(), ptr(state), state.numel(), int(B), int(beam_width), int(max_frames),
+                                   *_stream_flags(fam, with_lm, with_bias), *([int(bos)] if fam == "ctc" else []), ptr(mask))
+    check(rc, name)
+
+
+def _stream_advance(fam, state, logits, lengths, blank, beam_width, top_k, gram, frames_before, max_frames, image, graph, alpha, beta,
+                    bos, min_logp):
+    Tc, B, V = logits.shape
+    if fam != "ctc":
+        _check_gram(gram, V, logits.device)
+    nbytes = _stream_workspace_bytes(fam, Tc, B, V, beam_width, top_k)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=logits.device)
+    args = [stream(), ptr(logits), ptr(lengths), Tc, B, V, int(blank), int(beam_width), int(top_k), _min_logp(min_logp)]
+    if fam != "ctc":
+        args.append(ptr(gram))
+    args += _lm_or_none(image)
+    if fam != "ctc":
+        args.append(int(bos))
+    if fam != "gram":
+        args += _graph_or_none(graph)
+    args += [float(alpha), float(beta), int(frames_before), int(max_frames), ptr(state), state.numel(), ptr(ws), nbytes]
+    check(getattr(_lib.lib(), _STREAM[fam] + "advance")(*args), _STREAM[fam] + "advance")
+
+
+def _stream_result(fam, state, B, beam_width, max_frames, blank, Lcap, image, graph, alpha, beta, bos, eos):
+    dev = state.device
+    n = 1 if image is None and graph is None else (3 if graph is None else 4)
+    ids, out_len, scores = _nbest_out(B, beam_width, Lcap, dev, n)
+    frames = torch.empty((B,), dtype=I32, device=dev)
+    extra = [ptr(s) for s in scores[1:]] + [None] * ((3 if fam == "gram" else 4) - n)
+    args = [stream(), *_lm_or_none(image)]
+    if fam != "ctc":
+        args += [int(bos), int(eos)]
+    if fam != "gram":
+        args += _graph_or_none(graph)
+    args += [float(alpha), float(beta)]
+    if fam == "ctc":
+        args.append(int(eos))
+    args += [int(B), int(beam_width), int(max_frames), int(blank), int(Lcap), ptr(state), state.numel(), ptr(ids), ptr(out_len),
+             ptr(scores[0]), *extra, ptr(frames)]
+    check(getattr(_lib.lib(), _STREAM[fam] + "result")(*args), _STREAM[fam] + "result")
+    return (ids, out_len) + scores, frames
+
+
 def ctc_beam_search(logits, lengths, blank, beam_width, top_k, min_logp=None):
     """(T, B, V) f32 logits -> (ids (B, beam_width, T) int32 padded with blank, lengths (B, beam_width) int32,
     scores (B, beam_width) f32): the N-best of the CTC prefix beam search, best first; unused slots have length 0 and
     score -inf.  `lengths` (B) int32 or None (all T frames); min_logp None: no candidate threshold."""
-    T, B, V = logits.shape
-    dev = logits.device
-    nbytes = _lib.lib().asr_ctc_beam_workspace_bytes(T, B, V, int(beam_width), int(top_k))
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    ids, out_len, (scores,) = _nbest_out(B, beam_width, T, dev)
-    rc = _lib.lib().asr_ctc_beam_search(stream(), ptr(logits), ptr(lengths), T, B, V, int(blank), int(beam_width), int(top_k),
-                                        _min_logp(min_logp), ptr(ws), nbytes, ptr(ids), ptr(out_len), ptr(scores))
-    check(rc, "asr_ctc_beam_search")
-    return ids, out_len, scores
+    return _beam_search("", logits, lengths, blank, beam_width, top_k, min_logp)
 
 
 def gram_ctc_beam_search(logits, lengths, blank, beam_width, top_k, gram, min_logp=None):
@@ -851,22 +960,7 @@ def gram_ctc_beam_search(logits, lengths, blank, beam_width, top_k, gram, min_lo
     lengths (B, beam_width) int32, scores (B, beam_width) f32): the N-best strings of the Gram-CTC beam search
     (asr_gram_ctc_beam_search), best first; unused slots have length 0 and score -inf.  The table is not checked here
     (asr.error.gram_beam_decode does)."""
-    T, B, V = logits.shape
-    dev = logits.device
-    _check_gram(gram, V, dev)
-    nbytes = _lib.lib().asr_gram_ctc_beam_workspace_bytes(T, B, V, int(beam_width), int(top_k))
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    ids, out_len, (scores,) = _nbest_out(B, beam_width, 2 * T, dev)
-    rc = _lib.lib().asr_gram_ctc_beam_search(stream(), ptr(logits), ptr(lengths), T, B, V, int(blank), int(beam_width), int(top_k),
-                                             _min_logp(min_logp), ptr(gram), ptr(ws), nbytes, ptr(ids), ptr(out_len), ptr(scores))
-    check(rc, "asr_gram_ctc_beam_search")
-    return ids, out_len, scores
-
-
-def _lm_args(image):
-    """(uni, vlm, keys, vals, slots, max_probe, order) of a device image of asr.lm.NGramLM.to(device)"""
-    return (ptr(image["uni"]), int(image["uni"].shape[0]), ptr(image["keys"]), ptr(image["vals"]), int(image["slots"]),
-            int(image["max_probe"]), int(image["order"]))
+    return _beam_search("", logits, lengths, blank, beam_width, top_k, min_logp, gram)
 
 
 def ngram_score(image, ids, lengths=None, bos=-1, eos=-1):
@@ -887,22 +981,7 @@ def ngram_score(image, ids, lengths=None, bos=-1, eos=-1):
 def ctc_beam_search_lm(logits, lengths, blank, beam_width, top_k, image, alpha, beta, bos=-1, eos=-1, min_logp=None):
     """ctc_beam_search ranked by ctc + alpha * lm + beta * len (asr_ctc_beam_search_lm) -> (ids, lengths, scores, ctc_scores,
     lm_scores); `image`: the device image of an asr.lm.NGramLM"""
-    T, B, V = logits.shape
-    dev = logits.device
-    nbytes = _lib.lib().asr_ctc_beam_lm_workspace_bytes(T, B, V, int(beam_width), int(top_k))
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    ids, out_len, (scores, ctc, lm) = _nbest_out(B, beam_width, T, dev, 3)
-    rc = _lib.lib().asr_ctc_beam_search_lm(stream(), ptr(logits), ptr(lengths), T, B, V, int(blank), int(beam_width), int(top_k),
-                                           _min_logp(min_logp), *_lm_args(image), int(bos), int(eos), float(alpha), float(beta),
-                                           ptr(ws), nbytes, ptr(ids), ptr(out_len), ptr(scores), ptr(ctc), ptr(lm))
-    check(rc, "asr_ctc_beam_search_lm")
-    return ids, out_len, scores, ctc, lm
-
-
-def _graph_args(image):
-    """(keys, vals, slots, max_probe, ret, n_states) of a device image of asr.bias.ContextGraph.to(device)"""
-    return (ptr(image["keys"]), ptr(image["vals"]), int(image["slots"]), int(image["max_probe"]), ptr(image["ret"]),
-            int(image["n_states"]))
+    return _beam_search("_lm", logits, lengths, blank, beam_width, top_k, min_logp, None, image, None, alpha, beta, bos, eos)
 
 
 def ctx_score(image, V, ids, lengths=None, finalize=True):
@@ -926,108 +1005,61 @@ def ctc_beam_search_bias(logits, lengths, blank, beam_width, top_k, graph, image
     """ctc_beam_search (image None) or ctc_beam_search_lm ranked with the phrase bonus of `graph` on top
     (asr_ctc_beam_search_bias) -> (ids, lengths, scores, ctc_scores, lm_scores, bias_scores); `graph`: the device image of an
     asr.bias.ContextGraph, `image`: that of an asr.lm.NGramLM"""
-    T, B, V = logits.shape
-    dev = logits.device
-    nbytes = _lib.lib().asr_ctc_beam_bias_workspace_bytes(T, B, V, int(beam_width), int(top_k))
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    ids, out_len, (scores, ctc, lm, bias) = _nbest_out(B, beam_width, T, dev, 4)
-    lm_args = _NO_LM if image is None else _lm_args(image)
-    rc = _lib.lib().asr_ctc_beam_search_bias(stream(), ptr(logits), ptr(lengths), T, B, V, int(blank), int(beam_width), int(top_k),
-                                             _min_logp(min_logp), *lm_args, int(bos), int(eos), float(alpha), float(beta), ptr(ws),
-                                             nbytes, ptr(ids), ptr(out_len), ptr(scores), ptr(ctc), ptr(lm), *_graph_args(graph),
-                                             ptr(bias))
-    check(rc, "asr_ctc_beam_search_bias")
-    return ids, out_len, scores, ctc, lm, bias
-
-
-_NO_LM = (None, 0, None, None, 0, 0, 0)
-_NO_GRAPH = (None, None, 0, 0, None, 0)
+    return _beam_search("_bias", logits, lengths, blank, beam_width, top_k, min_logp, None, image, graph, alpha, beta, bos, eos)
 
 
 def ctc_beam_stream_state_bytes(B, beam_width, max_frames, with_lm, with_bias):
     """bytes of the device-resident state of a streaming beam search (asr_ctc_beam_stream_state_bytes; host only)"""
-    return _lib.lib().asr_ctc_beam_stream_state_bytes(int(B), int(beam_width), int(max_frames), int(bool(with_lm)), int(bool(with_bias)))
+    return _stream_state_bytes("ctc", B, beam_width, max_frames, with_lm, with_bias)
 
 
 def ctc_beam_stream_workspace_bytes(Tc, B, V, beam_width, top_k):
     """bytes of the per-call scratch of ctc_beam_stream_advance for a chunk of Tc frames (host only)"""
-    return _lib.lib().asr_ctc_beam_stream_workspace_bytes(int(Tc), int(B), int(V), int(beam_width), int(top_k))
+    return _stream_workspace_bytes("ctc", Tc, B, V, beam_width, top_k)
 
 
 def ctc_beam_stream_reset(state, B, beam_width, max_frames, with_lm, with_bias, bos=-1, mask=None):
     """the root beam into `state` (uint8, ctc_beam_stream_state_bytes) for every utterance, or for those with mask[b] != 0
     (mask (B) int32 on the device): asr_ctc_beam_stream_reset"""
-    rc = _lib.lib().asr_ctc_beam_stream_reset(stream(), ptr(state), state.numel(), int(B), int(beam_width), int(max_frames),
-                                              int(bool(with_lm)), int(bool(with_bias)), int(bos), ptr(mask))
-    check(rc, "asr_ctc_beam_stream_reset")
+    _stream_reset("ctc", state, B, beam_width, max_frames, with_lm, with_bias, bos, mask)
 
 
 def ctc_beam_stream_advance(state, logits, lengths, blank, beam_width, top_k, frames_before, max_frames, image=None, graph=None,
                             alpha=0.0, beta=0.0, min_logp=None):
     """one chunk (Tc, B, V) f32 of logits into the beam kept in `state` (asr_ctc_beam_stream_advance); `lengths` (B) int32: the valid
     frames of this chunk per utterance, or None; `image` / `graph`: the device images of an asr.lm.NGramLM / asr.bias.ContextGraph"""
-    Tc, B, V = logits.shape
-    nbytes = _lib.lib().asr_ctc_beam_stream_workspace_bytes(Tc, B, V, int(beam_width), int(top_k))
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=logits.device)
-    rc = _lib.lib().asr_ctc_beam_stream_advance(stream(), ptr(logits), ptr(lengths), Tc, B, V, int(blank), int(beam_width),
-                                                int(top_k), _min_logp(min_logp), *(_NO_LM if image is None else _lm_args(image)),
-                                                *(_NO_GRAPH if graph is None else _graph_args(graph)), float(alpha), float(beta),
-                                                int(frames_before), int(max_frames), ptr(state), state.numel(), ptr(ws), nbytes)
-    check(rc, "asr_ctc_beam_stream_advance")
+    _stream_advance("ctc", state, logits, lengths, blank, beam_width, top_k, None, frames_before, max_frames, image, graph, alpha,
+                    beta, -1, min_logp)
 
 
 def ctc_beam_stream_result(state, B, beam_width, max_frames, blank, Lcap, image=None, graph=None, alpha=0.0, beta=0.0, eos=-1):
     """the N-best of the beam kept in `state`, which stays as it is (asr_ctc_beam_stream_result) -> ((ids (B, beam_width, Lcap),
     lengths, scores[, ctc_scores, lm_scores[, bias_scores]]) as the one-shot search of the same variant returns them,
     frames (B) int32: the frames every utterance has consumed)"""
-    dev = state.device
-    n = 1 if image is None and graph is None else (3 if graph is None else 4)
-    ids, out_len, scores = _nbest_out(B, beam_width, Lcap, dev, n)
-    frames = torch.empty((B,), dtype=I32, device=dev)
-    extra = [ptr(s) for s in scores[1:]] + [None] * (4 - n)
-    rc = _lib.lib().asr_ctc_beam_stream_result(stream(), *(_NO_LM if image is None else _lm_args(image)),
-                                               *(_NO_GRAPH if graph is None else _graph_args(graph)), float(alpha), float(beta),
-                                               int(eos), int(B), int(beam_width), int(max_frames), int(blank), int(Lcap),
-                                               ptr(state), state.numel(), ptr(ids), ptr(out_len), ptr(scores[0]), *extra,
-                                               ptr(frames))
-    check(rc, "asr_ctc_beam_stream_result")
-    return (ids, out_len) + scores, frames
+    return _stream_result("ctc", state, B, beam_width, max_frames, blank, Lcap, image, graph, alpha, beta, -1, eos)
 
 
 def gram_ctc_beam_search_lm(logits, lengths, blank, beam_width, top_k, gram, image, alpha, beta, bos=-1, eos=-1, min_logp=None):
     """gram_ctc_beam_search ranked by ctc + alpha * lm + beta * len over the spelled characters (asr_gram_ctc_beam_search_lm) ->
     (ids (B, beam_width, 2T), lengths, scores, ctc_scores, lm_scores); `image`: the device image of an asr.lm.NGramLM over the
     unigram ids of `gram`.  The table is not checked here (asr.error.gram_beam_decode_lm does)."""
-    T, B, V = logits.shape
-    dev = logits.device
-    _check_gram(gram, V, dev)
-    nbytes = _lib.lib().asr_gram_ctc_beam_lm_workspace_bytes(T, B, V, int(beam_width), int(top_k))
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    ids, out_len, (scores, ctc, lm) = _nbest_out(B, beam_width, 2 * T, dev, 3)
-    rc = _lib.lib().asr_gram_ctc_beam_search_lm(stream(), ptr(logits), ptr(lengths), T, B, V, int(blank), int(beam_width),
-                                                int(top_k), _min_logp(min_logp), ptr(gram), *_lm_args(image), int(bos), int(eos),
-                                                float(alpha), float(beta), ptr(ws), nbytes, ptr(ids), ptr(out_len), ptr(scores),
-                                                ptr(ctc), ptr(lm))
-    check(rc, "asr_gram_ctc_beam_search_lm")
-    return ids, out_len, scores, ctc, lm
+    return _beam_search("_lm", logits, lengths, blank, beam_width, top_k, min_logp, gram, image, None, alpha, beta, bos, eos)
 
 
 def gram_ctc_beam_stream_state_bytes(B, beam_width, max_frames, with_lm):
     """bytes of the device-resident state of a streaming Gram-CTC beam search (asr_gram_ctc_beam_stream_state_bytes; host only)"""
-    return _lib.lib().asr_gram_ctc_beam_stream_state_bytes(int(B), int(beam_width), int(max_frames), int(bool(with_lm)))
+    return _stream_state_bytes("gram", B, beam_width, max_frames, with_lm)
 
 
 def gram_ctc_beam_stream_workspace_bytes(Tc, B, V, beam_width, top_k):
     """bytes of the per-call scratch of gram_ctc_beam_stream_advance for a chunk of Tc frames (host only)"""
-    return _lib.lib().asr_gram_ctc_beam_stream_workspace_bytes(int(Tc), int(B), int(V), int(beam_width), int(top_k))
+    return _stream_workspace_bytes("gram", Tc, B, V, beam_width, top_k)
 
 
 def gram_ctc_beam_stream_reset(state, B, beam_width, max_frames, with_lm, mask=None):
     """the root beam into `state` (uint8, gram_ctc_beam_stream_state_bytes) for every utterance, or for those with mask[b] != 0
     (mask (B) int32 on the device): asr_gram_ctc_beam_stream_reset"""
-    rc = _lib.lib().asr_gram_ctc_beam_stream_reset(stream(), ptr(state), state.numel(), int(B), int(beam_width), int(max_frames),
-                                                   int(bool(with_lm)), ptr(mask))
-    check(rc, "asr_gram_ctc_beam_stream_reset")
+    _stream_reset("gram", state, B, beam_width, max_frames, with_lm, False, -1, mask)
 
 
 def gram_ctc_beam_stream_advance(state, logits, lengths, blank, beam_width, top_k, gram, frames_before, max_frames, image=None,
@@ -1035,33 +1067,15 @@ def gram_ctc_beam_stream_advance(state, logits, lengths, blank, beam_width, top_
     """one chunk (Tc, B, V) f32 of logits into the beam of strings kept in `state` (asr_gram_ctc_beam_stream_advance); gram (V, 2)
     int32 on the same device (not checked here); `lengths` (B) int32: the valid frames of this chunk per utterance, or None;
     `image`: the device image of an asr.lm.NGramLM over the unigram ids of `gram`"""
-    Tc, B, V = logits.shape
-    _check_gram(gram, V, logits.device)
-    nbytes = _lib.lib().asr_gram_ctc_beam_stream_workspace_bytes(Tc, B, V, int(beam_width), int(top_k))
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=logits.device)
-    rc = _lib.lib().asr_gram_ctc_beam_stream_advance(stream(), ptr(logits), ptr(lengths), Tc, B, V, int(blank), int(beam_width),
-                                                     int(top_k), _min_logp(min_logp), ptr(gram),
-                                                     *(_NO_LM if image is None else _lm_args(image)), int(bos), float(alpha),
-                                                     float(beta), int(frames_before), int(max_frames), ptr(state), state.numel(),
-                                                     ptr(ws), nbytes)
-    check(rc, "asr_gram_ctc_beam_stream_advance")
+    _stream_advance("gram", state, logits, lengths, blank, beam_width, top_k, gram, frames_before, max_frames, image, None, alpha,
+                    beta, bos, min_logp)
 
 
 def gram_ctc_beam_stream_result(state, B, beam_width, max_frames, blank, Lcap, image=None, alpha=0.0, beta=0.0, bos=-1, eos=-1):
     """the N-best strings of the beam kept in `state`, which stays as it is (asr_gram_ctc_beam_stream_result) -> ((ids (B, beam_width,
     Lcap), lengths, scores[, ctc_scores, lm_scores]) as the one-shot search of the same variant returns them, frames (B) int32:
     the frames every utterance has consumed)"""
-    dev = state.device
-    n = 1 if image is None else 3
-    ids, out_len, scores = _nbest_out(B, beam_width, Lcap, dev, n)
-    frames = torch.empty((B,), dtype=I32, device=dev)
-    extra = [ptr(s) for s in scores[1:]] + [None] * (3 - n)
-    rc = _lib.lib().asr_gram_ctc_beam_stream_result(stream(), *(_NO_LM if image is None else _lm_args(image)), int(bos), int(eos),
-                                                    float(alpha), float(beta), int(B), int(beam_width), int(max_frames),
-                                                    int(blank), int(Lcap), ptr(state), state.numel(), ptr(ids), ptr(out_len),
-                                                    ptr(scores[0]), *extra, ptr(frames))
-    check(rc, "asr_gram_ctc_beam_stream_result")
-    return (ids, out_len) + scores, frames
+    return _stream_result("gram", state, B, beam_width, max_frames, blank, Lcap, image, None, alpha, beta, bos, eos)
 
 
 def gram_ctc_beam_search_bias(logits, lengths, blank, beam_width, top_k, gram, graph, image=None, alpha=0.0, beta=0.0, bos=-1, eos=-1,
@@ -1070,69 +1084,35 @@ def gram_ctc_beam_search_bias(logits, lengths, blank, beam_width, top_k, gram, g
     (asr_gram_ctc_beam_search_bias) -> (ids (B, beam_width, 2T), lengths, scores, ctc_scores, lm_scores, bias_scores); `graph`: the
     device image of an asr.bias.ContextGraph over the unigram ids of `gram`, `image`: that of an asr.lm.NGramLM over them.  The
     table is not checked here (asr.error.gram_beam_decode_biased does)."""
-    T, B, V = logits.shape
-    dev = logits.device
-    _check_gram(gram, V, dev)
+    _check_gram(gram, logits.shape[2], logits.device)
     ptr(logits)                                   # a CPU tensor is refused here, before anything asks for the device's stream
-    nbytes = _lib.lib().asr_gram_ctc_beam_bias_workspace_bytes(T, B, V, int(beam_width), int(top_k))
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    ids, out_len, (scores, ctc, lm, bias) = _nbest_out(B, beam_width, 2 * T, dev, 4)
-    rc = _lib.lib().asr_gram_ctc_beam_search_bias(stream(), ptr(logits), ptr(lengths), T, B, V, int(blank), int(beam_width),
-                                                  int(top_k), _min_logp(min_logp), ptr(gram),
-                                                  *(_NO_LM if image is None else _lm_args(image)), int(bos), int(eos), float(alpha),
-                                                  float(beta), ptr(ws), nbytes, ptr(ids), ptr(out_len), ptr(scores), ptr(ctc),
-                                                  ptr(lm), *_graph_args(graph), ptr(bias))
-    check(rc, "asr_gram_ctc_beam_search_bias")
-    return ids, out_len, scores, ctc, lm, bias
+    return _beam_search("_bias", logits, lengths, blank, beam_width, top_k, min_logp, gram, image, graph, alpha, beta, bos, eos)
 
 
 def gram_ctc_beam_bias_stream_state_bytes(B, beam_width, max_frames, with_lm, with_bias):
     """bytes of the device-resident state of a streaming Gram-CTC beam search with or without a graph
     (asr_gram_ctc_beam_bias_stream_state_bytes; host only); without one, gram_ctc_beam_stream_state_bytes"""
-    return _lib.lib().asr_gram_ctc_beam_bias_stream_state_bytes(int(B), int(beam_width), int(max_frames), int(bool(with_lm)),
-                                                                int(bool(with_bias)))
+    return _stream_state_bytes("gram_bias", B, beam_width, max_frames, with_lm, with_bias)
 
 
 def gram_ctc_beam_bias_stream_reset(state, B, beam_width, max_frames, with_lm, with_bias, mask=None):
     """gram_ctc_beam_stream_reset for a state of gram_ctc_beam_bias_stream_state_bytes: asr_gram_ctc_beam_bias_stream_reset"""
-    rc = _lib.lib().asr_gram_ctc_beam_bias_stream_reset(stream(), ptr(state), state.numel(), int(B), int(beam_width), int(max_frames),
-                                                        int(bool(with_lm)), int(bool(with_bias)), ptr(mask))
-    check(rc, "asr_gram_ctc_beam_bias_stream_reset")
+    _stream_reset("gram_bias", state, B, beam_width, max_frames, with_lm, with_bias, -1, mask)
 
 
 def gram_ctc_beam_bias_stream_advance(state, logits, lengths, blank, beam_width, top_k, gram, frames_before, max_frames, image=None,
                                       graph=None, alpha=0.0, beta=0.0, bos=-1, min_logp=None):
     """gram_ctc_beam_stream_advance with `graph`, the device image of an asr.bias.ContextGraph over the unigram ids of `gram`, or
     None (asr_gram_ctc_beam_bias_stream_advance)"""
-    Tc, B, V = logits.shape
-    _check_gram(gram, V, logits.device)
-    nbytes = _lib.lib().asr_gram_ctc_beam_stream_workspace_bytes(Tc, B, V, int(beam_width), int(top_k))
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=logits.device)
-    rc = _lib.lib().asr_gram_ctc_beam_bias_stream_advance(stream(), ptr(logits), ptr(lengths), Tc, B, V, int(blank), int(beam_width),
-                                                          int(top_k), _min_logp(min_logp), ptr(gram),
-                                                          *(_NO_LM if image is None else _lm_args(image)), int(bos),
-                                                          *(_NO_GRAPH if graph is None else _graph_args(graph)), float(alpha),
-                                                          float(beta), int(frames_before), int(max_frames), ptr(state),
-                                                          state.numel(), ptr(ws), nbytes)
-    check(rc, "asr_gram_ctc_beam_bias_stream_advance")
+    _stream_advance("gram_bias", state, logits, lengths, blank, beam_width, top_k, gram, frames_before, max_frames, image, graph,
+                    alpha, beta, bos, min_logp)
 
 
 def gram_ctc_beam_bias_stream_result(state, B, beam_width, max_frames, blank, Lcap, image=None, graph=None, alpha=0.0, beta=0.0,
                                      bos=-1, eos=-1):
     """gram_ctc_beam_stream_result with `graph` (asr_gram_ctc_beam_bias_stream_result) -> ((ids (B, beam_width, Lcap), lengths,
     scores[, ctc_scores, lm_scores[, bias_scores]]) as the one-shot search of the same variant returns them, frames (B) int32)"""
-    dev = state.device
-    n = 1 if image is None and graph is None else (3 if graph is None else 4)
-    ids, out_len, scores = _nbest_out(B, beam_width, Lcap, dev, n)
-    frames = torch.empty((B,), dtype=I32, device=dev)
-    extra = [ptr(s) for s in scores[1:]] + [None] * (4 - n)
-    rc = _lib.lib().asr_gram_ctc_beam_bias_stream_result(stream(), *(_NO_LM if image is None else _lm_args(image)), int(bos), int(eos),
-                                                         *(_NO_GRAPH if graph is None else _graph_args(graph)), float(alpha),
-                                                         float(beta), int(B), int(beam_width), int(max_frames), int(blank),
-                                                         int(Lcap), ptr(state), state.numel(), ptr(ids), ptr(out_len),
-                                                         ptr(scores[0]), *extra, ptr(frames))
-    check(rc, "asr_gram_ctc_beam_bias_stream_result")
-    return (ids, out_len) + scores, frames
+    return _stream_result("gram_bias", state, B, beam_width, max_frames, blank, Lcap, image, graph, alpha, beta, bos, eos)
 
 
 def beam_stream_commit_workspace_bytes(B, beam_width, max_frames, per_frame):

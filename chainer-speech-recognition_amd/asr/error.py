@@ -49,6 +49,28 @@ def _needs_retokenisation(vocab_id_to_token, vocab_token_to_id):
     return False
 
 
+def _prepared(logits, blank, lengths, gram=None, lm=None, lm_weight=0.0, length_bonus=0.0, use_eos=True, graph=None):
+    """What the six decode functions do before their search, in the order their errors are raised: `graph` must have been built
+    for the logits' V and blank; `gram` is validated (``_gram_table``) and, in the Gram-CTC searches, ``lm.vlm`` against V;
+    `lengths`, `graph` and `lm` go to the logits' device.  -> (contiguous logits, lengths, the gram table or None, the model's
+    arguments (image, alpha, beta, bos, eos) with `eos` from `use_eos` (no model: None, 0, 0, -1, -1), the graph's image or None)"""
+    V, dev = logits.shape[2], logits.device
+    if graph is not None and (graph.V != V or graph.blank != blank):
+        raise ValueError("the context graph was built for %d ids with blank %d, the logits have %d with blank %d"
+                         % (graph.V, graph.blank, V, blank))
+    table = None if gram is None else _gram_table(gram, V, blank, dev)
+    if gram is not None and lm is not None and lm.vlm < V:
+        raise ValueError("the language model covers %d ids, fewer than the %d of the logits" % (lm.vlm, V))
+    if lengths is not None:
+        lengths = lengths.to(dev, torch.int32).contiguous()
+    image = None if graph is None else graph.to(dev).image
+    model = (None, 0.0, 0.0, -1, -1)
+    if lm is not None:
+        lm = lm.to(dev)
+        model = (lm.image, lm_weight, length_bonus, lm.bos_id, lm.eos_id if use_eos else -1)
+    return logits.contiguous(), lengths, table, model, image
+
+
 def beam_decode(logits, beam_width=16, top_k=16, blank=0, lengths=None, min_logp=None):
     """(T, B, V) f32 logits on the GPU -> (ids (B, beam_width, T) int32 padded with blank, lengths (B, beam_width) int32,
     scores (B, beam_width) f32): the N-best labellings of a CTC prefix beam search, best first, each with its log-probability
@@ -58,9 +80,8 @@ def beam_decode(logits, beam_width=16, top_k=16, blank=0, lengths=None, min_logp
     ``greedy_decode``.  The search runs over token ids: with the Gram-CTC inventory two token sequences that spell the same
     string (a bigram token and its two unigrams) stay two hypotheses here; ``gram_beam_decode`` is the search that merges them.
     The reference has no beam decoder; this extends its greedy call sites (run/ctc/cnn/dev.py:102, run/ctc/cnn/test.py:102)."""
-    if lengths is not None:
-        lengths = lengths.to(logits.device, torch.int32).contiguous()
-    return _ops.ctc_beam_search(logits.contiguous(), lengths, blank, beam_width, top_k, min_logp)
+    x, lengths, _, _, _ = _prepared(logits, blank, lengths)
+    return _ops.ctc_beam_search(x, lengths, blank, beam_width, top_k, min_logp)
 
 
 def beam_decode_lm(logits, lm, lm_weight, length_bonus, beam_width=16, top_k=16, blank=0, lengths=None, min_logp=None,
@@ -70,11 +91,8 @@ def beam_decode_lm(logits, lm, lm_weight, length_bonus, beam_width=16, top_k=16,
     on first use); its `bos` starts every context and, with `use_eos`, its `eos` closes every hypothesis after the last frame.
     -> (ids, lengths, scores (the combined score), ctc_scores, lm_scores), the last three (B, beam_width) f32, so that a caller
     can re-weight the N-best without decoding again.  Unused slots: length 0, scores and ctc_scores -inf, lm_scores 0."""
-    if lengths is not None:
-        lengths = lengths.to(logits.device, torch.int32).contiguous()
-    lm = lm.to(logits.device)
-    return _ops.ctc_beam_search_lm(logits.contiguous(), lengths, blank, beam_width, top_k, lm.image, lm_weight, length_bonus,
-                                   lm.bos_id, lm.eos_id if use_eos else -1, min_logp)
+    x, lengths, _, model, _ = _prepared(logits, blank, lengths, None, lm, lm_weight, length_bonus, use_eos)
+    return _ops.ctc_beam_search_lm(x, lengths, blank, beam_width, top_k, *model, min_logp)
 
 
 def beam_decode_biased(logits, graph, lm=None, lm_weight=0.0, length_bonus=0.0, beam_width=16, top_k=16, blank=0, lengths=None,
@@ -88,18 +106,8 @@ def beam_decode_biased(logits, graph, lm=None, lm_weight=0.0, length_bonus=0.0, 
     -> (ids, lengths, scores (the combined score), ctc_scores, lm_scores, bias_scores), the last four (B, beam_width) f32.
     Unused slots: length 0, scores and ctc_scores -inf, lm_scores and bias_scores 0.  Without `lm`, lm_scores is all 0 and
     `lm_weight`, `length_bonus` and `use_eos` have no effect."""
-    if graph.V != logits.shape[2] or graph.blank != blank:
-        raise ValueError("the context graph was built for %d ids with blank %d, the logits have %d with blank %d"
-                         % (graph.V, graph.blank, logits.shape[2], blank))
-    if lengths is not None:
-        lengths = lengths.to(logits.device, torch.int32).contiguous()
-    graph = graph.to(logits.device)
-    if lm is None:
-        return _ops.ctc_beam_search_bias(logits.contiguous(), lengths, blank, beam_width, top_k, graph.image, None, 0.0, 0.0, -1, -1,
-                                         min_logp)
-    lm = lm.to(logits.device)
-    return _ops.ctc_beam_search_bias(logits.contiguous(), lengths, blank, beam_width, top_k, graph.image, lm.image, lm_weight,
-                                     length_bonus, lm.bos_id, lm.eos_id if use_eos else -1, min_logp)
+    x, lengths, _, model, image = _prepared(logits, blank, lengths, None, lm, lm_weight, length_bonus, use_eos, graph)
+    return _ops.ctc_beam_search_bias(x, lengths, blank, beam_width, top_k, image, *model, min_logp)
 
 
 class _Stream:
@@ -107,7 +115,12 @@ class _Stream:
     host, `frames` on the device), the argument checks of ``reset`` and ``advance``, and ``commit``, which lets a stream run
     for any number of frames."""
 
-    _GRAM = False                                 # the Gram-CTC stream: two table nodes (characters) per frame and beam slot
+    # what a family is, for the methods below: its functions in _ops (``_OPS`` + "reset" ...), whether it is the Gram-CTC stream
+    # (the table `gram` goes to advance, and a frame gives two tokens, i.e. table nodes per beam slot, not one), and where the
+    # model's <s> goes: to reset, or to advance and result
+    _OPS = "ctc_beam_stream_"
+    _GRAM = False
+    _BOS_AT_RESET = True
 
     def __init__(self, B, V, max_frames, beam_width, top_k, blank, min_logp, lm, lm_weight, length_bonus, device):
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -120,9 +133,48 @@ class _Stream:
         self.committed = [[] for _ in range(self.B)]          # per utterance: the tokens ``commit`` has made final
         self.frames_base = torch.zeros((self.B,), dtype=torch.int32, device=self.device)   # frames - the table rows in use
 
-    def _new_state(self, nbytes):
+    def _new_state(self, graph):
+        self.graph = None if graph is None else graph.to(self.device)
+        nbytes = self._op("state_bytes")(self.B, self.beam_width, self.max_frames, self.lm is not None, graph is not None)
         self.state = torch.zeros(max(nbytes, 1), dtype=torch.uint8, device=self.device)
         self.reset()
+
+    def _op(self, verb):
+        return getattr(_ops, self._OPS + verb)
+
+    def _bos(self, at_reset):
+        """the model's <s> as one positional argument of the calls that take it, none of the others"""
+        return (-1 if self.lm is None else self.lm.bos_id,) if at_reset == self._BOS_AT_RESET else ()
+
+    def _images(self):
+        return (None if self.lm is None else self.lm.image), (None if self.graph is None else self.graph.image)
+
+    def reset(self, mask=None):
+        """start every utterance over, or those with mask[b] != 0 (`mask`: (B) integers, host or device)"""
+        self._op("reset")(self.state, self.B, self.beam_width, self.max_frames, self.lm is not None, self.graph is not None,
+                          *self._bos(True), self._reset_mask(mask))
+
+    def advance(self, logits, lengths=None):
+        """consume a chunk (Tc, B, V) of f32 logits; `lengths` (B): the valid frames of this chunk per utterance (0: the
+        utterance is left as it is; frames past the length are never read), None: all Tc"""
+        chunk = self._chunk(logits, lengths)
+        if chunk is None:
+            return
+        self._op("advance")(self.state, chunk[0], chunk[1], self.blank, self.beam_width, self.top_k,
+                            *((self.gram,) if self._GRAM else ()), self.fed, self.max_frames, *self._images(), self.lm_weight,
+                            self.length_bonus, *self._bos(False), self.min_logp)
+        self.fed += chunk[0].shape[0]
+
+    def result(self, use_eos=True):
+        """the N-best of the frames fed so far: the tuple of the one-shot function without a model or a graph (3), with `lm` (5)
+        or with `graph` (6), with ids of shape (B, beam_width, tokens the frames fed can give: one per frame, Gram-CTC two); the
+        search goes on unchanged.  Sets ``frames`` (B) int32 on the device: the frames every utterance has consumed."""
+        width = (2 if self._GRAM else 1) * self.fed
+        eos = self.lm.eos_id if self.lm is not None and use_eos else -1
+        out, rows = self._op("result")(self.state, self.B, self.beam_width, self.max_frames, self.blank, max(width, 1),
+                                       *self._images(), self.lm_weight, self.length_bonus, *self._bos(False), eos)
+        self._set_frames(rows)
+        return (out[0][:, :, :width],) + out[1:]
 
     def _reset_mask(self, mask):
         """`mask` of ``reset`` as a (B) int32 device tensor; None (a full reset) also starts the frame count over.  Once tokens
@@ -259,38 +311,8 @@ class BeamStream(_Stream):
             raise ValueError("the context graph was built for %d ids with blank %d, the stream has %d with blank %d"
                              % (graph.V, graph.blank, V, blank))
         super().__init__(B, V, max_frames, beam_width, top_k, blank, min_logp, lm, lm_weight, length_bonus, device)
-        self.graph = None if graph is None else graph.to(self.device)
-        self._new_state(_ops.ctc_beam_stream_state_bytes(B, beam_width, max_frames, lm is not None, graph is not None))
+        self._new_state(graph)
 
-    def _images(self):
-        return (None if self.lm is None else self.lm.image), (None if self.graph is None else self.graph.image)
-
-    def reset(self, mask=None):
-        """start every utterance over, or those with mask[b] != 0 (`mask`: (B) integers, host or device)"""
-        _ops.ctc_beam_stream_reset(self.state, self.B, self.beam_width, self.max_frames, self.lm is not None, self.graph is not None,
-                                   -1 if self.lm is None else self.lm.bos_id, self._reset_mask(mask))
-
-    def advance(self, logits, lengths=None):
-        """consume a chunk (Tc, B, V) of f32 logits; `lengths` (B): the valid frames of this chunk per utterance (0: the
-        utterance is left as it is; frames past the length are never read), None: all Tc"""
-        chunk = self._chunk(logits, lengths)
-        if chunk is None:
-            return
-        image, graph = self._images()
-        _ops.ctc_beam_stream_advance(self.state, chunk[0], chunk[1], self.blank, self.beam_width, self.top_k, self.fed,
-                                     self.max_frames, image, graph, self.lm_weight, self.length_bonus, self.min_logp)
-        self.fed += chunk[0].shape[0]
-
-    def result(self, use_eos=True):
-        """the N-best of the frames fed so far: the tuple of ``beam_decode`` (3), ``beam_decode_lm`` (5) or ``beam_decode_biased``
-        (6) with ids of shape (B, beam_width, frames fed); the search goes on unchanged.  Sets ``frames`` (B) int32 on the
-        device: the frames every utterance has consumed."""
-        image, graph = self._images()
-        eos = self.lm.eos_id if self.lm is not None and use_eos else -1
-        out, rows = _ops.ctc_beam_stream_result(self.state, self.B, self.beam_width, self.max_frames, self.blank,
-                                                max(self.fed, 1), image, graph, self.lm_weight, self.length_bonus, eos)
-        self._set_frames(rows)
-        return (out[0][:, :, :self.fed],) + out[1:]
 
 
 def check_gram_table(gram, V, blank=0):
@@ -329,10 +351,8 @@ def gram_beam_decode(logits, gram, beam_width=16, top_k=16, blank=0, lengths=Non
     ``compute_sequence_error(ids[:, k], lengths[:, k], t_batch, blank, None, None)`` with no retokenisation on the host.
     Candidates, `lengths` and `min_logp` as in ``beam_decode``.  ``gram_ctc_align`` on a decoded string gives its best cut.
     ``gram_beam_decode_lm`` is this search with a character n-gram language model in the ranking."""
-    table = _gram_table(gram, logits.shape[2], blank, logits.device)
-    if lengths is not None:
-        lengths = lengths.to(logits.device, torch.int32).contiguous()
-    return _ops.gram_ctc_beam_search(logits.contiguous(), lengths, blank, beam_width, top_k, table, min_logp)
+    x, lengths, table, _, _ = _prepared(logits, blank, lengths, gram)
+    return _ops.gram_ctc_beam_search(x, lengths, blank, beam_width, top_k, table, min_logp)
 
 
 def gram_beam_decode_lm(logits, gram, lm, lm_weight, length_bonus, beam_width=16, top_k=16, blank=0, lengths=None, min_logp=None,
@@ -346,14 +366,8 @@ def gram_beam_decode_lm(logits, gram, lm, lm_weight, length_bonus, beam_width=16
     the last frame.  A bigram token adds the steps of its two characters, so log p_lm(s) does not depend on how s was cut.
     -> (ids (B, beam_width, 2T), lengths, scores (the combined score), ctc_scores, lm_scores), the last three (B, beam_width)
     f32.  Unused slots: length 0, scores and ctc_scores -inf, lm_scores 0."""
-    table = _gram_table(gram, logits.shape[2], blank, logits.device)
-    if lm.vlm < logits.shape[2]:
-        raise ValueError("the language model covers %d ids, fewer than the %d of the logits" % (lm.vlm, logits.shape[2]))
-    if lengths is not None:
-        lengths = lengths.to(logits.device, torch.int32).contiguous()
-    lm = lm.to(logits.device)
-    return _ops.gram_ctc_beam_search_lm(logits.contiguous(), lengths, blank, beam_width, top_k, table, lm.image, lm_weight,
-                                        length_bonus, lm.bos_id, lm.eos_id if use_eos else -1, min_logp)
+    x, lengths, table, model, _ = _prepared(logits, blank, lengths, gram, lm, lm_weight, length_bonus, use_eos)
+    return _ops.gram_ctc_beam_search_lm(x, lengths, blank, beam_width, top_k, table, *model, min_logp)
 
 
 def gram_beam_decode_biased(logits, gram, graph, lm=None, lm_weight=0.0, length_bonus=0.0, beam_width=16, top_k=16, blank=0,
@@ -370,21 +384,8 @@ def gram_beam_decode_biased(logits, gram, graph, lm=None, lm_weight=0.0, length_
     (B, beam_width) f32; ids, lengths and the score to rank by go into ``mbr_decode`` unchanged.  Unused slots: length 0, scores and ctc_scores
     -inf, lm_scores and bias_scores 0.  Without `lm`, lm_scores is all 0 and `lm_weight`, `length_bonus` and `use_eos` have no
     effect."""
-    if graph.V != logits.shape[2] or graph.blank != blank:
-        raise ValueError("the context graph was built for %d ids with blank %d, the logits have %d with blank %d"
-                         % (graph.V, graph.blank, logits.shape[2], blank))
-    table = _gram_table(gram, logits.shape[2], blank, logits.device)
-    if lm is not None and lm.vlm < logits.shape[2]:
-        raise ValueError("the language model covers %d ids, fewer than the %d of the logits" % (lm.vlm, logits.shape[2]))
-    if lengths is not None:
-        lengths = lengths.to(logits.device, torch.int32).contiguous()
-    graph = graph.to(logits.device)
-    if lm is None:
-        return _ops.gram_ctc_beam_search_bias(logits.contiguous(), lengths, blank, beam_width, top_k, table, graph.image, None, 0.0,
-                                              0.0, -1, -1, min_logp)
-    lm = lm.to(logits.device)
-    return _ops.gram_ctc_beam_search_bias(logits.contiguous(), lengths, blank, beam_width, top_k, table, graph.image, lm.image,
-                                          lm_weight, length_bonus, lm.bos_id, lm.eos_id if use_eos else -1, min_logp)
+    x, lengths, table, model, image = _prepared(logits, blank, lengths, gram, lm, lm_weight, length_bonus, use_eos, graph)
+    return _ops.gram_ctc_beam_search_bias(x, lengths, blank, beam_width, top_k, table, image, *model, min_logp)
 
 
 class GramBeamStream(_Stream):
@@ -403,7 +404,10 @@ class GramBeamStream(_Stream):
     the prefix table holds two characters per frame.  Nothing here synchronises with the host, except ``commit``, which works
     as in ``BeamStream`` with characters for tokens."""
 
+    # the entries with a graph argument are the family: without a graph they are the narrow ones, size for size and byte for byte
+    _OPS = "gram_ctc_beam_bias_stream_"
     _GRAM = True
+    _BOS_AT_RESET = False
 
     def __init__(self, B, V, max_frames, gram, beam_width=16, top_k=16, blank=0, min_logp=None, lm=None, lm_weight=0.0,
                  length_bonus=0.0, device=None, graph=None):
@@ -416,58 +420,7 @@ class GramBeamStream(_Stream):
                              % (graph.V, graph.blank, V, blank))
         super().__init__(B, V, max_frames, beam_width, top_k, blank, min_logp, lm, lm_weight, length_bonus, device)
         self.gram = _gram_table(gram, self.V, self.blank, self.device)
-        self.graph = None if graph is None else graph.to(self.device)
-        if graph is None:
-            self._new_state(_ops.gram_ctc_beam_stream_state_bytes(B, beam_width, max_frames, lm is not None))
-        else:
-            self._new_state(_ops.gram_ctc_beam_bias_stream_state_bytes(B, beam_width, max_frames, lm is not None, True))
-
-    def reset(self, mask=None):
-        """start every utterance over, or those with mask[b] != 0 (`mask`: (B) integers, host or device)"""
-        if self.graph is not None:
-            _ops.gram_ctc_beam_bias_stream_reset(self.state, self.B, self.beam_width, self.max_frames, self.lm is not None, True,
-                                                 self._reset_mask(mask))
-            return
-        _ops.gram_ctc_beam_stream_reset(self.state, self.B, self.beam_width, self.max_frames, self.lm is not None,
-                                        self._reset_mask(mask))
-
-    def advance(self, logits, lengths=None):
-        """consume a chunk (Tc, B, V) of f32 logits; `lengths` (B): the valid frames of this chunk per utterance (0: the
-        utterance is left as it is; frames past the length are never read), None: all Tc"""
-        chunk = self._chunk(logits, lengths)
-        if chunk is None:
-            return
-        if self.graph is not None:
-            _ops.gram_ctc_beam_bias_stream_advance(self.state, chunk[0], chunk[1], self.blank, self.beam_width, self.top_k, self.gram,
-                                                   self.fed, self.max_frames, None if self.lm is None else self.lm.image,
-                                                   self.graph.image, self.lm_weight, self.length_bonus,
-                                                   -1 if self.lm is None else self.lm.bos_id, self.min_logp)
-            self.fed += chunk[0].shape[0]
-            return
-        _ops.gram_ctc_beam_stream_advance(self.state, chunk[0], chunk[1], self.blank, self.beam_width, self.top_k, self.gram,
-                                          self.fed, self.max_frames, None if self.lm is None else self.lm.image, self.lm_weight,
-                                          self.length_bonus, -1 if self.lm is None else self.lm.bos_id, self.min_logp)
-        self.fed += chunk[0].shape[0]
-
-    def result(self, use_eos=True):
-        """the N-best strings of the frames fed so far: the tuple of ``gram_beam_decode`` (3), ``gram_beam_decode_lm`` (5) or
-        ``gram_beam_decode_biased`` (6) with ids of shape (B, beam_width, 2 x frames fed); the search goes on unchanged.  Sets
-        ``frames`` (B) int32 on the device: the frames every utterance has consumed."""
-        eos = self.lm.eos_id if self.lm is not None and use_eos else -1
-        if self.graph is not None:
-            out, rows = _ops.gram_ctc_beam_bias_stream_result(self.state, self.B, self.beam_width, self.max_frames, self.blank,
-                                                              max(2 * self.fed, 1),
-                                                              None if self.lm is None else self.lm.image, self.graph.image,
-                                                              self.lm_weight, self.length_bonus,
-                                                              -1 if self.lm is None else self.lm.bos_id, eos)
-            self._set_frames(rows)
-            return (out[0][:, :, :2 * self.fed],) + out[1:]
-        out, rows = _ops.gram_ctc_beam_stream_result(self.state, self.B, self.beam_width, self.max_frames, self.blank,
-                                                     max(2 * self.fed, 1), None if self.lm is None else self.lm.image,
-                                                     self.lm_weight, self.length_bonus,
-                                                     -1 if self.lm is None else self.lm.bos_id, eos)
-        self._set_frames(rows)
-        return (out[0][:, :, :2 * self.fed],) + out[1:]
+        self._new_state(graph)
 
 
 def _retokenised(pred, pred_len, BLANK, vocab_token_to_id, vocab_id_to_token):

@@ -885,63 +885,8 @@ __global__ __launch_bounds__(THREADS) void beam_kernel(const float* __restrict__
     }
 }
 
-// ---------------------------------------------------------------------------------------------- what the entries share
-// The one-shot entries' common checks: BAD_ARG for a null pointer, a dimension or a blank out of range, else UNSUPPORTED beyond
-// the kernels' limits (`per_frame` prefix table nodes per frame and beam slot: 1, Gram-CTC 2), else OK.  An entry returns a
-// BAD_ARG at once, but an UNSUPPORTED only after its own argument checks and the model's and the graph's codes.
-static int oneshot_check(const float* logits, const void* workspace, const int32_t* out_ids, const int32_t* out_len,
-                         const float* out_score, int T, int B, int V, int blank, int beam_width, int top_k, int per_frame) {
-    if (!logits || !workspace || !out_ids || !out_len || !out_score || T <= 0 || B <= 0 || V <= 0 || blank < 0 || blank >= V ||
-        beam_width <= 0 || top_k <= 0)
-        return ASR_ERR_BAD_ARG;
-    if (beam_width > MAX_BEAM || top_k > MAX_TOPK || beam_width * top_k > MAX_EXT) return ASR_ERR_UNSUPPORTED;
-    if ((long long)per_frame * T * beam_width > 0x7fffffffLL) return ASR_ERR_UNSUPPORTED;    // prefix table node ids are int32
-    return ASR_OK;
-}
-
-// cand_kernel over the (T, B, V) logits into ws
-static int launch_cand(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank, int K,
-                       float min_logp, const Ws& ws) {
-    const long long rows = (long long)T * B;
-    hipLaunchKernelGGL(cand_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, lengths, T, B, V,
-                       blank, K, min_logp, ws);
-    ASR_LAUNCH_CHECK();
-    return ASR_OK;
-}
-
-}  // namespace beam
-}  // namespace asr
-
-using namespace asr;
-using namespace asr::beam;
-
-extern "C" size_t asr_ctc_beam_workspace_bytes(int T, int B, int V, int beam_width, int top_k) {
-    if (T <= 0 || B <= 0 || V <= 0 || beam_width <= 0 || top_k <= 0) return 0;
-    return ws_layout(T, B, beam_width, min(top_k, V - 1), nullptr, nullptr);
-}
-
-extern "C" int asr_ctc_beam_search(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank,
-                                   int beam_width, int top_k, float min_logp, void* workspace, size_t workspace_bytes,
-                                   int32_t* out_ids, int32_t* out_len, float* out_score) {
-    int rc = oneshot_check(logits, workspace, out_ids, out_len, out_score, T, B, V, blank, beam_width, top_k, 1);
-    if (rc != ASR_OK) return rc;
-    const int K = min(top_k, V - 1);
-    Ws ws;
-    const size_t need = ws_layout(T, B, beam_width, K, (char*)workspace, &ws);
-    if (workspace_bytes < need) return ASR_ERR_WORKSPACE;
-    rc = launch_cand(stream, logits, lengths, T, B, V, blank, K, min_logp, ws);
-    if (rc != ASR_OK) return rc;
-    hipLaunchKernelGGL((beam_kernel<false, false, ONESHOT>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V,
-                       beam_width, K, blank, ws, out_ids, out_len, out_score, Fuse<false>{}, Bias<false>{}, Strm<ONESHOT>{});
-    ASR_LAUNCH_CHECK();
-    return ASR_OK;
-}
-
-// ---------------------------------------------------------------------------------------------- language model entries
-namespace asr {
-namespace beam {
-
-// one workgroup per sequence; a thread scores the positions tid, tid + 256, ...; the sum is the threads' partial sums (each in
+// ---------------------------------------------------------------------------------------------- the small kernels
+// asr_ngram_score: one workgroup per sequence; a thread scores the positions tid, tid + 256, ...; the sum is the threads' partial sums (each in
 // position order) reduced by a fixed tree, so it repeats bitwise
 __global__ __launch_bounds__(THREADS) void ngram_score_kernel(ngram::Lm lm, const int32_t* __restrict__ ids,
                                                               const int32_t* __restrict__ lengths, int Lmax, int bos, int eos,
@@ -968,80 +913,7 @@ __global__ __launch_bounds__(THREADS) void ngram_score_kernel(ngram::Lm lm, cons
     if (tid == 0) out_sum[nseq] = part[0];
 }
 
-static int make_lm(const float* uni, int vlm, const int32_t* keys, const float* vals, int slots, int max_probe, int order,
-                   ngram::Lm* lm) {
-    if (!uni || vlm <= 0 || order < 1 || slots < 0) return ASR_ERR_BAD_ARG;
-    if (order > ngram::MAX_ORDER) return ASR_ERR_UNSUPPORTED;
-    if (slots > 0 && ((slots & (slots - 1)) != 0 || max_probe <= 0 || !keys || !vals)) return ASR_ERR_BAD_ARG;
-    lm->uni = (const float2*)uni;
-    lm->keys = slots > 0 ? (const int4*)keys : nullptr;
-    lm->vals = (const float2*)vals;
-    lm->mask = slots > 0 ? (unsigned)slots - 1u : 0u;
-    lm->max_probe = max_probe;
-    lm->order = order;
-    lm->vlm = vlm;
-    return ASR_OK;
-}
-
-// the search's side of the model arguments (fz->lm is make_lm's); a negative bos / eos means none
-static void fill_fuse(Fuse<true>* fz, int bos, int eos, float alpha, float beta, float* out_ctc, float* out_lm) {
-    fz->bos = bos < 0 ? -1 : bos;
-    fz->eos = eos < 0 ? -1 : eos;
-    fz->alpha = alpha;
-    fz->beta = beta;
-    fz->out_ctc = out_ctc;
-    fz->out_lm = out_lm;
-}
-
-}  // namespace beam
-}  // namespace asr
-
-extern "C" int asr_ngram_score(void* stream, const float* uni, int vlm, const int32_t* keys, const float* vals, int slots,
-                               int max_probe, int order, const int32_t* ids, const int32_t* lengths, int N, int Lmax, int bos,
-                               int eos, float* out_tok, float* out_sum) {
-    if (!ids || !out_tok || !out_sum || N <= 0 || Lmax <= 0 || bos >= vlm || eos >= vlm) return ASR_ERR_BAD_ARG;
-    ngram::Lm lm;
-    const int rc = make_lm(uni, vlm, keys, vals, slots, max_probe, order, &lm);
-    if (rc != ASR_OK) return rc;
-    hipLaunchKernelGGL(ngram_score_kernel, dim3(N), dim3(THREADS), 0, (hipStream_t)stream, lm, ids, lengths, Lmax, bos < 0 ? -1 : bos,
-                       eos < 0 ? -1 : eos, out_tok, out_sum);
-    ASR_LAUNCH_CHECK();
-    return ASR_OK;
-}
-
-extern "C" size_t asr_ctc_beam_lm_workspace_bytes(int T, int B, int V, int beam_width, int top_k) {
-    return asr_ctc_beam_workspace_bytes(T, B, V, beam_width, top_k);
-}
-
-extern "C" int asr_ctc_beam_search_lm(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank,
-                                      int beam_width, int top_k, float min_logp, const float* uni, int vlm, const int32_t* keys,
-                                      const float* vals, int slots, int max_probe, int order, int bos, int eos, float alpha,
-                                      float beta, void* workspace, size_t workspace_bytes, int32_t* out_ids, int32_t* out_len,
-                                      float* out_score, float* out_ctc, float* out_lm) {
-    const int lim = oneshot_check(logits, workspace, out_ids, out_len, out_score, T, B, V, blank, beam_width, top_k, 1);
-    if (lim == ASR_ERR_BAD_ARG || !out_ctc || !out_lm || vlm < V || bos >= vlm || eos >= vlm) return ASR_ERR_BAD_ARG;
-    Fuse<true> fz;
-    int rc = make_lm(uni, vlm, keys, vals, slots, max_probe, order, &fz.lm);
-    if (rc != ASR_OK) return rc;
-    if (lim != ASR_OK) return lim;
-    const int K = min(top_k, V - 1);
-    Ws ws;
-    const size_t need = ws_layout(T, B, beam_width, K, (char*)workspace, &ws);
-    if (workspace_bytes < need) return ASR_ERR_WORKSPACE;
-    fill_fuse(&fz, bos, eos, alpha, beta, out_ctc, out_lm);
-    rc = launch_cand(stream, logits, lengths, T, B, V, blank, K, min_logp, ws);
-    if (rc != ASR_OK) return rc;
-    hipLaunchKernelGGL((beam_kernel<true, false, ONESHOT>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V,
-                       beam_width, K, blank, ws, out_ids, out_len, out_score, fz, Bias<false>{}, Strm<ONESHOT>{});
-    ASR_LAUNCH_CHECK();
-    return ASR_OK;
-}
-
-// ---------------------------------------------------------------------------------------------- phrase biasing entries
-namespace asr {
-namespace beam {
-
-// one sequence per thread: a step's state comes from the step before it, so a sequence is walked in order; the sum is the
+// asr_ctx_score: one sequence per thread: a step's state comes from the step before it, so a sequence is walked in order; the sum is the
 // left-to-right f32 sum of the deltas
 __global__ __launch_bounds__(64) void ctx_score_kernel(ctx::Graph g, int V, const int32_t* __restrict__ ids,
                                                        const int32_t* __restrict__ lengths, int N, int Lmax, int finalize,
@@ -1070,86 +942,7 @@ __global__ __launch_bounds__(64) void ctx_score_kernel(ctx::Graph g, int V, cons
     out_sum[nseq] = acc;
 }
 
-static int make_graph(const int32_t* keys, const int32_t* vals, int slots, int max_probe, const float* ret, int n_states,
-                      ctx::Graph* g) {
-    if (!ret || n_states < 1 || slots < 0) return ASR_ERR_BAD_ARG;
-    if (slots > 0 && ((slots & (slots - 1)) != 0 || max_probe <= 0 || !keys || !vals)) return ASR_ERR_BAD_ARG;
-    g->keys = slots > 0 ? (const int2*)keys : nullptr;
-    g->vals = (const int2*)vals;
-    g->ret = ret;
-    g->mask = slots > 0 ? (unsigned)slots - 1u : 0u;
-    g->max_probe = max_probe;
-    g->n_states = n_states;
-    return ASR_OK;
-}
-
-}  // namespace beam
-}  // namespace asr
-
-extern "C" int asr_ctx_score(void* stream, const int32_t* g_keys, const int32_t* g_vals, int g_slots, int g_max_probe,
-                             const float* g_ret, int g_n_states, int V, const int32_t* ids, const int32_t* lengths, int N,
-                             int Lmax, int finalize, float* out_tok, float* out_sum) {
-    if (!ids || !out_tok || !out_sum || N <= 0 || Lmax <= 0 || V <= 0) return ASR_ERR_BAD_ARG;
-    ctx::Graph g;
-    const int rc = make_graph(g_keys, g_vals, g_slots, g_max_probe, g_ret, g_n_states, &g);
-    if (rc != ASR_OK) return rc;
-    hipLaunchKernelGGL(ctx_score_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, (hipStream_t)stream, g, V, ids, lengths, N,
-                       Lmax, finalize, out_tok, out_sum);
-    ASR_LAUNCH_CHECK();
-    return ASR_OK;
-}
-
-extern "C" size_t asr_ctc_beam_bias_workspace_bytes(int T, int B, int V, int beam_width, int top_k) {
-    return asr_ctc_beam_workspace_bytes(T, B, V, beam_width, top_k);
-}
-
-extern "C" int asr_ctc_beam_search_bias(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank,
-                                        int beam_width, int top_k, float min_logp, const float* uni, int vlm, const int32_t* keys,
-                                        const float* vals, int slots, int max_probe, int order, int bos, int eos, float alpha,
-                                        float beta, void* workspace, size_t workspace_bytes, int32_t* out_ids, int32_t* out_len,
-                                        float* out_score, float* out_ctc, float* out_lm, const int32_t* g_keys,
-                                        const int32_t* g_vals, int g_slots, int g_max_probe, const float* g_ret, int g_n_states,
-                                        float* out_bias) {
-    const int lim = oneshot_check(logits, workspace, out_ids, out_len, out_score, T, B, V, blank, beam_width, top_k, 1);
-    if (lim == ASR_ERR_BAD_ARG || !out_ctc || !out_lm || !out_bias) return ASR_ERR_BAD_ARG;
-    const bool with_lm = uni != nullptr;
-    Fuse<true> fz;
-    int rc;
-    if (with_lm) {
-        if (vlm < V || bos >= vlm || eos >= vlm) return ASR_ERR_BAD_ARG;
-        rc = make_lm(uni, vlm, keys, vals, slots, max_probe, order, &fz.lm);
-        if (rc != ASR_OK) return rc;
-    }
-    Bias<true> bz;
-    rc = make_graph(g_keys, g_vals, g_slots, g_max_probe, g_ret, g_n_states, &bz.g);
-    if (rc != ASR_OK) return rc;
-    if (lim != ASR_OK) return lim;
-    const int K = min(top_k, V - 1);
-    Ws ws;
-    const size_t need = ws_layout(T, B, beam_width, K, (char*)workspace, &ws);
-    if (workspace_bytes < need) return ASR_ERR_WORKSPACE;
-    bz.out_ctc = out_ctc;
-    bz.out_lm = out_lm;
-    bz.out_bias = out_bias;
-    rc = launch_cand(stream, logits, lengths, T, B, V, blank, K, min_logp, ws);
-    if (rc != ASR_OK) return rc;
-    if (with_lm) {
-        fill_fuse(&fz, bos, eos, alpha, beta, out_ctc, out_lm);
-        hipLaunchKernelGGL((beam_kernel<true, true, ONESHOT>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V,
-                           beam_width, K, blank, ws, out_ids, out_len, out_score, fz, bz, Strm<ONESHOT>{});
-    } else {
-        hipLaunchKernelGGL((beam_kernel<false, true, ONESHOT>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T, B, V,
-                           beam_width, K, blank, ws, out_ids, out_len, out_score, Fuse<false>{}, bz, Strm<ONESHOT>{});
-    }
-    ASR_LAUNCH_CHECK();
-    return ASR_OK;
-}
-
-// ---------------------------------------------------------------------------------------------- streaming entries
-namespace asr {
-namespace beam {
-
-// the header and the root beam (what beam_kernel<., ., ONESHOT> starts from) of every utterance, or of those with mask[b] != 0
+// asr_ctc_beam_stream_reset: the header and the root beam (what beam_kernel<., ., ONESHOT> starts from) of every utterance, or of those with mask[b] != 0
 __global__ __launch_bounds__(256) void stream_reset_kernel(State s, int B, int W, int F, int variant, int bos,
                                                            const int32_t* __restrict__ mask) {
     const int b = blockIdx.x * 256 + threadIdx.x;
@@ -1184,160 +977,12 @@ __global__ __launch_bounds__(256) void stream_reset_kernel(State s, int B, int W
     }
 }
 
-template <bool LM, bool BIAS, int MODE>
-static void launch_stream(hipStream_t st, const float* x, const int32_t* lengths, int T, int B, int V, int W, int K, int blank,
-                          const Ws& ws, int32_t* out_ids, int32_t* out_len, float* out_score, const Fuse<true>& fz,
-                          const Bias<true>& bz, const Strm<MODE>& sz) {
-    Fuse<LM> f;
-    Bias<BIAS> g;
-    if constexpr (LM) f = fz;
-    if constexpr (BIAS) g = bz;
-    hipLaunchKernelGGL((beam_kernel<LM, BIAS, MODE>), dim3(B), dim3(THREADS), 0, st, x, lengths, T, B, V, W, K, blank, ws, out_ids,
-                       out_len, out_score, f, g, sz);
-}
-
-template <int MODE>
-static void launch_stream_variant(int variant, hipStream_t st, const float* x, const int32_t* lengths, int T, int B, int V, int W,
-                                  int K, int blank, const Ws& ws, int32_t* out_ids, int32_t* out_len, float* out_score,
-                                  const Fuse<true>& fz, const Bias<true>& bz, const Strm<MODE>& sz) {
-    switch (variant) {
-        case 0: launch_stream<false, false, MODE>(st, x, lengths, T, B, V, W, K, blank, ws, out_ids, out_len, out_score, fz, bz, sz); break;
-        case 1: launch_stream<true, false, MODE>(st, x, lengths, T, B, V, W, K, blank, ws, out_ids, out_len, out_score, fz, bz, sz); break;
-        case 2: launch_stream<false, true, MODE>(st, x, lengths, T, B, V, W, K, blank, ws, out_ids, out_len, out_score, fz, bz, sz); break;
-        default: launch_stream<true, true, MODE>(st, x, lengths, T, B, V, W, K, blank, ws, out_ids, out_len, out_score, fz, bz, sz);
-    }
-}
-
-// the CTC stream's variant word (State's header, state_layout)
-static int ctc_variant(bool with_lm, bool with_bias) { return (with_lm ? 1 : 0) | (with_bias ? 2 : 0); }
-
-// The dimension and limit part of every streaming entry of both searches: BAD_ARG without a state (`has_state`) or for a
-// dimension that is not positive, else UNSUPPORTED beyond the kernels' limits (`per_frame` prefix table nodes per frame and beam
-// slot: 1, Gram-CTC 2), else OK.  As with oneshot_check, an UNSUPPORTED waits for the model's and the graph's codes.
-static int stream_dims(bool has_state, int B, int W, int F, int per_frame) {
-    if (!has_state || B <= 0 || W <= 0 || F <= 0) return ASR_ERR_BAD_ARG;
-    if (W > MAX_BEAM) return ASR_ERR_UNSUPPORTED;
-    if ((long long)per_frame * F * W > 0x7fffffffLL) return ASR_ERR_UNSUPPORTED;      // prefix table node ids are int32
-    return ASR_OK;
-}
-
-// the checks on dimensions, state size and the model / graph arguments that advance and result share; fills fz.lm, bz.g, sz->s
-static int stream_open(int B, int W, int F, const float* uni, int vlm, const int32_t* keys, const float* vals, int slots,
-                       int max_probe, int order, const int32_t* g_keys, const int32_t* g_vals, int g_slots, int g_max_probe,
-                       const float* g_ret, int g_n_states, void* state, size_t state_bytes, Fuse<true>* fz, Bias<true>* bz,
-                       StrmArgs* sz) {
-    const int lim = stream_dims(state != nullptr, B, W, F, 1);
-    if (lim == ASR_ERR_BAD_ARG) return lim;
-    const bool with_lm = uni != nullptr, with_bias = g_ret != nullptr;
-    if (with_lm) {
-        const int rc = make_lm(uni, vlm, keys, vals, slots, max_probe, order, &fz->lm);
-        if (rc != ASR_OK) return rc;
-    }
-    if (with_bias) {
-        const int rc = make_graph(g_keys, g_vals, g_slots, g_max_probe, g_ret, g_n_states, &bz->g);
-        if (rc != ASR_OK) return rc;
-    } else if (g_keys || g_vals || g_slots != 0 || g_n_states != 0) {
-        return ASR_ERR_BAD_ARG;                      // a graph without its ret: section 22's check, not "no graph"
-    }
-    if (lim != ASR_OK) return lim;
-    sz->max_frames = F;
-    sz->variant = ctc_variant(with_lm, with_bias);
-    sz->out_frames = nullptr;
-    if (state_bytes < state_layout(B, W, F, sz->variant, (char*)state, &sz->s)) return ASR_ERR_WORKSPACE;
-    return ASR_OK;
-}
-
-}  // namespace beam
-}  // namespace asr
-
-extern "C" size_t asr_ctc_beam_stream_state_bytes(int B, int beam_width, int max_frames, int with_lm, int with_bias) {
-    if (stream_dims(true, B, beam_width, max_frames, 1) == ASR_ERR_BAD_ARG) return 0;
-    return state_layout(B, beam_width, max_frames, ctc_variant(with_lm, with_bias), nullptr, nullptr);
-}
-
-extern "C" size_t asr_ctc_beam_stream_workspace_bytes(int Tc, int B, int V, int beam_width, int top_k) {
-    if (Tc <= 0 || B <= 0 || V <= 0 || beam_width <= 0 || top_k <= 0) return 0;
-    return ws_layout(Tc, B, 0, min(top_k, V - 1), nullptr, nullptr);          // the candidate rows; the prefix table is the state's
-}
-
-extern "C" int asr_ctc_beam_stream_reset(void* stream, void* state, size_t state_bytes, int B, int beam_width, int max_frames,
-                                         int with_lm, int with_bias, int bos, const int32_t* mask) {
-    const int rc = stream_dims(state != nullptr, B, beam_width, max_frames, 1);
-    if (rc != ASR_OK) return rc;
-    const int variant = ctc_variant(with_lm, with_bias);
-    State s;
-    if (state_bytes < state_layout(B, beam_width, max_frames, variant, (char*)state, &s)) return ASR_ERR_WORKSPACE;
-    hipLaunchKernelGGL(stream_reset_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, s, B, beam_width,
-                       max_frames, variant, bos < 0 ? -1 : bos, mask);
-    ASR_LAUNCH_CHECK();
-    return ASR_OK;
-}
-
-extern "C" int asr_ctc_beam_stream_advance(void* stream, const float* logits, const int32_t* lengths, int Tc, int B, int V,
-                                           int blank, int beam_width, int top_k, float min_logp, const float* uni, int vlm,
-                                           const int32_t* keys, const float* vals, int slots, int max_probe, int order,
-                                           const int32_t* g_keys, const int32_t* g_vals, int g_slots, int g_max_probe,
-                                           const float* g_ret, int g_n_states, float alpha, float beta, int frames_before,
-                                           int max_frames, void* state, size_t state_bytes, void* workspace,
-                                           size_t workspace_bytes) {
-    if (!logits || !workspace || Tc <= 0 || V <= 0 || blank < 0 || blank >= V || top_k <= 0 || frames_before < 0)
-        return ASR_ERR_BAD_ARG;
-    if (uni && vlm < V) return ASR_ERR_BAD_ARG;
-    Fuse<true> fz{};
-    Bias<true> bz{};
-    Strm<ADVANCE> sz{};
-    int rc = stream_open(B, beam_width, max_frames, uni, vlm, keys, vals, slots, max_probe, order, g_keys, g_vals, g_slots,
-                         g_max_probe, g_ret, g_n_states, state, state_bytes, &fz, &bz, &sz);
-    if (rc != ASR_OK) return rc;
-    if (top_k > MAX_TOPK || beam_width * top_k > MAX_EXT) return ASR_ERR_UNSUPPORTED;
-    if ((long long)frames_before + Tc > max_frames) return ASR_ERR_UNSUPPORTED;
-    const int K = min(top_k, V - 1);
-    Ws ws;
-    if (workspace_bytes < ws_layout(Tc, B, 0, K, (char*)workspace, &ws)) return ASR_ERR_WORKSPACE;
-    fill_fuse(&fz, -1, -1, alpha, beta, nullptr, nullptr);       // the contexts start in reset and end in result
-    rc = launch_cand(stream, logits, lengths, Tc, B, V, blank, K, min_logp, ws);
-    if (rc != ASR_OK) return rc;
-    launch_stream_variant<ADVANCE>(sz.variant, (hipStream_t)stream, logits, lengths, Tc, B, V, beam_width, K, blank, ws, nullptr,
-                                   nullptr, nullptr, fz, bz, sz);
-    ASR_LAUNCH_CHECK();
-    return ASR_OK;
-}
-
-extern "C" int asr_ctc_beam_stream_result(void* stream, const float* uni, int vlm, const int32_t* keys, const float* vals, int slots,
-                                          int max_probe, int order, const int32_t* g_keys, const int32_t* g_vals, int g_slots,
-                                          int g_max_probe, const float* g_ret, int g_n_states, float alpha, float beta, int eos,
-                                          int B, int beam_width, int max_frames, int blank, int Lcap, const void* state,
-                                          size_t state_bytes, int32_t* out_ids, int32_t* out_len, float* out_score, float* out_ctc,
-                                          float* out_lm, float* out_bias, int32_t* out_frames) {
-    if (!out_ids || !out_len || !out_score || !out_frames || Lcap <= 0 || blank < 0) return ASR_ERR_BAD_ARG;
-    if ((uni || g_ret) && (!out_ctc || !out_lm)) return ASR_ERR_BAD_ARG;
-    if (g_ret && !out_bias) return ASR_ERR_BAD_ARG;
-    if (uni && eos >= vlm) return ASR_ERR_BAD_ARG;
-    Fuse<true> fz{};
-    Bias<true> bz{};
-    Strm<RESULT> sz{};
-    const int rc = stream_open(B, beam_width, max_frames, uni, vlm, keys, vals, slots, max_probe, order, g_keys, g_vals, g_slots,
-                               g_max_probe, g_ret, g_n_states, const_cast<void*>(state), state_bytes, &fz, &bz, &sz);
-    if (rc != ASR_OK) return rc;
-    sz.out_frames = out_frames;
-    fill_fuse(&fz, -1, eos, alpha, beta, out_ctc, out_lm);
-    bz.out_ctc = out_ctc;
-    bz.out_lm = out_lm;
-    bz.out_bias = out_bias;
-    launch_stream_variant<RESULT>(sz.variant, (hipStream_t)stream, nullptr, nullptr, Lcap, B, 0, beam_width, 0, blank, Ws{}, out_ids,
-                                  out_len, out_score, fz, bz, sz);
-    ASR_LAUNCH_CHECK();
-    return ASR_OK;
-}
-
 // ------------------------------------------------------------------------------ Gram-CTC: beam search over spelled strings
 // asr_gram_ctc_beam_search.  The hypotheses are strings of unigrams; a string carries the mass of the paths
 // that end in blank (pb), in the unigram token of its last character (pu) and in the bigram token of its last two (pg), so every
 // way of cutting it into unigram and bigram tokens is summed.  cand_kernel is the one above; gram_rows_kernel spells its
 // candidates; gram_beam_kernel is beam_kernel's frame loop with three masses, a three-deep identity (the hashes and last
 // characters of s, s[:-1] and s[:-2]) and one more merge: two extensions of one frame that spell the same string.
-namespace asr {
-namespace beam {
 
 constexpr unsigned short NO_MATE = 0xffff;
 
@@ -2034,146 +1679,7 @@ __global__ __launch_bounds__(THREADS) void gram_beam_kernel(const float* __restr
     }
 }
 
-// the workspace of asr_ctc_beam_search with a prefix table of 2 * T * W nodes per utterance (a bigram extension adds two), then
-// the candidates' spellings (T * B, K) int2
-static size_t gram_ws_layout(int T, int B, int W, int K, char* base, Ws* ws, int2** cgr) {
-    size_t off = ws_layout(T, B, 2 * W, K, base, ws);
-    if (cgr) *cgr = (int2*)(base + off);
-    off += align256((size_t)T * B * K * 8);
-    return off;
-}
-
-// gram_rows_kernel over the candidate rows that launch_cand left in ws; nothing to spell where a row can have no candidate
-static int launch_gram_rows(void* stream, const int32_t* lengths, int T, int B, int K, const Ws& ws, const int32_t* gram, int2* cgr) {
-    if (K <= 0) return ASR_OK;
-    const long long rows = (long long)T * B;
-    hipLaunchKernelGGL(gram_rows_kernel, dim3((unsigned)((rows * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, lengths, T, B,
-                       K, ws, (const int2*)gram, cgr);
-    ASR_LAUNCH_CHECK();
-    return ASR_OK;
-}
-
-}  // namespace beam
-}  // namespace asr
-
-extern "C" size_t asr_gram_ctc_beam_workspace_bytes(int T, int B, int V, int beam_width, int top_k) {
-    if (T <= 0 || B <= 0 || V <= 0 || beam_width <= 0 || top_k <= 0) return 0;
-    return gram_ws_layout(T, B, beam_width, min(top_k, V - 1), nullptr, nullptr, nullptr);
-}
-
-extern "C" int asr_gram_ctc_beam_search(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank,
-                                        int beam_width, int top_k, float min_logp, const int32_t* gram, void* workspace,
-                                        size_t workspace_bytes, int32_t* out_ids, int32_t* out_len, float* out_score) {
-    int rc = oneshot_check(logits, workspace, out_ids, out_len, out_score, T, B, V, blank, beam_width, top_k, 2);
-    if (rc == ASR_OK && !gram) rc = ASR_ERR_UNSUPPORTED;
-    if (rc != ASR_OK) return rc;
-    const int K = min(top_k, V - 1);
-    Ws ws;
-    int2* cgr;
-    const size_t need = gram_ws_layout(T, B, beam_width, K, (char*)workspace, &ws, &cgr);
-    if (workspace_bytes < need) return ASR_ERR_WORKSPACE;
-    rc = launch_cand(stream, logits, lengths, T, B, V, blank, K, min_logp, ws);
-    if (rc != ASR_OK) return rc;
-    rc = launch_gram_rows(stream, lengths, T, B, K, ws, gram, cgr);
-    if (rc != ASR_OK) return rc;
-    hipLaunchKernelGGL((gram_beam_kernel<false, false, ONESHOT>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T,
-                       B, V, beam_width, K, blank, ws, (const int2*)cgr, out_ids, out_len, out_score, Fuse<false>{}, GStrm<ONESHOT>{},
-                       Bias<false>{}, GBiasStrm<false>{});
-    ASR_LAUNCH_CHECK();
-    return ASR_OK;
-}
-
-extern "C" size_t asr_gram_ctc_beam_lm_workspace_bytes(int T, int B, int V, int beam_width, int top_k) {
-    return asr_gram_ctc_beam_workspace_bytes(T, B, V, beam_width, top_k);
-}
-
-extern "C" int asr_gram_ctc_beam_search_lm(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank,
-                                           int beam_width, int top_k, float min_logp, const int32_t* gram, const float* uni, int vlm,
-                                           const int32_t* keys, const float* vals, int slots, int max_probe, int order, int bos,
-                                           int eos, float alpha, float beta, void* workspace, size_t workspace_bytes,
-                                           int32_t* out_ids, int32_t* out_len, float* out_score, float* out_ctc, float* out_lm) {
-    const int lim = oneshot_check(logits, workspace, out_ids, out_len, out_score, T, B, V, blank, beam_width, top_k, 2);
-    if (lim == ASR_ERR_BAD_ARG || !out_ctc || !out_lm || vlm < V || bos >= vlm || eos >= vlm) return ASR_ERR_BAD_ARG;
-    Fuse<true> fz;
-    int rc = make_lm(uni, vlm, keys, vals, slots, max_probe, order, &fz.lm);
-    if (rc != ASR_OK) return rc;
-    if (!gram) return ASR_ERR_UNSUPPORTED;
-    if (lim != ASR_OK) return lim;
-    const int K = min(top_k, V - 1);
-    Ws ws;
-    int2* cgr;
-    const size_t need = gram_ws_layout(T, B, beam_width, K, (char*)workspace, &ws, &cgr);
-    if (workspace_bytes < need) return ASR_ERR_WORKSPACE;
-    fill_fuse(&fz, bos, eos, alpha, beta, out_ctc, out_lm);
-    rc = launch_cand(stream, logits, lengths, T, B, V, blank, K, min_logp, ws);
-    if (rc != ASR_OK) return rc;
-    rc = launch_gram_rows(stream, lengths, T, B, K, ws, gram, cgr);
-    if (rc != ASR_OK) return rc;
-    hipLaunchKernelGGL((gram_beam_kernel<true, false, ONESHOT>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T,
-                       B, V, beam_width, K, blank, ws, (const int2*)cgr, out_ids, out_len, out_score, fz, GStrm<ONESHOT>{}, Bias<false>{},
-                       GBiasStrm<false>{});
-    ASR_LAUNCH_CHECK();
-    return ASR_OK;
-}
-
-// ------------------------------------------------------------------------------ Gram-CTC: phrase biasing
-extern "C" size_t asr_gram_ctc_beam_bias_workspace_bytes(int T, int B, int V, int beam_width, int top_k) {
-    return asr_gram_ctc_beam_workspace_bytes(T, B, V, beam_width, top_k);
-}
-
-extern "C" int asr_gram_ctc_beam_search_bias(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank,
-                                             int beam_width, int top_k, float min_logp, const int32_t* gram, const float* uni, int vlm,
-                                             const int32_t* keys, const float* vals, int slots, int max_probe, int order, int bos,
-                                             int eos, float alpha, float beta, void* workspace, size_t workspace_bytes,
-                                             int32_t* out_ids, int32_t* out_len, float* out_score, float* out_ctc, float* out_lm,
-                                             const int32_t* g_keys, const int32_t* g_vals, int g_slots, int g_max_probe,
-                                             const float* g_ret, int g_n_states, float* out_bias) {
-    const int lim = oneshot_check(logits, workspace, out_ids, out_len, out_score, T, B, V, blank, beam_width, top_k, 2);
-    if (lim == ASR_ERR_BAD_ARG || !out_ctc || !out_lm || !out_bias) return ASR_ERR_BAD_ARG;
-    const bool with_lm = uni != nullptr;
-    Fuse<true> fz;
-    int rc;
-    if (with_lm) {
-        if (vlm < V || bos >= vlm || eos >= vlm) return ASR_ERR_BAD_ARG;
-        rc = make_lm(uni, vlm, keys, vals, slots, max_probe, order, &fz.lm);
-        if (rc != ASR_OK) return rc;
-    }
-    Bias<true> bz;
-    rc = make_graph(g_keys, g_vals, g_slots, g_max_probe, g_ret, g_n_states, &bz.g);
-    if (rc != ASR_OK) return rc;
-    if (!gram) return ASR_ERR_UNSUPPORTED;
-    if (lim != ASR_OK) return lim;
-    const int K = min(top_k, V - 1);
-    Ws ws;
-    int2* cgr;
-    const size_t need = gram_ws_layout(T, B, beam_width, K, (char*)workspace, &ws, &cgr);
-    if (workspace_bytes < need) return ASR_ERR_WORKSPACE;
-    bz.out_ctc = out_ctc;
-    bz.out_lm = out_lm;
-    bz.out_bias = out_bias;
-    rc = launch_cand(stream, logits, lengths, T, B, V, blank, K, min_logp, ws);
-    if (rc != ASR_OK) return rc;
-    rc = launch_gram_rows(stream, lengths, T, B, K, ws, gram, cgr);
-    if (rc != ASR_OK) return rc;
-    if (with_lm) {
-        fill_fuse(&fz, bos, eos, alpha, beta, out_ctc, out_lm);
-        hipLaunchKernelGGL((gram_beam_kernel<true, true, ONESHOT>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T,
-                           B, V, beam_width, K, blank, ws, (const int2*)cgr, out_ids, out_len, out_score, fz, GStrm<ONESHOT>{}, bz,
-                           GBiasStrm<false>{});
-    } else {
-        hipLaunchKernelGGL((gram_beam_kernel<false, true, ONESHOT>), dim3(B), dim3(THREADS), 0, (hipStream_t)stream, logits, lengths, T,
-                           B, V, beam_width, K, blank, ws, (const int2*)cgr, out_ids, out_len, out_score, Fuse<false>{}, GStrm<ONESHOT>{},
-                           bz, GBiasStrm<false>{});
-    }
-    ASR_LAUNCH_CHECK();
-    return ASR_OK;
-}
-
-// ---------------------------------------------------------------------------------------------- Gram-CTC streaming entries
-namespace asr {
-namespace beam {
-
-// the header and the root beam (what gram_beam_kernel<., ONESHOT> starts from) of every utterance, or of those with mask[b] != 0
+// asr_gram_ctc_beam_bias_stream_reset: the header and the root beam (what gram_beam_kernel<., ONESHOT> starts from) of every utterance, or of those with mask[b] != 0
 __global__ __launch_bounds__(256) void gram_stream_reset_kernel(GState s, int B, int W, int F, int variant,
                                                                 const int32_t* __restrict__ mask, GBiasState bs) {
     const int b = blockIdx.x * 256 + threadIdx.x;
@@ -2203,98 +1709,548 @@ __global__ __launch_bounds__(256) void gram_stream_reset_kernel(GState s, int B,
     }
 }
 
-template <bool LM, bool BIAS, int MODE>
-static void launch_gram(hipStream_t st, const float* x, const int32_t* lengths, int T, int B, int V, int W, int K, int blank,
-                        const Ws& ws, const int2* cgr, int32_t* out_ids, int32_t* out_len, float* out_score, const Fuse<true>& fz,
-                        const Bias<true>& bz, const GStrm<MODE>& sz, const GBiasState& bs) {
-    Fuse<LM> f;
-    Bias<BIAS> g;
-    GBiasStrm<BIAS && MODE != ONESHOT> gs;
-    if constexpr (LM) f = fz;
-    if constexpr (BIAS) g = bz;
-    if constexpr (BIAS && MODE != ONESHOT) static_cast<GBiasState&>(gs) = bs;
-    hipLaunchKernelGGL((gram_beam_kernel<LM, BIAS, MODE>), dim3(B), dim3(THREADS), 0, st, x, lengths, T, B, V, W, K, blank, ws, cgr,
-                       out_ids, out_len, out_score, f, sz, g, gs);
+// ================================================================================================= the searches' host side
+// All host code of the searches: the argument packs, the checks, one driver per entry family over the search
+// family (Ctc / Gram), one dispatch from the variant to the kernel, and then the extern "C" entries, each of which packs its
+// arguments and forwards.  Return codes are behaviour, down to which one wins when two apply; the order is stated where a driver
+// runs its checks, and where the two families or two entries of one family differ, the difference is a parameter or a comment there.
+
+// the language model and the phrase graph as the entries get them; filled once at the extern "C" boundary and passed by value
+struct LmArgs {
+    const float* uni;
+    int vlm;
+    const int32_t* keys;
+    const float* vals;
+    int slots, max_probe, order;
+};
+
+struct GraphArgs {
+    const int32_t* keys;
+    const int32_t* vals;
+    int slots, max_probe;
+    const float* ret;
+    int n_states;
+};
+
+// what a search returns; ctc and lm with a model or a graph, bias with a graph, and all null in advance
+struct Outs {
+    int32_t* ids;
+    int32_t* len;
+    float* score;
+    float* ctc;
+    float* lm;
+    float* bias;
+};
+
+static int make_lm(LmArgs a, ngram::Lm* lm) {
+    if (!a.uni || a.vlm <= 0 || a.order < 1 || a.slots < 0) return ASR_ERR_BAD_ARG;
+    if (a.order > ngram::MAX_ORDER) return ASR_ERR_UNSUPPORTED;
+    if (a.slots > 0 && ((a.slots & (a.slots - 1)) != 0 || a.max_probe <= 0 || !a.keys || !a.vals)) return ASR_ERR_BAD_ARG;
+    lm->uni = (const float2*)a.uni;
+    lm->keys = a.slots > 0 ? (const int4*)a.keys : nullptr;
+    lm->vals = (const float2*)a.vals;
+    lm->mask = a.slots > 0 ? (unsigned)a.slots - 1u : 0u;
+    lm->max_probe = a.max_probe;
+    lm->order = a.order;
+    lm->vlm = a.vlm;
+    return ASR_OK;
 }
 
-template <int MODE>
-static void launch_gram_stream(hipStream_t st, const float* x, const int32_t* lengths, int T, int B, int V, int W, int K, int blank,
-                               const Ws& ws, const int2* cgr, int32_t* out_ids, int32_t* out_len, float* out_score,
-                               const Fuse<true>& fz, const Bias<true>& bz, const GStrm<MODE>& sz, const GBiasState& bs) {
-    switch (sz.variant & 3) {
-        case 0: launch_gram<false, false, MODE>(st, x, lengths, T, B, V, W, K, blank, ws, cgr, out_ids, out_len, out_score, fz, bz, sz, bs); break;
-        case 1: launch_gram<true, false, MODE>(st, x, lengths, T, B, V, W, K, blank, ws, cgr, out_ids, out_len, out_score, fz, bz, sz, bs); break;
-        case 2: launch_gram<false, true, MODE>(st, x, lengths, T, B, V, W, K, blank, ws, cgr, out_ids, out_len, out_score, fz, bz, sz, bs); break;
-        default: launch_gram<true, true, MODE>(st, x, lengths, T, B, V, W, K, blank, ws, cgr, out_ids, out_len, out_score, fz, bz, sz, bs);
+static int make_graph(GraphArgs a, ctx::Graph* g) {
+    if (!a.ret || a.n_states < 1 || a.slots < 0) return ASR_ERR_BAD_ARG;
+    if (a.slots > 0 && ((a.slots & (a.slots - 1)) != 0 || a.max_probe <= 0 || !a.keys || !a.vals)) return ASR_ERR_BAD_ARG;
+    g->keys = a.slots > 0 ? (const int2*)a.keys : nullptr;
+    g->vals = (const int2*)a.vals;
+    g->ret = a.ret;
+    g->mask = a.slots > 0 ? (unsigned)a.slots - 1u : 0u;
+    g->max_probe = a.max_probe;
+    g->n_states = a.n_states;
+    return ASR_OK;
+}
+
+// The one-shot entries' common checks: BAD_ARG for a null pointer, a dimension or a blank out of range, else UNSUPPORTED beyond
+// the kernels' limits (`per_frame` prefix table nodes per frame and beam slot), else OK.  The driver returns a BAD_ARG at once,
+// but an UNSUPPORTED only after its own argument checks and the model's and the graph's codes.
+static int oneshot_check(const float* logits, const void* workspace, const Outs& out, int T, int B, int V, int blank, int beam_width,
+                         int top_k, int per_frame) {
+    if (!logits || !workspace || !out.ids || !out.len || !out.score || T <= 0 || B <= 0 || V <= 0 || blank < 0 || blank >= V ||
+        beam_width <= 0 || top_k <= 0)
+        return ASR_ERR_BAD_ARG;
+    if (beam_width > MAX_BEAM || top_k > MAX_TOPK || beam_width * top_k > MAX_EXT) return ASR_ERR_UNSUPPORTED;
+    if ((long long)per_frame * T * beam_width > 0x7fffffffLL) return ASR_ERR_UNSUPPORTED;    // prefix table node ids are int32
+    return ASR_OK;
+}
+
+// The dimension and limit part of every streaming entry of both searches: BAD_ARG without a state (`has_state`) or for a
+// dimension that is not positive, else UNSUPPORTED beyond the kernels' limits, else OK.  As with oneshot_check, an UNSUPPORTED
+// waits for the model's and the graph's codes.
+static int stream_dims(bool has_state, int B, int W, int F, int per_frame) {
+    if (!has_state || B <= 0 || W <= 0 || F <= 0) return ASR_ERR_BAD_ARG;
+    if (W > MAX_BEAM) return ASR_ERR_UNSUPPORTED;
+    if ((long long)per_frame * F * W > 0x7fffffffLL) return ASR_ERR_UNSUPPORTED;      // prefix table node ids are int32
+    return ASR_OK;
+}
+
+// the workspace of asr_ctc_beam_search with a prefix table of 2 * T * W nodes per utterance (a bigram extension adds two), then
+// the candidates' spellings (T * B, K) int2
+static size_t gram_ws_layout(int T, int B, int W, int K, char* base, Ws* ws, int2** cgr) {
+    size_t off = ws_layout(T, B, 2 * W, K, base, ws);
+    if (cgr) *cgr = (int2*)(base + off);
+    off += align256((size_t)T * B * K * 8);
+    return off;
+}
+
+// the streams' variant words (the states' headers and layouts)
+static int ctc_variant(bool with_lm, bool with_bias) { return (with_lm ? 1 : 0) | (with_bias ? 2 : 0); }
+static int gram_variant(bool with_lm, bool with_bias) { return GRAM_VARIANT | ctc_variant(with_lm, with_bias); }
+
+// The two search families as the drivers see them: prefix table nodes per frame and beam slot, the variant word, and the
+// workspace and state layouts (sz and bs may be null for the size alone).  Ctc has no spellings (*cgr = null) and keeps its
+// graph fields inside State (bs untouched).
+struct Ctc {
+    static constexpr bool GRAM = false;
+    static constexpr int PER_FRAME = 1;
+    using Args = StrmArgs;
+    static int variant(bool with_lm, bool with_bias) { return ctc_variant(with_lm, with_bias); }
+    static size_t ws(int T, int B, int W, int K, char* base, Ws* ws, int2** cgr) {
+        if (cgr) *cgr = nullptr;
+        return ws_layout(T, B, W, K, base, ws);
+    }
+    static size_t state(int B, int W, int F, int variant, char* base, Args* sz, GBiasState*) {
+        return state_layout(B, W, F, variant, base, sz ? &sz->s : nullptr);
+    }
+};
+
+struct Gram {
+    static constexpr bool GRAM = true;
+    static constexpr int PER_FRAME = 2;
+    using Args = GStrmArgs;
+    static int variant(bool with_lm, bool with_bias) { return gram_variant(with_lm, with_bias); }
+    static size_t ws(int T, int B, int W, int K, char* base, Ws* ws, int2** cgr) { return gram_ws_layout(T, B, W, K, base, ws, cgr); }
+    static size_t state(int B, int W, int F, int variant, char* base, Args* sz, GBiasState* bs) {
+        return gram_state_layout(B, W, F, variant, base, sz ? &sz->s : nullptr, bs);
+    }
+};
+
+// everything a beam kernel of either family is launched with, in the widest form; launch_beam_as narrows it to the instantiation
+template <class Fam>
+struct Launch {
+    hipStream_t st;
+    const float* x;
+    const int32_t* lengths;
+    int T, B, V, W, K, blank;
+    Ws ws;
+    int2* cgr;                                       // Gram-CTC: the candidates' spellings
+    Outs out;
+    Fuse<true> fz;
+    Bias<true> bz;
+    typename Fam::Args sz;                           // unused in ONESHOT
+    GBiasState bs;                                   // Gram-CTC streams with a graph
+};
+
+// the search's side of the model arguments (a.fz.lm is make_lm's; a negative bos / eos means none) and the outputs' places
+template <class Fam>
+static void fill_fuse(Launch<Fam>* a, int bos, int eos, float alpha, float beta, const Outs& out) {
+    a->out = out;
+    a->fz.bos = bos < 0 ? -1 : bos;
+    a->fz.eos = eos < 0 ? -1 : eos;
+    a->fz.alpha = alpha;
+    a->fz.beta = beta;
+    a->fz.out_ctc = a->bz.out_ctc = out.ctc;
+    a->fz.out_lm = a->bz.out_lm = out.lm;
+    a->bz.out_bias = out.bias;
+}
+
+template <class Fam, bool LM, bool BIAS, int MODE>
+static void launch_beam_as(const Launch<Fam>& a) {
+    Fuse<LM> f;
+    Bias<BIAS> g;
+    if constexpr (LM) f = a.fz;
+    if constexpr (BIAS) g = a.bz;
+    if constexpr (Fam::GRAM) {
+        GStrm<MODE> sz;
+        GBiasStrm<BIAS && MODE != ONESHOT> gs;
+        if constexpr (MODE != ONESHOT) static_cast<GStrmArgs&>(sz) = a.sz;
+        if constexpr (BIAS && MODE != ONESHOT) static_cast<GBiasState&>(gs) = a.bs;
+        hipLaunchKernelGGL((gram_beam_kernel<LM, BIAS, MODE>), dim3(a.B), dim3(THREADS), 0, a.st, a.x, a.lengths, a.T, a.B, a.V, a.W, a.K,
+                           a.blank, a.ws, (const int2*)a.cgr, a.out.ids, a.out.len, a.out.score, f, sz, g, gs);
+    } else {
+        Strm<MODE> sz;
+        if constexpr (MODE != ONESHOT) static_cast<StrmArgs&>(sz) = a.sz;
+        hipLaunchKernelGGL((beam_kernel<LM, BIAS, MODE>), dim3(a.B), dim3(THREADS), 0, a.st, a.x, a.lengths, a.T, a.B, a.V, a.W, a.K,
+                           a.blank, a.ws, a.out.ids, a.out.len, a.out.score, f, g, sz);
     }
 }
 
-// the Gram-CTC stream's variant word (GState's header, gram_state_layout)
-static int gram_variant(bool with_lm, bool with_bias) { return GRAM_VARIANT | (with_lm ? 1 : 0) | (with_bias ? 2 : 0); }
+// The one place a variant word becomes a kernel: bit 0 the model, bit 1 the graph.  Both families in all three modes come through
+// here, so the instantiations are beam_kernel and gram_beam_kernel <LM, BIAS, MODE> over everything, 12 each.
+template <class Fam, int MODE>
+static void launch_beam(int variant, const Launch<Fam>& a) {
+    switch (variant & 3) {
+        case 0: launch_beam_as<Fam, false, false, MODE>(a); break;
+        case 1: launch_beam_as<Fam, true, false, MODE>(a); break;
+        case 2: launch_beam_as<Fam, false, true, MODE>(a); break;
+        default: launch_beam_as<Fam, true, true, MODE>(a);
+    }
+}
 
-// the checks on dimensions, state size and the model / graph arguments that advance and result share; fills fz->lm, bz->g and sz->s
-static int gram_stream_open(int B, int W, int F, const float* uni, int vlm, const int32_t* keys, const float* vals, int slots,
-                            int max_probe, int order, int bos, const int32_t* g_keys, const int32_t* g_vals, int g_slots,
-                            int g_max_probe, const float* g_ret, int g_n_states, void* state, size_t state_bytes, Fuse<true>* fz,
-                            Bias<true>* bz, GStrmArgs* sz, GBiasState* bs) {
-    const int lim = stream_dims(state != nullptr, B, W, F, 2);
+// cand_kernel over the (T, B, V) logits into a.ws, then for Gram-CTC gram_rows_kernel over the candidate rows into a.cgr
+// (nothing to spell where a row can have no candidate)
+template <class Fam>
+static int launch_cand(const Launch<Fam>& a, float min_logp, const int32_t* gram) {
+    const long long rows = (long long)a.T * a.B;
+    hipLaunchKernelGGL(cand_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, a.st, a.x, a.lengths, a.T, a.B, a.V, a.blank, a.K,
+                       min_logp, a.ws);
+    ASR_LAUNCH_CHECK();
+    if (Fam::GRAM && a.K > 0) {
+        hipLaunchKernelGGL(gram_rows_kernel, dim3((unsigned)((rows * a.K + 255) / 256)), dim3(256), 0, a.st, a.lengths, a.T, a.B, a.K,
+                           a.ws, (const int2*)gram, a.cgr);
+        ASR_LAUNCH_CHECK();
+    }
+    return ASR_OK;
+}
+
+// the workspace of a one-shot search (`table`) or of a stream's advance, whose prefix table is the state's
+template <class Fam>
+static size_t ws_bytes(int T, int B, int V, int beam_width, int top_k, bool table) {
+    if (T <= 0 || B <= 0 || V <= 0 || beam_width <= 0 || top_k <= 0) return 0;
+    return Fam::ws(T, B, table ? beam_width : 0, min(top_k, V - 1), nullptr, nullptr, nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------- the one-shot driver
+// Which one-shot entry calls: PLAIN has neither model nor graph nor the ctc / lm outputs; WITH_LM requires the model, so its
+// vlm / bos / eos test runs whatever uni is (a null uni is then make_lm's BAD_ARG); WITH_BIAS requires the graph and takes the
+// model only if uni != NULL, so without one its vlm, bos and eos are not looked at.
+enum Kind { PLAIN, WITH_LM, WITH_BIAS };
+
+// Order of the codes: the common BAD_ARGs, the entry's outputs, the model (its vlm / bos / eos BAD_ARG first), the graph,
+// Gram-CTC's missing inventory (UNSUPPORTED), the limits' UNSUPPORTED, the workspace.
+template <class Fam>
+static int oneshot(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank, int beam_width, int top_k,
+                   float min_logp, const int32_t* gram, Kind kind, LmArgs lm, int bos, int eos, float alpha, float beta,
+                   GraphArgs graph, void* workspace, size_t workspace_bytes, Outs out) {
+    const int lim = oneshot_check(logits, workspace, out, T, B, V, blank, beam_width, top_k, Fam::PER_FRAME);
     if (lim == ASR_ERR_BAD_ARG) return lim;
-    const bool with_lm = uni != nullptr, with_bias = g_ret != nullptr;
+    if (kind != PLAIN && (!out.ctc || !out.lm)) return ASR_ERR_BAD_ARG;
+    if (kind == WITH_BIAS && !out.bias) return ASR_ERR_BAD_ARG;
+    const bool with_lm = kind == WITH_LM || lm.uni != nullptr;
+    Launch<Fam> a{};
+    int rc;
     if (with_lm) {
-        if (bos >= vlm) return ASR_ERR_BAD_ARG;
-        const int rc = make_lm(uni, vlm, keys, vals, slots, max_probe, order, &fz->lm);
+        if (lm.vlm < V || bos >= lm.vlm || eos >= lm.vlm) return ASR_ERR_BAD_ARG;
+        rc = make_lm(lm, &a.fz.lm);
+        if (rc != ASR_OK) return rc;
+    }
+    if (kind == WITH_BIAS) {
+        rc = make_graph(graph, &a.bz.g);
+        if (rc != ASR_OK) return rc;
+    }
+    if (Fam::GRAM && !gram) return ASR_ERR_UNSUPPORTED;
+    if (lim != ASR_OK) return lim;
+    a.st = (hipStream_t)stream, a.x = logits, a.lengths = lengths;
+    a.T = T, a.B = B, a.V = V, a.W = beam_width, a.K = min(top_k, V - 1), a.blank = blank;
+    if (workspace_bytes < Fam::ws(T, B, beam_width, a.K, (char*)workspace, &a.ws, &a.cgr)) return ASR_ERR_WORKSPACE;
+    fill_fuse(&a, bos, eos, alpha, beta, out);
+    rc = launch_cand(a, min_logp, gram);
+    if (rc != ASR_OK) return rc;
+    launch_beam<Fam, ONESHOT>(Fam::variant(with_lm, kind == WITH_BIAS), a);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- the stream drivers
+template <class Fam>
+static size_t stream_state_bytes(int B, int beam_width, int max_frames, int with_lm, int with_bias) {
+    if (stream_dims(true, B, beam_width, max_frames, Fam::PER_FRAME) == ASR_ERR_BAD_ARG) return 0;
+    return Fam::state(B, beam_width, max_frames, Fam::variant(with_lm, with_bias), nullptr, nullptr, nullptr);
+}
+
+// The header and the root beam of every utterance, or of those with mask[b] != 0.  The two states differ, so each family has
+// its kernel; `bos` is the CTC stream's alone (Gram-CTC gives it to advance and result), and nothing here can test it: there
+// is no vlm.
+template <class Fam>
+static int stream_reset(void* stream, void* state, size_t state_bytes, int B, int beam_width, int max_frames, int with_lm,
+                        int with_bias, int bos, const int32_t* mask) {
+    const int rc = stream_dims(state != nullptr, B, beam_width, max_frames, Fam::PER_FRAME);
+    if (rc != ASR_OK) return rc;
+    const int variant = Fam::variant(with_lm, with_bias);
+    typename Fam::Args sz;
+    GBiasState bs{};
+    if (state_bytes < Fam::state(B, beam_width, max_frames, variant, (char*)state, &sz, &bs)) return ASR_ERR_WORKSPACE;
+    const dim3 grid((unsigned)((B + 255) / 256));
+    if constexpr (Fam::GRAM) {
+        hipLaunchKernelGGL(gram_stream_reset_kernel, grid, dim3(256), 0, (hipStream_t)stream, sz.s, B, beam_width, max_frames, variant,
+                           mask, bs);
+    } else {
+        hipLaunchKernelGGL(stream_reset_kernel, grid, dim3(256), 0, (hipStream_t)stream, sz.s, B, beam_width, max_frames, variant,
+                           bos < 0 ? -1 : bos, mask);
+    }
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+// The checks on dimensions, state size and the model / graph arguments that advance and result share, in this order: the
+// dimensions' BAD_ARG, the model, the graph, the limits' UNSUPPORTED, the state size (WORKSPACE).  A model or a graph is there
+// if its uni / ret is.  Fills a->fz.lm, a->bz.g, a->sz and a->bs.
+template <class Fam>
+static int stream_open(int B, int W, int F, LmArgs lm, int bos, GraphArgs graph, void* state, size_t state_bytes, Launch<Fam>* a) {
+    const int lim = stream_dims(state != nullptr, B, W, F, Fam::PER_FRAME);
+    if (lim == ASR_ERR_BAD_ARG) return lim;
+    const bool with_lm = lm.uni != nullptr, with_bias = graph.ret != nullptr;
+    if (with_lm) {
+        // Gram-CTC's advance and result take bos, and it is tested here.  The CTC stream's bos went to reset (above), so its
+        // advance and result have none to test.
+        if (Fam::GRAM && bos >= lm.vlm) return ASR_ERR_BAD_ARG;
+        const int rc = make_lm(lm, &a->fz.lm);
         if (rc != ASR_OK) return rc;
     }
     if (with_bias) {
-        const int rc = make_graph(g_keys, g_vals, g_slots, g_max_probe, g_ret, g_n_states, &bz->g);
+        const int rc = make_graph(graph, &a->bz.g);
         if (rc != ASR_OK) return rc;
-    } else if (g_keys || g_vals || g_slots != 0 || g_n_states != 0) {
+    } else if (graph.keys || graph.vals || graph.slots != 0 || graph.n_states != 0) {
         return ASR_ERR_BAD_ARG;                      // a graph without its ret: section 22's check, not "no graph"
     }
     if (lim != ASR_OK) return lim;
-    sz->max_frames = F;
-    sz->variant = gram_variant(with_lm, with_bias);
-    sz->out_frames = nullptr;
-    if (state_bytes < gram_state_layout(B, W, F, sz->variant, (char*)state, &sz->s, bs)) return ASR_ERR_WORKSPACE;
+    a->sz.max_frames = F;
+    a->sz.variant = Fam::variant(with_lm, with_bias);
+    a->sz.out_frames = nullptr;
+    if (state_bytes < Fam::state(B, W, F, a->sz.variant, (char*)state, &a->sz, &a->bs)) return ASR_ERR_WORKSPACE;
+    return ASR_OK;
+}
+
+// Order of the codes: the entry's BAD_ARGs, stream_open's, Gram-CTC's missing inventory, the top_k limits, the frames the state
+// has room for (all three UNSUPPORTED), the workspace.  So a state that is too small beats a top_k that is too large.
+// `bos`: Gram-CTC's; the CTC entry passes -1.
+template <class Fam>
+static int stream_advance(void* stream, const float* logits, const int32_t* lengths, int Tc, int B, int V, int blank, int beam_width,
+                          int top_k, float min_logp, const int32_t* gram, LmArgs lm, int bos, GraphArgs graph, float alpha,
+                          float beta, int frames_before, int max_frames, void* state, size_t state_bytes, void* workspace,
+                          size_t workspace_bytes) {
+    if (!logits || !workspace || Tc <= 0 || V <= 0 || blank < 0 || blank >= V || top_k <= 0 || frames_before < 0)
+        return ASR_ERR_BAD_ARG;
+    if (lm.uni && lm.vlm < V) return ASR_ERR_BAD_ARG;
+    Launch<Fam> a{};
+    int rc = stream_open(B, beam_width, max_frames, lm, bos, graph, state, state_bytes, &a);
+    if (rc != ASR_OK) return rc;
+    if (Fam::GRAM && !gram) return ASR_ERR_UNSUPPORTED;
+    if (top_k > MAX_TOPK || beam_width * top_k > MAX_EXT) return ASR_ERR_UNSUPPORTED;
+    if ((long long)frames_before + Tc > max_frames) return ASR_ERR_UNSUPPORTED;
+    a.st = (hipStream_t)stream, a.x = logits, a.lengths = lengths;
+    a.T = Tc, a.B = B, a.V = V, a.W = beam_width, a.K = min(top_k, V - 1), a.blank = blank;
+    if (workspace_bytes < Fam::ws(Tc, B, 0, a.K, (char*)workspace, &a.ws, &a.cgr)) return ASR_ERR_WORKSPACE;
+    fill_fuse(&a, bos, -1, alpha, beta, Outs{});     // the contexts start in reset (CTC) or with bos; they end in result
+    rc = launch_cand(a, min_logp, gram);
+    if (rc != ASR_OK) return rc;
+    launch_beam<Fam, ADVANCE>(a.sz.variant, a);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+// Order of the codes: the outputs, of which ctc / lm / bias are required only by the variants that write them, eos against vlm,
+// then stream_open's.  `bos`: Gram-CTC's; the CTC entry passes -1.
+template <class Fam>
+static int stream_result(void* stream, LmArgs lm, int bos, int eos, GraphArgs graph, float alpha, float beta, int B, int beam_width,
+                         int max_frames, int blank, int Lcap, const void* state, size_t state_bytes, Outs out, int32_t* out_frames) {
+    if (!out.ids || !out.len || !out.score || !out_frames || Lcap <= 0 || blank < 0) return ASR_ERR_BAD_ARG;
+    if ((lm.uni || graph.ret) && (!out.ctc || !out.lm)) return ASR_ERR_BAD_ARG;
+    if (graph.ret && !out.bias) return ASR_ERR_BAD_ARG;
+    if (lm.uni && eos >= lm.vlm) return ASR_ERR_BAD_ARG;
+    Launch<Fam> a{};
+    const int rc = stream_open(B, beam_width, max_frames, lm, bos, graph, const_cast<void*>(state), state_bytes, &a);
+    if (rc != ASR_OK) return rc;
+    a.sz.out_frames = out_frames;
+    a.st = (hipStream_t)stream;
+    a.T = Lcap, a.B = B, a.W = beam_width, a.blank = blank;     // no logits, no candidates: the tail only
+    fill_fuse(&a, bos, eos, alpha, beta, out);
+    launch_beam<Fam, RESULT>(a.sz.variant, a);
+    ASR_LAUNCH_CHECK();
     return ASR_OK;
 }
 
 }  // namespace beam
 }  // namespace asr
 
-// The family with a graph.  Without one (with_bias == 0, g_ret == NULL) it is the family of section 26, size
-// for size and byte for byte, so those entries are these with no graph.
-extern "C" size_t asr_gram_ctc_beam_bias_stream_state_bytes(int B, int beam_width, int max_frames, int with_lm, int with_bias) {
-    if (stream_dims(true, B, beam_width, max_frames, 2) == ASR_ERR_BAD_ARG) return 0;
-    return gram_state_layout(B, beam_width, max_frames, gram_variant(with_lm, with_bias), nullptr, nullptr);
-}
+using namespace asr;
+using namespace asr::beam;
 
-extern "C" size_t asr_gram_ctc_beam_stream_state_bytes(int B, int beam_width, int max_frames, int with_lm) {
-    return asr_gram_ctc_beam_bias_stream_state_bytes(B, beam_width, max_frames, with_lm, 0);
-}
+// ---------------------------------------------------------------------------------------------- the entries
+// Each packs its arguments and forwards; what an entry does not take is a null pack (no model, no graph), -1 (no bos) or a null
+// output.  The *_workspace_bytes of one search family are one size.
+static const LmArgs NO_LM{};
+static const GraphArgs NO_GRAPH{};
 
-extern "C" size_t asr_gram_ctc_beam_stream_workspace_bytes(int Tc, int B, int V, int beam_width, int top_k) {
-    if (Tc <= 0 || B <= 0 || V <= 0 || beam_width <= 0 || top_k <= 0) return 0;
-    return gram_ws_layout(Tc, B, 0, min(top_k, V - 1), nullptr, nullptr, nullptr);    // candidate rows and spellings; no table
-}
-
-extern "C" int asr_gram_ctc_beam_bias_stream_reset(void* stream, void* state, size_t state_bytes, int B, int beam_width,
-                                                   int max_frames, int with_lm, int with_bias, const int32_t* mask) {
-    const int rc = stream_dims(state != nullptr, B, beam_width, max_frames, 2);
+extern "C" int asr_ngram_score(void* stream, const float* uni, int vlm, const int32_t* keys, const float* vals, int slots,
+                               int max_probe, int order, const int32_t* ids, const int32_t* lengths, int N, int Lmax, int bos,
+                               int eos, float* out_tok, float* out_sum) {
+    if (!ids || !out_tok || !out_sum || N <= 0 || Lmax <= 0 || bos >= vlm || eos >= vlm) return ASR_ERR_BAD_ARG;
+    ngram::Lm lm;
+    const int rc = make_lm({uni, vlm, keys, vals, slots, max_probe, order}, &lm);
     if (rc != ASR_OK) return rc;
-    const int variant = gram_variant(with_lm, with_bias);
-    GState s;
-    GBiasState bs;
-    if (state_bytes < gram_state_layout(B, beam_width, max_frames, variant, (char*)state, &s, &bs)) return ASR_ERR_WORKSPACE;
-    hipLaunchKernelGGL(gram_stream_reset_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, s, B,
-                       beam_width, max_frames, variant, mask, bs);
+    hipLaunchKernelGGL(ngram_score_kernel, dim3(N), dim3(THREADS), 0, (hipStream_t)stream, lm, ids, lengths, Lmax, bos < 0 ? -1 : bos,
+                       eos < 0 ? -1 : eos, out_tok, out_sum);
     ASR_LAUNCH_CHECK();
     return ASR_OK;
 }
 
+extern "C" int asr_ctx_score(void* stream, const int32_t* g_keys, const int32_t* g_vals, int g_slots, int g_max_probe,
+                             const float* g_ret, int g_n_states, int V, const int32_t* ids, const int32_t* lengths, int N,
+                             int Lmax, int finalize, float* out_tok, float* out_sum) {
+    if (!ids || !out_tok || !out_sum || N <= 0 || Lmax <= 0 || V <= 0) return ASR_ERR_BAD_ARG;
+    ctx::Graph g;
+    const int rc = make_graph({g_keys, g_vals, g_slots, g_max_probe, g_ret, g_n_states}, &g);
+    if (rc != ASR_OK) return rc;
+    hipLaunchKernelGGL(ctx_score_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, (hipStream_t)stream, g, V, ids, lengths, N,
+                       Lmax, finalize, out_tok, out_sum);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
+}
+
+// ---- CTC, one-shot
+extern "C" size_t asr_ctc_beam_workspace_bytes(int T, int B, int V, int beam_width, int top_k) {
+    return ws_bytes<Ctc>(T, B, V, beam_width, top_k, true);
+}
+
+extern "C" size_t asr_ctc_beam_lm_workspace_bytes(int T, int B, int V, int beam_width, int top_k) {
+    return ws_bytes<Ctc>(T, B, V, beam_width, top_k, true);
+}
+
+extern "C" size_t asr_ctc_beam_bias_workspace_bytes(int T, int B, int V, int beam_width, int top_k) {
+    return ws_bytes<Ctc>(T, B, V, beam_width, top_k, true);
+}
+
+extern "C" int asr_ctc_beam_search(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank,
+                                   int beam_width, int top_k, float min_logp, void* workspace, size_t workspace_bytes,
+                                   int32_t* out_ids, int32_t* out_len, float* out_score) {
+    return oneshot<Ctc>(stream, logits, lengths, T, B, V, blank, beam_width, top_k, min_logp, nullptr, PLAIN, NO_LM, -1, -1, 0.f, 0.f,
+                        NO_GRAPH, workspace, workspace_bytes, {out_ids, out_len, out_score, nullptr, nullptr, nullptr});
+}
+
+extern "C" int asr_ctc_beam_search_lm(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank,
+                                      int beam_width, int top_k, float min_logp, const float* uni, int vlm, const int32_t* keys,
+                                      const float* vals, int slots, int max_probe, int order, int bos, int eos, float alpha,
+                                      float beta, void* workspace, size_t workspace_bytes, int32_t* out_ids, int32_t* out_len,
+                                      float* out_score, float* out_ctc, float* out_lm) {
+    return oneshot<Ctc>(stream, logits, lengths, T, B, V, blank, beam_width, top_k, min_logp, nullptr, WITH_LM,
+                        {uni, vlm, keys, vals, slots, max_probe, order}, bos, eos, alpha, beta, NO_GRAPH, workspace, workspace_bytes,
+                        {out_ids, out_len, out_score, out_ctc, out_lm, nullptr});
+}
+
+extern "C" int asr_ctc_beam_search_bias(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank,
+                                        int beam_width, int top_k, float min_logp, const float* uni, int vlm, const int32_t* keys,
+                                        const float* vals, int slots, int max_probe, int order, int bos, int eos, float alpha,
+                                        float beta, void* workspace, size_t workspace_bytes, int32_t* out_ids, int32_t* out_len,
+                                        float* out_score, float* out_ctc, float* out_lm, const int32_t* g_keys,
+                                        const int32_t* g_vals, int g_slots, int g_max_probe, const float* g_ret, int g_n_states,
+                                        float* out_bias) {
+    return oneshot<Ctc>(stream, logits, lengths, T, B, V, blank, beam_width, top_k, min_logp, nullptr, WITH_BIAS,
+                        {uni, vlm, keys, vals, slots, max_probe, order}, bos, eos, alpha, beta,
+                        {g_keys, g_vals, g_slots, g_max_probe, g_ret, g_n_states}, workspace, workspace_bytes,
+                        {out_ids, out_len, out_score, out_ctc, out_lm, out_bias});
+}
+
+// ---- CTC, streaming
+extern "C" size_t asr_ctc_beam_stream_state_bytes(int B, int beam_width, int max_frames, int with_lm, int with_bias) {
+    return stream_state_bytes<Ctc>(B, beam_width, max_frames, with_lm, with_bias);
+}
+
+extern "C" size_t asr_ctc_beam_stream_workspace_bytes(int Tc, int B, int V, int beam_width, int top_k) {
+    return ws_bytes<Ctc>(Tc, B, V, beam_width, top_k, false);
+}
+
+extern "C" int asr_ctc_beam_stream_reset(void* stream, void* state, size_t state_bytes, int B, int beam_width, int max_frames,
+                                         int with_lm, int with_bias, int bos, const int32_t* mask) {
+    return stream_reset<Ctc>(stream, state, state_bytes, B, beam_width, max_frames, with_lm, with_bias, bos, mask);
+}
+
+extern "C" int asr_ctc_beam_stream_advance(void* stream, const float* logits, const int32_t* lengths, int Tc, int B, int V,
+                                           int blank, int beam_width, int top_k, float min_logp, const float* uni, int vlm,
+                                           const int32_t* keys, const float* vals, int slots, int max_probe, int order,
+                                           const int32_t* g_keys, const int32_t* g_vals, int g_slots, int g_max_probe,
+                                           const float* g_ret, int g_n_states, float alpha, float beta, int frames_before,
+                                           int max_frames, void* state, size_t state_bytes, void* workspace,
+                                           size_t workspace_bytes) {
+    return stream_advance<Ctc>(stream, logits, lengths, Tc, B, V, blank, beam_width, top_k, min_logp, nullptr,
+                               {uni, vlm, keys, vals, slots, max_probe, order}, -1,
+                               {g_keys, g_vals, g_slots, g_max_probe, g_ret, g_n_states}, alpha, beta, frames_before, max_frames, state,
+                               state_bytes, workspace, workspace_bytes);
+}
+
+extern "C" int asr_ctc_beam_stream_result(void* stream, const float* uni, int vlm, const int32_t* keys, const float* vals, int slots,
+                                          int max_probe, int order, const int32_t* g_keys, const int32_t* g_vals, int g_slots,
+                                          int g_max_probe, const float* g_ret, int g_n_states, float alpha, float beta, int eos,
+                                          int B, int beam_width, int max_frames, int blank, int Lcap, const void* state,
+                                          size_t state_bytes, int32_t* out_ids, int32_t* out_len, float* out_score, float* out_ctc,
+                                          float* out_lm, float* out_bias, int32_t* out_frames) {
+    return stream_result<Ctc>(stream, {uni, vlm, keys, vals, slots, max_probe, order}, -1, eos,
+                              {g_keys, g_vals, g_slots, g_max_probe, g_ret, g_n_states}, alpha, beta, B, beam_width, max_frames, blank,
+                              Lcap, state, state_bytes, {out_ids, out_len, out_score, out_ctc, out_lm, out_bias}, out_frames);
+}
+
+// ---- Gram-CTC, one-shot
+extern "C" size_t asr_gram_ctc_beam_workspace_bytes(int T, int B, int V, int beam_width, int top_k) {
+    return ws_bytes<Gram>(T, B, V, beam_width, top_k, true);
+}
+
+extern "C" size_t asr_gram_ctc_beam_lm_workspace_bytes(int T, int B, int V, int beam_width, int top_k) {
+    return ws_bytes<Gram>(T, B, V, beam_width, top_k, true);
+}
+
+extern "C" size_t asr_gram_ctc_beam_bias_workspace_bytes(int T, int B, int V, int beam_width, int top_k) {
+    return ws_bytes<Gram>(T, B, V, beam_width, top_k, true);
+}
+
+extern "C" int asr_gram_ctc_beam_search(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank,
+                                        int beam_width, int top_k, float min_logp, const int32_t* gram, void* workspace,
+                                        size_t workspace_bytes, int32_t* out_ids, int32_t* out_len, float* out_score) {
+    return oneshot<Gram>(stream, logits, lengths, T, B, V, blank, beam_width, top_k, min_logp, gram, PLAIN, NO_LM, -1, -1, 0.f, 0.f,
+                         NO_GRAPH, workspace, workspace_bytes, {out_ids, out_len, out_score, nullptr, nullptr, nullptr});
+}
+
+extern "C" int asr_gram_ctc_beam_search_lm(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank,
+                                           int beam_width, int top_k, float min_logp, const int32_t* gram, const float* uni, int vlm,
+                                           const int32_t* keys, const float* vals, int slots, int max_probe, int order, int bos,
+                                           int eos, float alpha, float beta, void* workspace, size_t workspace_bytes,
+                                           int32_t* out_ids, int32_t* out_len, float* out_score, float* out_ctc, float* out_lm) {
+    return oneshot<Gram>(stream, logits, lengths, T, B, V, blank, beam_width, top_k, min_logp, gram, WITH_LM,
+                         {uni, vlm, keys, vals, slots, max_probe, order}, bos, eos, alpha, beta, NO_GRAPH, workspace, workspace_bytes,
+                         {out_ids, out_len, out_score, out_ctc, out_lm, nullptr});
+}
+
+extern "C" int asr_gram_ctc_beam_search_bias(void* stream, const float* logits, const int32_t* lengths, int T, int B, int V, int blank,
+                                             int beam_width, int top_k, float min_logp, const int32_t* gram, const float* uni, int vlm,
+                                             const int32_t* keys, const float* vals, int slots, int max_probe, int order, int bos,
+                                             int eos, float alpha, float beta, void* workspace, size_t workspace_bytes,
+                                             int32_t* out_ids, int32_t* out_len, float* out_score, float* out_ctc, float* out_lm,
+                                             const int32_t* g_keys, const int32_t* g_vals, int g_slots, int g_max_probe,
+                                             const float* g_ret, int g_n_states, float* out_bias) {
+    return oneshot<Gram>(stream, logits, lengths, T, B, V, blank, beam_width, top_k, min_logp, gram, WITH_BIAS,
+                         {uni, vlm, keys, vals, slots, max_probe, order}, bos, eos, alpha, beta,
+                         {g_keys, g_vals, g_slots, g_max_probe, g_ret, g_n_states}, workspace, workspace_bytes,
+                         {out_ids, out_len, out_score, out_ctc, out_lm, out_bias});
+}
+
+// ---- Gram-CTC, streaming.  The family with a graph is the family: without one (with_bias == 0,
+// g_ret == NULL) it is section 26's, size for size and byte for byte, so the narrow entries are these with no graph.
+extern "C" size_t asr_gram_ctc_beam_bias_stream_state_bytes(int B, int beam_width, int max_frames, int with_lm, int with_bias) {
+    return stream_state_bytes<Gram>(B, beam_width, max_frames, with_lm, with_bias);
+}
+
+extern "C" size_t asr_gram_ctc_beam_stream_state_bytes(int B, int beam_width, int max_frames, int with_lm) {
+    return stream_state_bytes<Gram>(B, beam_width, max_frames, with_lm, 0);
+}
+
+extern "C" size_t asr_gram_ctc_beam_stream_workspace_bytes(int Tc, int B, int V, int beam_width, int top_k) {
+    return ws_bytes<Gram>(Tc, B, V, beam_width, top_k, false);
+}
+
+extern "C" int asr_gram_ctc_beam_bias_stream_reset(void* stream, void* state, size_t state_bytes, int B, int beam_width,
+                                                   int max_frames, int with_lm, int with_bias, const int32_t* mask) {
+    return stream_reset<Gram>(stream, state, state_bytes, B, beam_width, max_frames, with_lm, with_bias, -1, mask);
+}
+
 extern "C" int asr_gram_ctc_beam_stream_reset(void* stream, void* state, size_t state_bytes, int B, int beam_width, int max_frames,
                                               int with_lm, const int32_t* mask) {
-    return asr_gram_ctc_beam_bias_stream_reset(stream, state, state_bytes, B, beam_width, max_frames, with_lm, 0, mask);
+    return stream_reset<Gram>(stream, state, state_bytes, B, beam_width, max_frames, with_lm, 0, -1, mask);
 }
 
 extern "C" int asr_gram_ctc_beam_bias_stream_advance(void* stream, const float* logits, const int32_t* lengths, int Tc, int B, int V,
@@ -2304,32 +2260,10 @@ extern "C" int asr_gram_ctc_beam_bias_stream_advance(void* stream, const float* 
                                                      const int32_t* g_vals, int g_slots, int g_max_probe, const float* g_ret,
                                                      int g_n_states, float alpha, float beta, int frames_before, int max_frames,
                                                      void* state, size_t state_bytes, void* workspace, size_t workspace_bytes) {
-    if (!logits || !workspace || Tc <= 0 || V <= 0 || blank < 0 || blank >= V || top_k <= 0 || frames_before < 0)
-        return ASR_ERR_BAD_ARG;
-    if (uni && vlm < V) return ASR_ERR_BAD_ARG;
-    Fuse<true> fz{};
-    Bias<true> bz{};
-    GStrm<ADVANCE> sz{};
-    GBiasState bs{};
-    int rc = gram_stream_open(B, beam_width, max_frames, uni, vlm, keys, vals, slots, max_probe, order, bos, g_keys, g_vals, g_slots,
-                              g_max_probe, g_ret, g_n_states, state, state_bytes, &fz, &bz, &sz, &bs);
-    if (rc != ASR_OK) return rc;
-    if (!gram) return ASR_ERR_UNSUPPORTED;
-    if (top_k > MAX_TOPK || beam_width * top_k > MAX_EXT) return ASR_ERR_UNSUPPORTED;
-    if ((long long)frames_before + Tc > max_frames) return ASR_ERR_UNSUPPORTED;
-    const int K = min(top_k, V - 1);
-    Ws ws;
-    int2* cgr;
-    if (workspace_bytes < gram_ws_layout(Tc, B, 0, K, (char*)workspace, &ws, &cgr)) return ASR_ERR_WORKSPACE;
-    fill_fuse(&fz, bos, -1, alpha, beta, nullptr, nullptr);      // the strings end in result
-    rc = launch_cand(stream, logits, lengths, Tc, B, V, blank, K, min_logp, ws);
-    if (rc != ASR_OK) return rc;
-    rc = launch_gram_rows(stream, lengths, Tc, B, K, ws, gram, cgr);
-    if (rc != ASR_OK) return rc;
-    launch_gram_stream<ADVANCE>((hipStream_t)stream, logits, lengths, Tc, B, V, beam_width, K, blank, ws, (const int2*)cgr, nullptr,
-                                nullptr, nullptr, fz, bz, sz, bs);
-    ASR_LAUNCH_CHECK();
-    return ASR_OK;
+    return stream_advance<Gram>(stream, logits, lengths, Tc, B, V, blank, beam_width, top_k, min_logp, gram,
+                                {uni, vlm, keys, vals, slots, max_probe, order}, bos,
+                                {g_keys, g_vals, g_slots, g_max_probe, g_ret, g_n_states}, alpha, beta, frames_before, max_frames, state,
+                                state_bytes, workspace, workspace_bytes);
 }
 
 extern "C" int asr_gram_ctc_beam_stream_advance(void* stream, const float* logits, const int32_t* lengths, int Tc, int B, int V,
@@ -2338,9 +2272,9 @@ extern "C" int asr_gram_ctc_beam_stream_advance(void* stream, const float* logit
                                                 int max_probe, int order, int bos, float alpha, float beta, int frames_before,
                                                 int max_frames, void* state, size_t state_bytes, void* workspace,
                                                 size_t workspace_bytes) {
-    return asr_gram_ctc_beam_bias_stream_advance(stream, logits, lengths, Tc, B, V, blank, beam_width, top_k, min_logp, gram, uni, vlm,
-                                                 keys, vals, slots, max_probe, order, bos, nullptr, nullptr, 0, 0, nullptr, 0, alpha,
-                                                 beta, frames_before, max_frames, state, state_bytes, workspace, workspace_bytes);
+    return stream_advance<Gram>(stream, logits, lengths, Tc, B, V, blank, beam_width, top_k, min_logp, gram,
+                                {uni, vlm, keys, vals, slots, max_probe, order}, bos, NO_GRAPH, alpha, beta, frames_before, max_frames,
+                                state, state_bytes, workspace, workspace_bytes);
 }
 
 extern "C" int asr_gram_ctc_beam_bias_stream_result(void* stream, const float* uni, int vlm, const int32_t* keys, const float* vals,
@@ -2350,27 +2284,9 @@ extern "C" int asr_gram_ctc_beam_bias_stream_result(void* stream, const float* u
                                                     int blank, int Lcap, const void* state, size_t state_bytes, int32_t* out_ids,
                                                     int32_t* out_len, float* out_score, float* out_ctc, float* out_lm,
                                                     float* out_bias, int32_t* out_frames) {
-    if (!out_ids || !out_len || !out_score || !out_frames || Lcap <= 0 || blank < 0) return ASR_ERR_BAD_ARG;
-    if ((uni || g_ret) && (!out_ctc || !out_lm)) return ASR_ERR_BAD_ARG;
-    if (g_ret && !out_bias) return ASR_ERR_BAD_ARG;
-    if (uni && eos >= vlm) return ASR_ERR_BAD_ARG;
-    Fuse<true> fz{};
-    Bias<true> bz{};
-    GStrm<RESULT> sz{};
-    GBiasState bs{};
-    const int rc = gram_stream_open(B, beam_width, max_frames, uni, vlm, keys, vals, slots, max_probe, order, bos, g_keys, g_vals,
-                                    g_slots, g_max_probe, g_ret, g_n_states, const_cast<void*>(state), state_bytes, &fz, &bz, &sz,
-                                    &bs);
-    if (rc != ASR_OK) return rc;
-    sz.out_frames = out_frames;
-    fill_fuse(&fz, bos, eos, alpha, beta, out_ctc, out_lm);
-    bz.out_ctc = out_ctc;
-    bz.out_lm = out_lm;
-    bz.out_bias = out_bias;
-    launch_gram_stream<RESULT>((hipStream_t)stream, nullptr, nullptr, Lcap, B, 0, beam_width, 0, blank, Ws{}, nullptr, out_ids,
-                               out_len, out_score, fz, bz, sz, bs);
-    ASR_LAUNCH_CHECK();
-    return ASR_OK;
+    return stream_result<Gram>(stream, {uni, vlm, keys, vals, slots, max_probe, order}, bos, eos,
+                               {g_keys, g_vals, g_slots, g_max_probe, g_ret, g_n_states}, alpha, beta, B, beam_width, max_frames, blank,
+                               Lcap, state, state_bytes, {out_ids, out_len, out_score, out_ctc, out_lm, out_bias}, out_frames);
 }
 
 extern "C" int asr_gram_ctc_beam_stream_result(void* stream, const float* uni, int vlm, const int32_t* keys, const float* vals,
@@ -2378,9 +2294,9 @@ extern "C" int asr_gram_ctc_beam_stream_result(void* stream, const float* uni, i
                                                int beam_width, int max_frames, int blank, int Lcap, const void* state,
                                                size_t state_bytes, int32_t* out_ids, int32_t* out_len, float* out_score,
                                                float* out_ctc, float* out_lm, int32_t* out_frames) {
-    return asr_gram_ctc_beam_bias_stream_result(stream, uni, vlm, keys, vals, slots, max_probe, order, bos, eos, nullptr, nullptr, 0, 0,
-                                                nullptr, 0, alpha, beta, B, beam_width, max_frames, blank, Lcap, state, state_bytes,
-                                                out_ids, out_len, out_score, out_ctc, out_lm, nullptr, out_frames);
+    return stream_result<Gram>(stream, {uni, vlm, keys, vals, slots, max_probe, order}, bos, eos, NO_GRAPH, alpha, beta, B, beam_width,
+                               max_frames, blank, Lcap, state, state_bytes, {out_ids, out_len, out_score, out_ctc, out_lm, nullptr},
+                               out_frames);
 }
 
 // ------------------------------------------------------------------------------ commit: a stream of any length
