@@ -236,6 +236,11 @@ SIGNATURES = {
     "asr_spp_fwd": (c_int, [c_void_p] * 4 + [c_int] * 5),
     "asr_spp_bwd": (c_int, [c_void_p] * 4 + [c_int] * 5),
     "asr_sgd_ctl": (c_int, [c_void_p] * 4 + [c_longlong, c_int] + [c_float] * 3 + [c_void_p]),
+    "asr_lookahead_ws_bytes": (c_size_t, [c_int] * 4),
+    "asr_lookahead_fwd": (c_int, [c_void_p] * 5 + [c_int] * 4),
+    "asr_lookahead_bwd": (c_int, [c_void_p] * 8 + [c_size_t] + [c_int] * 4),
+    "asr_stream_push": (c_int, [c_void_p] * 9 + [c_int] * 5),
+    "asr_stream_push_reset": (c_int, [c_void_p] * 4 + [c_int] * 3),
 }
 
 _ERRORS = {-1: "bad argument", -2: "workspace too small", -3: "unsupported shape", -4: "kernel launch failed"}

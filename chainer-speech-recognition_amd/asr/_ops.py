@@ -1537,3 +1537,65 @@ def gaussian_noise(x, std, seed):
     y = torch.empty_like(x)
     check(_lib.lib().asr_gaussian_noise(stream(), ptr(x), ptr(y), x.numel(), float(std), int(seed) & 0xffffffff), "asr_gaussian_noise")
     return y
+
+
+# ---------------------------------------------------------------------------------------------- lookahead convolution / carried rows
+LOOKAHEAD_MAX_TAU = 96          # ASR_LOOKAHEAD_MAX_TAU and ASR_LOOKAHEAD_TIME_TILE of include/asr_hip.h
+LOOKAHEAD_TIME_TILE = 64
+STREAM_CONTEXT, STREAM_LOOKAHEAD = 0, 1
+
+
+def _lookahead_args(x, w):
+    if x.dtype != BF16 or x.dim() != 3 or not x.is_contiguous():
+        raise ValueError("expected contiguous (T, B, D) activations, got %s %s" % (x.dtype, tuple(x.shape)))
+    T, B, D = x.shape
+    if w.dtype != F32 or w.dim() != 2 or w.shape[0] != D or not w.is_contiguous():
+        raise ValueError("the lookahead weight must be (%d, tau + 1) float32, got %s" % (D, tuple(w.shape)))
+    return T, B, D, w.shape[1] - 1
+
+
+def lookahead_fwd(x, w, x_len=None, out=None):
+    """x (T, B, D) activations, w (D, tau + 1) f32, x_len (B) int32 or None -> y (T, B, D): y[t] = sum_j w[:, j] x[t + j] (asr_hip.h)"""
+    T, B, D, tau = _lookahead_args(x, w)
+    x_len = _len_i32(x_len, B, x.device)
+    y = torch.empty_like(x) if out is None else out
+    assert y.dtype == BF16 and y.shape == x.shape and y.is_contiguous()
+    check(_lib.lib().asr_lookahead_fwd(stream(), ptr(x), ptr(w), ptr(x_len), ptr(y), T, B, D, tau), "asr_lookahead_fwd")
+    return y
+
+
+def lookahead_bwd(gy, x, w, x_len=None, dW=None, need_dx=True):
+    """-> dx (T, B, D) or None; dW (D, tau + 1) f32 (optional) += the weight gradient, in two ordered stages (bit-reproducible)"""
+    T, B, D, tau = _lookahead_args(gy, w)
+    x_len = _len_i32(x_len, B, gy.device)
+    dx = torch.empty_like(gy) if need_dx else None
+    ws, nbytes = None, 0
+    if dW is not None:
+        assert dW.dtype == F32 and dW.shape == w.shape and dW.is_contiguous() and x.shape == gy.shape and x.dtype == BF16 and x.is_contiguous()
+        nbytes = _lib.lib().asr_lookahead_ws_bytes(T, B, D, tau)
+        ws = torch.empty(max(nbytes, 4) // 4, dtype=F32, device=gy.device)
+    check(_lib.lib().asr_lookahead_bwd(stream(), ptr(gy), ptr(x) if dW is not None else None, ptr(w), ptr(x_len), ptr(dx), ptr(dW), ptr(ws),
+                                       nbytes, T, B, D, tau), "asr_lookahead_bwd")
+    return dx
+
+
+def stream_push(state, m, chunk, n, window, mode, flush=None):
+    """asr_stream_push: state (K, B, R) activations (updated), m (B) int32 (lookahead mode; updated) or None, chunk (Tc, B, R) or None
+    (a flush), n (B) int32 or None, window (K + Tc, B, R) (written) -> (wlen, emit), (B) int32 each"""
+    K, B, R = state.shape
+    Tc = 0 if chunk is None else chunk.shape[0]
+    assert state.dtype == BF16 and window.dtype == BF16 and tuple(window.shape) == (K + Tc, B, R)
+    assert chunk is None or (chunk.dtype == BF16 and tuple(chunk.shape[1:]) == (B, R))
+    wlen = torch.empty((B,), dtype=torch.int32, device=state.device)
+    emit = torch.empty((B,), dtype=torch.int32, device=state.device)
+    check(_lib.lib().asr_stream_push(stream(), ptr(state) if K else None, ptr(m), ptr(chunk), ptr(_len_i32(n, B, state.device)),
+                                     ptr(_len_i32(flush, B, state.device)), ptr(window), ptr(wlen), ptr(emit), K, Tc, B, R, int(mode)),
+          "asr_stream_push")
+    return wlen, emit
+
+
+def stream_push_reset(state, m=None, mask=None):
+    """zero the carried rows (and m) of every slot, or of those with mask[b] != 0"""
+    K, B, R = state.shape
+    check(_lib.lib().asr_stream_push_reset(stream(), ptr(state) if K else None, ptr(m), ptr(_len_i32(mask, B, state.device)), K, B, R),
+          "asr_stream_push_reset")

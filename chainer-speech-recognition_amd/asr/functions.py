@@ -1290,6 +1290,37 @@ def gru(x, w_ih, w_hh, b_ih, b_hh, link, ndir, x_length=None, hx=None):
     return logical3(y.reshape(T, B, H))
 
 
+# ---------------------------------------------------------------------------------------------- lookahead convolution
+class _Lookahead(torch.autograd.Function):
+    """p (T, B, D) bf16, W (D, tau + 1) f32 master -> (T, B, D) bf16: csrc/lookahead.hip.  dW goes straight into W.grad."""
+
+    @staticmethod
+    def forward(ctx, p, W, x_len):
+        ctx.save_for_backward(p)
+        ctx.params = (W, x_len)
+        ctx.need_dx = ctx.needs_input_grad[0]
+        return _ops.lookahead_fwd(p, W.detach(), x_len)
+
+    @staticmethod
+    def backward(ctx, gy):
+        (p,) = ctx.saved_tensors
+        W, x_len = ctx.params
+        gy = gy.contiguous() if gy.dtype == BF16 else _ops.cast_bf16(gy.contiguous().reshape(-1, gy.shape[-1])).reshape(gy.shape)
+        dx = _ops.lookahead_bwd(gy, p, W.detach(), x_len, grad_buffer(W), ctx.need_dx)
+        grads_queued(W)
+        return dx, None, None
+
+
+def lookahead_convolution(x, W, x_length=None):
+    """Deep Speech 2's lookahead (row) convolution: x logical (B, D, T), W (D, tau + 1) float32, no bias:
+    y[b, d, t] = sum_{j=0..tau} W[d, j] x[b, d, t + j], with x = 0 and y = 0 at and beyond x_length[b] ((B) int32 on the device;
+    None = T).  float32 accumulation in the order j = 0..tau, so a frame's value does not depend on where a sequence was cut."""
+    p = phys3(x)
+    if p.shape[2] != W.shape[0]:
+        raise ValueError("lookahead weight of %d features applied to %d" % (W.shape[0], p.shape[2]))
+    return logical3(_Lookahead.apply(p, W, x_length))
+
+
 # ---------------------------------------------------------------------------------------------- array manipulation (views)
 def reshape(x, shape):
     """chainer.functions.reshape.  Merging (C, H) of a physical image -- run/ctc/sru/model.py:114

@@ -6,7 +6,8 @@ conv + recurrent template run/ctc/sru/model.py:10-139 (conv blocks -> reshape (B
 forward (the template drops it, run/ctc/sru/model.py:120-124).  SURVEY.md section 8(d) fixes the sizes:
   conv1 3->2*ndim_conv k(3,5) -> Maxout -> MaxPool(3,1);  conv2 ndim_conv->2*ndim_conv -> Maxout -> MaxPool(2,1);
   num_rnn_layers x BiGRU(ndim_rnn) (directions summed);  Conv1D(->2*dense)+Maxout, Conv1D(dense->2*dense)+Maxout,
-  Conv1D(dense->V), LayerNormalization.
+  Conv1D(dense->V), LayerNormalization.  ``lookahead`` > 0 (with bidirectional=False: the deployable streaming recipe,
+  asr/model/stream.py) puts nn.LookaheadConvolution(ndim_rnn, lookahead) between the recurrent stack and the dense layers.
 """
 from .. import functions, nn
 from .base import NeedsVocabulary
@@ -15,7 +16,7 @@ from ._acoustic import load_if_exists, save_atomic, split_output
 
 class Configuration(NeedsVocabulary):
     FIELDS = dict(ndim_audio_features=3, ndim_conv=64, ndim_rnn=512, ndim_dense=320, num_conv_layers=2, num_rnn_layers=4,
-                  bidirectional=True, kernel_size=(3, 5), dropout=0)
+                  bidirectional=True, kernel_size=(3, 5), dropout=0, lookahead=0)
 
 
 def configure():
@@ -44,6 +45,7 @@ class Model(nn.Module):
             in_ch = config.ndim_conv
         self.conv_blocks = conv_blocks
         height = config.num_mel_filters
+        self._input_height = height         # (asr/model/stream.py sizes the carried rows of the first block from it)
         for pool in pools:          # pad_h = 0 convolution, then cover_all pooling
             height -= kernel_size[0] - 1
             height = 1 if height <= pool else -(-(height - pool) // pool) + 1
@@ -54,6 +56,11 @@ class Model(nn.Module):
         for _ in range(config.num_rnn_layers):
             rnn_blocks.add(rnn_cls(None, config.ndim_rnn), nn.Dropout(dropout))
         self.rnn_blocks = rnn_blocks
+
+        # Deep Speech 2's lookahead convolution between the recurrent stack and the dense layers: `lookahead` future frames for a
+        # forward-only stack.  An attribute of its own -- the _sequential_%d names of the blocks are checkpoint names and stay put.
+        if config.lookahead > 0:
+            self.lookahead = nn.LookaheadConvolution(config.ndim_rnn, config.lookahead)
 
         dense_blocks = nn.Module()
         dense_blocks.add(nn.Convolution1D(None, config.ndim_dense * 2), nn.Maxout(2), nn.Dropout(dropout))
@@ -78,6 +85,8 @@ class Model(nn.Module):
         else:
             for layer in self.rnn_blocks.layers:
                 out_data = layer(out_data, x_length) if isinstance(layer, (nn.GRU, nn.BiGRU)) else layer(out_data)
+        if getattr(self, "lookahead", None) is not None:
+            out_data = self.lookahead(out_data, x_length)
         out_data = self.dense_blocks(out_data)
         assert out_data.shape[2] == seq_length
         return split_output(out_data, batchsize, seq_length, split_into_variables)

@@ -1,0 +1,238 @@
+"""Streaming forward of a causal ``ds2.Model``: features in chunk by chunk, logits out chunk by chunk, all state on the device.
+
+A ``ds2.Model`` with ``bidirectional=False`` is causal end to end: causal convolutions, pooling over height only, forward GRUs,
+per-frame dense layers and LayerNormalization, no subsampling in time.  What has to be carried from one chunk to the next is
+therefore small and local (``stream_plan``): the last kw - 1 input rows of every convolution, the hidden state of every GRU
+layer, and the pending frames of the lookahead convolution, whose ``lookahead`` frames are the stream's delay.  The carry kernels
+are csrc/stream.hip; every other launch is the model's own.  ``(logits, lengths)`` go as they are into
+``asr.error.BeamStream.advance``, ``asr.error.GramBeamStream.advance`` and ``asr.spot.KeywordStream.advance``.
+
+Not covered: the CNN recipes of architectures.py and the SRU template (``stream_plan`` is where they would
+plug in), a chunked log-mel front end (the delta features need +-4 frames of their own), and a backward pass through a stream.
+"""
+import torch
+
+from .. import _ops, functions, nn
+from . import ds2
+
+
+def _pair(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
+def stream_plan(model):
+    """What a stream over `model` carries, layer by layer, from the model's structure alone (no device, no parameters read):
+    {"delay": frames the output lags the input, "layers": [...]} with one entry per carrying layer, in order:
+      {"kind": "context", "K": kw - 1, "R": height * channels of the block's input, "height", "channels", "index": position in
+       conv_blocks.layers}                                       a causal convolution's left context, K rows of R features
+      {"kind": "state", "H": units, "index": position in rnn_blocks.layers}      a GRU layer's hidden state
+      {"kind": "lookahead", "K": lookahead, "R": features}                       the lookahead layer's pending frames
+    ValueError: not a ds2.Model, or a bidirectional one (its reverse recurrences need the whole utterance)."""
+    if not isinstance(model, ds2.Model):
+        raise ValueError("a stream runs a ds2.Model, got %s" % type(model).__name__)
+    layers = []
+    height, channels = model._input_height, None
+    for index, layer in enumerate(model.conv_blocks.layers):
+        if isinstance(layer, nn.PlainConvolution2D):
+            kh, kw = layer.ksize
+            if not layer.causal or layer.pad[1] != kw - 1:
+                raise ValueError("convolution %d is not causal" % index)
+            if channels is None:
+                channels = layer.W.shape[1]
+            layers.append({"kind": "context", "K": kw - 1, "R": height * channels, "height": height, "channels": channels,
+                           "index": index})
+            height, channels = height + 2 * layer.pad[0] - kh + 1, layer.out_channels
+        elif type(layer).__name__ == "Maxout":
+            channels //= layer.pool_size
+        elif type(layer).__name__ == "MaxPooling2D":
+            height = _ops.pooled_height(height, _pair(layer.ksize)[0])
+        elif type(layer).__name__ != "Dropout":
+            raise ValueError("no streaming form of %s" % type(layer).__name__)
+    for index, layer in enumerate(model.rnn_blocks.layers):
+        if isinstance(layer, nn.BiGRU):
+            raise ValueError("a bidirectional model cannot be streamed: its reverse recurrences start at the end of the utterance")
+        if isinstance(layer, nn.GRU):
+            layers.append({"kind": "state", "H": layer.out_size, "index": index})
+    delay = 0
+    look = getattr(model, "lookahead", None)
+    if look is not None:
+        delay = look.lookahead
+        layers.append({"kind": "lookahead", "K": delay, "R": look.W.shape[0]})
+    return {"delay": delay, "layers": layers}
+
+
+class AcousticStream:
+    """``model(x)`` of a causal ``ds2.Model`` fed chunk by chunk, for `B` batch slots that start and end on their own:
+
+        s = AcousticStream(model, B, max_chunk=64)
+        for x, n in chunks:                             # x (B, C, n_mel, Tc) features, n (B): valid frames per slot (0: untouched)
+            logits, lengths = s.advance(x, n)           # (Tc, B, V) f32 left-aligned per slot, (B) int32 on the device
+            beam.advance(logits, lengths)
+        logits, lengths = s.flush(mask)                 # end of utterance of the masked slots: the `delay` frames held back
+
+    ``delay`` is the model's lookahead: a slot's first `delay` frames come out with later chunks or with ``flush``, which feeds
+    the pending frames a zero future (as the one-shot forward does at an utterance's end) and then resets the slots.  ``frames``
+    (B) int32 on the device counts the logit frames a slot has emitted since it was last reset (``flush`` leaves the finished
+    utterance's count standing until the slot is fed again).  Rows of `logits` at or beyond ``lengths[b]`` are unspecified (the
+    epsilon-free LayerNormalization turns a constant row into NaN).  Runs under ``torch.no_grad()``; dropout layers are skipped.
+    Nothing here synchronises with the host."""
+
+    def __init__(self, model, B, max_chunk=64, device=None):
+        self.plan = stream_plan(model)
+        self.model, self.B, self.max_chunk, self.delay = model, int(B), int(max_chunk), self.plan["delay"]
+        if self.B < 1 or self.max_chunk < 1:
+            raise ValueError("B and max_chunk must be positive")
+        if device is None:
+            device = next(model.parameters()).device
+        self.device = dev = torch.device(device)
+        for entry in self.plan["layers"]:
+            if entry["kind"] != "state" and entry["R"] % 8 != 0:
+                raise ValueError("carried rows must be a multiple of 8 features wide, got %d" % entry["R"])
+        self._ctx = [(e, torch.zeros((e["K"], self.B, e["R"]), dtype=_ops.BF16, device=dev),
+                      torch.zeros((e["K"] + self.max_chunk, self.B, e["R"]), dtype=_ops.BF16, device=dev))
+                     for e in self.plan["layers"] if e["kind"] == "context"]
+        self._h = [torch.zeros((1, self.B, e["H"]), dtype=torch.float32, device=dev) for e in self.plan["layers"] if e["kind"] == "state"]
+        self._look = None
+        if self.delay > 0:
+            e = self.plan["layers"][-1]
+            self._look = (torch.zeros((e["K"], self.B, e["R"]), dtype=_ops.BF16, device=dev),
+                          torch.zeros((self.B,), dtype=torch.int32, device=dev),
+                          torch.zeros((e["K"] + self.max_chunk, self.B, e["R"]), dtype=_ops.BF16, device=dev))
+        self.frames = torch.zeros((self.B,), dtype=torch.int32, device=dev)
+        self._ended = torch.zeros((self.B,), dtype=torch.bool, device=dev)       # flushed and not fed since: `frames` is the old count
+        self._ones = torch.ones((self.B,), dtype=torch.int32, device=dev)
+        self._dense = [layer for layer in model.dense_blocks.layers if type(layer).__name__ != "Dropout"]
+        self._vocab = model.dense_blocks.layers[-2].out_channels
+
+    # ---------------------------------------------------------------------------------------------------------------- arguments
+    def _slots(self, values, what):
+        """(B) integers, host or device -> int32 on the device"""
+        values = torch.as_tensor(values).to(self.device, torch.int32).contiguous()
+        if tuple(values.shape) != (self.B,):
+            raise ValueError("%s must have one entry per utterance (%d)" % (what, self.B))
+        return values
+
+    def reset(self, mask=None):
+        """start every slot over, or those with mask[b] != 0 (`mask`: (B) integers, host or device)"""
+        mask = None if mask is None else self._slots(mask, "mask")
+        for _, state, _ in self._ctx:
+            if state.shape[0] > 0:
+                _ops.stream_push_reset(state, None, mask)
+        if self._look is not None:
+            _ops.stream_push_reset(self._look[0], self._look[1], mask)
+        if mask is None:
+            for h in self._h:
+                h.zero_()
+            self.frames.zero_()
+            self._ended.zero_()
+        else:
+            on = mask != 0
+            for h in self._h:
+                h.masked_fill_(on.view(1, self.B, 1), 0)
+            self.frames.masked_fill_(on, 0)
+            self._ended.masked_fill_(on, False)
+
+    def _emitted(self, lengths, fed):
+        """count `lengths` into ``frames``; the slots in `fed` (None: all) that were flushed before start their count over first"""
+        again = self._ended.clone() if fed is None else self._ended & fed
+        self.frames.masked_fill_(again, 0)
+        self._ended.logical_xor_(again)
+        self.frames += lengths
+
+    # ---------------------------------------------------------------------------------------------------------------- the chunk
+    def advance(self, x, x_length=None):
+        """x (B, C, n_mel, Tc) features, Tc <= max_chunk; x_length (B), host or device: the valid frames of this chunk per slot,
+        left-aligned (0: the slot is left exactly as it is), None: all Tc -> (logits (Tc, B, V) f32, lengths (B) int32)"""
+        first = self._ctx[0][0] if self._ctx else None
+        if x.dim() != 4 or x.shape[0] != self.B or (first is not None and tuple(x.shape[1:3]) != (first["channels"], first["height"])):
+            want = ("C", "n_mel") if first is None else (first["channels"], first["height"])
+            raise ValueError("the chunk must be (%d, %s, %s, Tc), got %s" % ((self.B,) + want + (tuple(x.shape),)))
+        Tc = x.shape[3]
+        if Tc > self.max_chunk:
+            raise ValueError("a chunk of %d frames exceeds max_chunk = %d" % (Tc, self.max_chunk))
+        n = None
+        if x_length is not None:
+            on_host = not (isinstance(x_length, torch.Tensor) and x_length.is_cuda)
+            if on_host and torch.as_tensor(x_length).numel() == self.B and int(torch.as_tensor(x_length).max()) > Tc:
+                raise ValueError("x_length exceeds the chunk's %d frames" % Tc)
+            n = self._slots(x_length, "x_length")
+            if not on_host:
+                n = n.clamp(0, Tc)
+        if Tc == 0:
+            return (torch.empty((0, self.B, self._vocab), dtype=torch.float32, device=self.device),
+                    torch.zeros((self.B,), dtype=torch.int32, device=self.device))
+        with torch.no_grad():
+            out = self._conv_blocks(functions.phys4(x.to(self.device)), n, Tc)
+            out = functions.reshape(out, (self.B, -1, Tc))
+            grus = [layer for layer in self.model.rnn_blocks.layers if isinstance(layer, nn.GRU)]
+            for layer, h in zip(grus, self._h):
+                out, hy = layer(out, n, hx=h)
+                h.copy_(hy)                 # (a slot beyond its length keeps its state bit for bit: csrc/gru.hip pins its update gate)
+            lengths = n
+            if self._look is not None:
+                state, m, window = self._look
+                window = window[:self.delay + Tc]
+                wlen, lengths = _ops.stream_push(state, m, functions.phys3(out), n, window, _ops.STREAM_LOOKAHEAD)
+                out = functions.logical3(_ops.lookahead_fwd(window, self.model.lookahead.W.detach(), wlen)[:Tc])
+            logits = self._logits(out)
+            if lengths is None:
+                lengths = torch.full((self.B,), Tc, dtype=torch.int32, device=self.device)
+            elif lengths is n:
+                lengths = n.clone()         # (the caller's own tensor stays the caller's)
+            self._emitted(lengths, None if n is None else n > 0)
+        return logits, lengths
+
+    def _conv_blocks(self, p, n, Tc):
+        """the conv stack on this chunk: p (Tc, B, H, C) physical features -> logical (B, C', H', Tc).  Every convolution runs
+        un-padded in time over [its K carried rows | the chunk], which is the causal convolution of the whole sequence."""
+        layers = self.model.conv_blocks.layers
+        out = None
+        for i, (entry, state, window) in enumerate(self._ctx):
+            K, conv = entry["K"], layers[entry["index"]]
+            window = window[:K + Tc]
+            _ops.stream_push(state, None, p.reshape(Tc, self.B, entry["R"]), n, window, _ops.STREAM_CONTEXT)
+            x = functions.logical4(window.view(K + Tc, self.B, entry["height"], entry["channels"]))
+            stop = self._ctx[i + 1][0]["index"] if i + 1 < len(self._ctx) else len(layers)
+            tail = [layer for layer in layers[entry["index"] + 1:stop] if type(layer).__name__ != "Dropout"]
+            pad = (conv.pad[0], 0)
+            if conv.W.numel() == 0:
+                conv._initialize_params(entry["channels"])
+            y = None
+            j = nn.nn._fusable_pool(tail, 0) if tail else -1
+            if j > 0 and not conv.output_float32:
+                ks = _pair(tail[j].ksize)[0]
+                y = functions.convolution_maxout_pool(x, conv.W, conv.b, conv, pad, False, ks)
+                if y is not None:
+                    tail = tail[j + 1:]
+            if y is None:
+                y = functions.convolution_2d(x, conv.W, conv.b, conv, pad, False, conv.output_float32)
+            out = nn.nn._apply_layers(tail, y)
+            p = functions.phys4(out)
+        return out
+
+    def _logits(self, out):
+        """dense blocks and the per-frame LayerNormalization on (B, D, To) -> (To, B, V) float32"""
+        out = nn.nn._apply_layers(self._dense, out)
+        return out.permute(2, 0, 1).to(torch.float32).contiguous()
+
+    def flush(self, mask=None):
+        """end of utterance for every slot, or those with mask[b] != 0: -> (logits (delay, B, V), lengths (B)) with the frames the
+        lookahead held back, computed with a zero future; then these slots are reset (``frames`` keeps the finished count until
+        the slot is fed again)"""
+        mask = self._ones if mask is None else self._slots(mask, "mask")
+        if self._look is None:
+            logits = torch.empty((0, self.B, self._vocab), dtype=torch.float32, device=self.device)
+            lengths = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
+        else:
+            with torch.no_grad():
+                state, m, window = self._look
+                window = window[:self.delay]
+                wlen, lengths = _ops.stream_push(state, m, None, None, window, _ops.STREAM_LOOKAHEAD, flush=mask)
+                out = functions.logical3(_ops.lookahead_fwd(window, self.model.lookahead.W.detach(), wlen))
+                logits = self._logits(out)
+        count = self.frames + lengths
+        self.reset(mask)
+        on = mask != 0
+        self.frames.copy_(torch.where(on, count, self.frames))
+        self._ended.logical_or_(on)
+        return logits, lengths

@@ -16,6 +16,7 @@ from .convolution_2d import Convolution2D as WeightnormConvolution2D
 from .convolution_2d import PlainConvolution2D
 from .gru import GRU, NStepBiGRU, NStepGRU, BiGRU  # noqa: F401
 from .layernorm import normalize_layer  # noqa: F401
+from .lookahead import LookaheadConvolution  # noqa: F401
 from .sru import SRU  # noqa: F401
 
 

@@ -1042,6 +1042,40 @@ int asr_spp_bins(int pyramid_height);
 int asr_spp_fwd(void* stream, const void* x, void* y, int* pos, int T, int B, int H, int C, int pyramid_height);
 int asr_spp_bwd(void* stream, const void* dy, const int* pos, float* dx32, int T, int B, int H, int C, int pyramid_height);
 
+/* ---------------------------------------------------------------------------------------- lookahead (row) convolution
+ * Deep Speech 2's lookahead layer on (T, B, D) 16-bit activations; w (D, tau + 1) float32, no bias; x_len (B) int32 or NULL (= T):
+ *   y[t, b, d]  = sum_{j=0..tau} w[d, j] * x[t + j, b, d]     with x = 0 at t + j >= x_len[b];  y = 0 at t >= x_len[b]
+ *   dx[t, b, d] = sum_{j=0..tau} w[d, j] * gy[t - j, b, d]    gy at and beyond x_len[b] is ignored; dx = 0 at t >= x_len[b]
+ *   dW[d, j]   += sum_{t, b} gy[t, b, d] * x[t + j, b, d]     over t + j < x_len[b]
+ * float32 accumulation in a fixed tap order (forward j = 0..tau), one rounding at the store: an output element does not depend on T,
+ * on the time tile (ASR_LOOKAHEAD_TIME_TILE rows) it fell into or on where a longer sequence was cut.  dW is summed in two stages
+ * (per-workgroup partial sums in `ws`, asr_lookahead_ws_bytes; then one ordered sum added once to dW): no float atomics, the same
+ * bits on every run.  asr_lookahead_bwd: dx_bf16 NULL = no input gradient, dW NULL = no weight gradient (then x_bf16 and ws may be
+ * NULL).  Limits: D % 8 == 0 and tau <= ASR_LOOKAHEAD_MAX_TAU, else ASR_ERR_UNSUPPORTED (nothing is written; _ws_bytes returns 0). */
+#define ASR_LOOKAHEAD_MAX_TAU 96
+#define ASR_LOOKAHEAD_TIME_TILE 64
+size_t asr_lookahead_ws_bytes(int T, int B, int D, int tau);
+int asr_lookahead_fwd(void* stream, const void* x_bf16, const float* w, const int* x_len, void* y_bf16, int T, int B, int D, int tau);
+int asr_lookahead_bwd(void* stream, const void* gy_bf16, const void* x_bf16, const float* w, const int* x_len, void* dx_bf16,
+                      float* dW, void* ws, size_t ws_bytes, int T, int B, int D, int tau);
+
+/* ---------------------------------------------------------------------------------------- carried rows of a streaming forward
+ * A delay line of K rows of R 16-bit features per batch slot: state (K, B, R), of which the first m[b] <= K rows are valid.
+ * asr_stream_push takes a chunk (Tc, B, R) of which n[b] rows are valid (n NULL = all Tc) and writes, per slot b,
+ *   window (K + Tc, B, R): [m[b] carried rows | n[b] new rows | zeros], left-aligned;  wlen[b] = m[b] + n[b];
+ *   emit[b]: the rows the layer behind the window may emit;  the new state: the last min(K, wlen[b]) valid rows, and m[b].
+ * mode ASR_STREAM_CONTEXT (the left context of a causal convolution): m == K always (the argument m is not read; a reset slot
+ * holds K zero rows that count as valid) and emit[b] = n[b].  mode ASR_STREAM_LOOKAHEAD (the pending frames of a lookahead layer):
+ * emit[b] = max(0, m[b] + n[b] - K).  A slot with n[b] == 0 keeps its state bytes.  flush (B) int32 or NULL, lookahead mode only --
+ * the end of utterances: no slot is fed (chunk may be NULL, Tc 0), emit[b] = m[b] where flush[b] != 0 (0 elsewhere) and those
+ * slots are then emptied.  asr_stream_push_reset zeroes the rows of every slot, or of those with mask[b] != 0, and sets m[b] = 0
+ * (m NULL: context mode).  Bit-exact copies.  R % 8 == 0, else ASR_ERR_UNSUPPORTED. */
+#define ASR_STREAM_CONTEXT 0
+#define ASR_STREAM_LOOKAHEAD 1
+int asr_stream_push(void* stream, void* state, int* m, const void* chunk, const int* n, const int* flush, void* window, int* wlen,
+                    int* emit, int K, int Tc, int B, int R, int mode);
+int asr_stream_push_reset(void* stream, void* state, int* m, const int* mask, int K, int B, int R);
+
 #ifdef __cplusplus
 }
 #endif
