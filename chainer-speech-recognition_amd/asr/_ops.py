@@ -1599,3 +1599,43 @@ def stream_push_reset(state, m=None, mask=None):
     K, B, R = state.shape
     check(_lib.lib().asr_stream_push_reset(stream(), ptr(state) if K else None, ptr(m), ptr(_len_i32(mask, B, state.device)), K, B, R),
           "asr_stream_push_reset")
+
+
+# ---------------------------------------------------------------------------------------------- streaming log-mel front end
+FBANK_STREAM_MAX_FRAMES = 128   # ASR_FBANK_STREAM_MAX_FRAMES, ASR_FBANK_STREAM_MAX_FILT and ASR_FBANK_STREAM_META of include/asr_hip.h
+FBANK_STREAM_MAX_FILT = 64
+FBANK_STREAM_META = 8
+
+
+def fbank_stream_push(chunk, n, flush, pend, last, meta, window, wlen, k, frame_len, frame_step, preemph):
+    """asr_fbank_stream_push: chunk (B, Nc) int16 / float32 or None (a flush), n / flush (B) int32 or None; pend (B, >= L) f32, last (B)
+    f32 and meta (B, 8) int32 are the slots' state (updated); window (B, pitch) f32, wlen and k (B) int32 are written"""
+    B = meta.shape[0]
+    Nc = 0 if chunk is None else chunk.shape[1]
+    if chunk is not None and chunk.dtype not in (F32, torch.int16):
+        raise ValueError("samples must be int16 or float32, got %s" % chunk.dtype)
+    assert chunk is None or (chunk.dim() == 2 and chunk.shape[0] == B and chunk.stride(1) == 1)
+    assert pend.dtype == F32 and last.dtype == F32 and window.dtype == F32 and window.stride(1) == 1 and pend.stride(1) == 1
+    assert meta.dtype == torch.int32 and tuple(meta.shape) == (B, FBANK_STREAM_META) and wlen.dtype == torch.int32 and k.dtype == torch.int32
+    dev = meta.device
+    check(_lib.lib().asr_fbank_stream_push(stream(), chunk.data_ptr() if Nc else None, 1 if chunk is not None and chunk.dtype == F32 else 0,
+                                           chunk.stride(0) if Nc else 0, Nc, ptr(_len_i32(n, B, dev)), ptr(_len_i32(flush, B, dev)),
+                                           pend.data_ptr(), pend.stride(0), ptr(last), ptr(meta), window.data_ptr(), window.stride(0),
+                                           ptr(wlen), ptr(k), B, int(frame_len), int(frame_step), float(preemph)), "asr_fbank_stream_push")
+
+
+def fbank_stream_deltas(logmel, k, flush, meta, out, lengths, mean=None, std=None):
+    """asr_fbank_stream_deltas: logmel (B, Fmax, nfilt) f32 (rows 0..3 of a slot: carried, updated; rows 4..: this call's), k / flush (B)
+    int32, meta (B, 8) int32 (updated); out (B, 3, nfilt, Tc) f32 and lengths (B) int32 are written"""
+    B, Fmax, nfilt = logmel.shape
+    Tc = out.shape[3]
+    assert logmel.dtype == F32 and out.dtype == F32 and tuple(out.shape) == (B, 3, nfilt, Tc) and lengths.dtype == torch.int32
+    dev = meta.device
+    check(_lib.lib().asr_fbank_stream_deltas(stream(), ptr(logmel), ptr(_len_i32(k, B, dev)), ptr(_len_i32(flush, B, dev)), ptr(meta), B, Fmax,
+                                             nfilt, Tc, ptr(mean), ptr(std), ptr(out), ptr(lengths)), "asr_fbank_stream_deltas")
+
+
+def fbank_stream_reset(meta, mask=None):
+    """empty every slot of a feature stream, or those with mask[b] != 0"""
+    B = meta.shape[0]
+    check(_lib.lib().asr_fbank_stream_reset(stream(), ptr(meta), ptr(_len_i32(mask, B, meta.device)), B), "asr_fbank_stream_reset")

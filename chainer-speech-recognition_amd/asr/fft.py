@@ -237,3 +237,154 @@ class Processor(object):
         x = _deltas(logmel, nfr, Tmax, m, s)
         x_length = meta[2] if warp is None else torch.tensor([max(f - 2, 0) for f in frames], dtype=torch.int32, device=dev)
         return x, x_length
+
+    def _constants(self):
+        """window, filterbank and its band table on the device, once per Processor"""
+        if self._window_d is None:
+            self._window_d, self._fbank_d = _dev_const(self.window, self.device), _dev_const(self.fbank, self.device)
+            self._bands_d = mel_bands(self._fbank_d)
+        return self._window_d, self._fbank_d, self._bands_d
+
+
+def stream_frames(n_samples, frame_step):
+    """the feature frames a chunk of `n_samples` can complete at most: 1 + (n - 1) // frame_step, 0 for an empty chunk"""
+    return 1 + (int(n_samples) - 1) // int(frame_step) if n_samples > 0 else 0
+
+
+class FeatureStream(object):
+    """``Processor.logfbank_batch`` fed chunk by chunk, for `B` batch slots that start and end on their own:
+
+        fs = FeatureStream(processor, B, max_samples=2560, mean=mean, std=std)
+        for samples, n in chunks:                       # samples (B, Nc) int16 or float32, n (B): new samples per slot (0: untouched)
+            x, lengths = fs.advance(samples, n)         # (B, 3, n_mel, Tc) f32 left-aligned per slot, (B) int32 on the device
+            logits, out = acoustic.advance(x, lengths)  # asr.model.stream.AcousticStream, max_chunk >= fs.max_frames
+        x, lengths = fs.flush(mask)                     # end of utterance of the masked slots: their last 0 or 1 frame, then a reset
+
+    The valid columns of all ``advance`` calls and the ``flush`` of an utterance, concatenated, are bit for bit
+    ``logfbank_batch(signal, mean, std)[0][b, :, :, :x_length[b]]`` of the whole signal, however it was cut (include/asr_hip.h states the
+    recurrence; csrc/fbank_stream.hip).  Columns at or beyond ``lengths[b]`` hold the one-shot's padding: 0, or (0 - mean) / std.
+    ``Tc = 1 + (Nc - 1) // frame_step`` follows from the chunk's shape alone; ``max_frames`` is the same for `max_samples`.
+    ``delay_samples = frame_len + 2 * frame_step``: feature frame t is out once sample (t + 2) * frame_step + frame_len - 1 is in.
+    ``frames`` (B) int32 on the device counts the feature frames a slot has emitted since its last reset (``flush`` leaves the finished
+    utterance's count standing until the slot is fed again).  The stream uses the Processor's window, filterbank, band table, frame
+    sizes and device; `noise`, `apply_cmn` and `warp` of the one-shot path are not streamable (CMN is a whole-utterance mean) and not
+    offered.  State and work buffers are allocated here, once; nothing synchronises with the host."""
+
+    PREEMPH = 0.97      # the coefficient of Processor.logfbank_batch
+
+    def __init__(self, processor, B, max_samples, mean=None, std=None):
+        ops = _ops_mod()
+        self.processor, self.B, self.max_samples = processor, int(B), int(max_samples)
+        self.frame_len, self.frame_step, self.n_mel = processor.frame_len, processor.frame_step, processor.num_mel_filters
+        if self.B < 1 or self.max_samples < 1:
+            raise ValueError("B and max_samples must be positive")
+        if self.frame_step > self.frame_len:
+            raise ValueError("frames that do not overlap or touch (step %d > length %d) have no streaming form here" % (self.frame_step, self.frame_len))
+        self.max_frames = stream_frames(self.max_samples, self.frame_step)
+        self.delay_samples = self.frame_len + 2 * self.frame_step
+        if self.max_frames > ops.FBANK_STREAM_MAX_FRAMES:
+            raise ValueError("max_samples = %d is %d frames a chunk; the limit is %d (%d samples)"
+                             % (self.max_samples, self.max_frames, ops.FBANK_STREAM_MAX_FRAMES, ops.FBANK_STREAM_MAX_FRAMES * self.frame_step))
+        if self.n_mel > ops.FBANK_STREAM_MAX_FILT:
+            raise ValueError("%d mel filters; the stream serves at most %d" % (self.n_mel, ops.FBANK_STREAM_MAX_FILT))
+        if (mean is None) != (std is None):
+            raise ValueError("mean and std come together")
+        self.device = dev = processor.device
+        self._window_d, self._fbank_d, self._bands_d = processor._constants()
+        self._mean, self._std = (None, None) if mean is None else (self._stat(mean, "mean"), self._stat(std, "std"))
+        L = self.frame_len
+        self._win_pitch = (L - 1 + self.max_samples + 3) // 4 * 4 + 4          # rows of 4 n floats: the four-sample loads of asr_specgram
+        self._Fmax = 4 + self.max_frames
+        # the slots' state ...
+        self._pend = self._alloc((self.B, (L + 3) // 4 * 4), F32)
+        self._last = self._alloc((self.B,), F32)
+        self._meta = self._alloc((self.B, ops.FBANK_STREAM_META), torch.int32)
+        self._logmel = self._alloc((self.B, self._Fmax, self.n_mel), F32)       # rows 0..3 of a slot: carried; 4..: the call's new rows
+        # ... and what one call hands to the next launch
+        self._window = self._alloc((self.B, self._win_pitch), F32)
+        self._wlen = self._alloc((self.B,), torch.int32)
+        self._k = self._alloc((self.B,), torch.int32)
+        self._ones = torch.ones((self.B,), dtype=torch.int32, device=dev)
+        self._new_rows = self._logmel.data_ptr() + 4 * self.n_mel * 4
+        self.reset()
+
+    def _alloc(self, shape, dtype):
+        return torch.zeros(shape, dtype=dtype, device=self.device)
+
+    def _stat(self, v, what):
+        v = v if isinstance(v, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(v))
+        v = v.to(self.device, F32).reshape(-1).contiguous()
+        if v.numel() != 3 * self.n_mel:
+            raise ValueError("%s must hold 3 x %d values, got %d" % (what, self.n_mel, v.numel()))
+        return v
+
+    @property
+    def frames(self):
+        return self._meta[:, 3]
+
+    def state(self):
+        """the tensors that carry a slot from one call to the next (views, not copies): pending samples, last raw sample, counters,
+        the four carried log-mel rows"""
+        return {"pend": self._pend, "last": self._last, "meta": self._meta, "rows": self._logmel[:, :4]}
+
+    def _slots(self, values, what):
+        """(B) integers, host or device -> int32 on the device"""
+        values = torch.as_tensor(values).to(self.device, torch.int32).contiguous()
+        if tuple(values.shape) != (self.B,):
+            raise ValueError("%s must have one entry per slot (%d)" % (what, self.B))
+        return values
+
+    def reset(self, mask=None):
+        """start every slot over, or those with mask[b] != 0 (`mask`: (B) integers, host or device)"""
+        _ops_mod().fbank_stream_reset(self._meta, None if mask is None else self._slots(mask, "mask"))
+
+    def _run(self, samples, n, flush, Tc, out):
+        ops = _ops_mod()
+        if out is None:
+            out = torch.empty((self.B, 3, self.n_mel, Tc), dtype=F32, device=self.device)
+        elif tuple(out.shape) != (self.B, 3, self.n_mel, Tc) or out.dtype != F32 or out.device != self.device or not out.is_contiguous():
+            raise ValueError("out must be a contiguous (%d, 3, %d, %d) float32 tensor on %s" % (self.B, self.n_mel, Tc, self.device))
+        lengths = torch.empty((self.B,), dtype=torch.int32, device=self.device)
+        ops.fbank_stream_push(samples, n, flush, self._pend, self._last, self._meta, self._window, self._wlen, self._k, self.frame_len,
+                              self.frame_step, self.PREEMPH)
+        p = self.processor
+        rc = _lib.lib().asr_specgram_bands(stream(), self._window.data_ptr(), 1, ptr(self._wlen), self._win_pitch, self.B, self.frame_len,
+                                           self.frame_step, p.num_fft, 0.0, ptr(self._window_d), ptr(self._k), self._Fmax, None,
+                                           ptr(self._fbank_d), self.n_mel, self._new_rows, ptr(self._bands_d))
+        check(rc, "asr_specgram_bands")
+        ops.fbank_stream_deltas(self._logmel, self._k, flush, self._meta, out, lengths, self._mean, self._std)
+        return out, lengths
+
+    def advance(self, samples, n=None, out=None):
+        """samples (B, Nc) int16 or float32, Nc <= max_samples; n (B), host or device: the new samples per slot, left-aligned (0: the
+        slot is left exactly as it is), None: all Nc.  A device `n` is clamped to [0, Nc]; a host `n` above Nc raises.
+        -> (x (B, 3, n_mel, Tc) float32, lengths (B) int32 on the device), Tc = 1 + (Nc - 1) // frame_step (0 for Nc = 0).
+        `out`: a (B, 3, n_mel, Tc) float32 tensor to write x into instead of a new one."""
+        if not isinstance(samples, torch.Tensor) or samples.dim() != 2 or samples.shape[0] != self.B:
+            raise ValueError("the chunk must be a (%d, Nc) tensor, got %s" % (self.B, tuple(getattr(samples, "shape", ()))))
+        if samples.dtype not in (torch.int16, F32):
+            raise ValueError("samples must be int16 or float32, got %s" % samples.dtype)
+        Nc = samples.shape[1]
+        if Nc > self.max_samples:
+            raise ValueError("a chunk of %d samples exceeds max_samples = %d" % (Nc, self.max_samples))
+        if n is not None:
+            on_host = not (isinstance(n, torch.Tensor) and n.is_cuda)
+            if on_host and torch.as_tensor(n).numel() == self.B and int(torch.as_tensor(n).max()) > Nc:
+                raise ValueError("n exceeds the chunk's %d samples" % Nc)
+            n = self._slots(n, "n")
+        Tc = stream_frames(Nc, self.frame_step)
+        if Tc == 0:
+            return (torch.empty((self.B, 3, self.n_mel, 0), dtype=F32, device=self.device) if out is None else out,
+                    torch.zeros((self.B,), dtype=torch.int32, device=self.device))
+        samples = samples.to(self.device)
+        if samples.stride(1) != 1:
+            samples = samples.contiguous()
+        return self._run(samples, n, None, Tc, out)
+
+    def flush(self, mask=None, out=None):
+        """end of utterance for every slot, or those with mask[b] != 0: -> (x (B, 3, n_mel, 1), lengths (B)) with the slot's last 0 or
+        1 feature frame (the pending samples make the zero-padded last frame of the one-shot framing where it has one); after it a
+        slot has emitted max(F - 2, 0) frames in all, the one-shot's x_length.  Then these slots are reset (``frames`` keeps the
+        finished count until the slot is fed again)."""
+        mask = self._ones if mask is None else self._slots(mask, "mask")
+        return self._run(None, None, mask, 1, out)

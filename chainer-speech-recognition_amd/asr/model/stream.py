@@ -7,8 +7,11 @@ layer, and the pending frames of the lookahead convolution, whose ``lookahead`` 
 are csrc/stream.hip; every other launch is the model's own.  ``(logits, lengths)`` go as they are into
 ``asr.error.BeamStream.advance``, ``asr.error.GramBeamStream.advance`` and ``asr.spot.KeywordStream.advance``.
 
+The features come chunk by chunk from ``asr.fft.FeatureStream``: its ``(x, lengths)`` go as they are into
+``advance``, with ``max_chunk >= FeatureStream.max_frames``.
+
 Not covered: the CNN recipes of architectures.py and the SRU template (``stream_plan`` is where they would
-plug in), a chunked log-mel front end (the delta features need +-4 frames of their own), and a backward pass through a stream.
+plug in), and a backward pass through a stream.
 """
 import torch
 

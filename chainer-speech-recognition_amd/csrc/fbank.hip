@@ -21,6 +21,7 @@
 // writes 64 consecutive frames of one (channel, mel) row of the reference's (B, 3, nmel, Tmax) float32 minibatch (zero padded beyond each
 // utterance's length, asr/data/processing.py:124).
 #include "common.hpp"
+#include "fbank_preemph.hpp"
 #include "../../include/asr_hip.h"
 
 namespace asr {
@@ -50,14 +51,7 @@ __device__ __forceinline__ float log_rounded_once(float v) {
     return (float)fma((double)e, 0.6931471805599453, fma(s * z, p, 2.0 * s));
 }
 
-// y[n] = x[n] - c x[n - 1] with the coefficient to float64 precision, as its float32 head and tail in two fused multiply-adds: on a slowly
-// varying signal the difference is a small fraction of its terms (1/32 of them on a constant), and the rounding of 0.97 to float32 (3e-8)
-// alone then put 1e-6 on every sample -- 2e-6 on the power spectrum of a constant, fifty times what float32 arithmetic costs there
-// (tests/test_fbank_edges_gpu.py: dc)
-__device__ __forceinline__ float preemphasised(float x, float prev, double c) {
-    const float hi = (float)c, lo = (float)(c - (double)hi);
-    return fmaf(-lo, prev, fmaf(-hi, prev, x));
-}
+// preemphasised(x, prev, c): y[n] = x[n] - c x[n - 1], in fbank_preemph.hpp (the streaming front end forms its samples with it too)
 
 template <typename SigT>
 __global__ __launch_bounds__(256) void specgram_kernel(const SigT* __restrict__ signals, const int* __restrict__ lengths,

@@ -1076,6 +1076,54 @@ int asr_stream_push(void* stream, void* state, int* m, const void* chunk, const 
                     int* emit, int K, int Tc, int B, int R, int mode);
 int asr_stream_push_reset(void* stream, void* state, int* m, const int* mask, int K, int B, int R);
 
+/* ---------------------------------------------------------------------------------------- streaming log-mel front end
+ * Samples in chunk by chunk, feature frames out, for B batch slots that start and end on their own: for every way of cutting a
+ * signal the emitted frames are, bit for bit, those of asr_specgram_bands + asr_deltas on the whole signal (L = frame_len,
+ * S = frame_step <= L, c = preemph).  Log-mel frame f depends on samples [f S - 1, f S + L); feature frame t (static, delta,
+ * delta-delta) on log-mel frames t - 2 .. t + 2, clamped at 0 on the left; the right-edge clamp of the one-shot deltas never reaches
+ * an emitted frame (the last two frames are dropped).  Feature frame t is therefore out once sample (t + 2) S + L - 1 is in.
+ * State per slot b (the caller owns the buffers; reset or zero-filled state is an empty slot):
+ *   pend (B, pend_pitch >= L) float32   the pre-emphasised samples of frames not yet complete, meta[b][0] = m[b] < L of them
+ *   last (B) float32                    the last raw sample: the predecessor of the next chunk's first sample (valid: meta[b][1])
+ *   logmel (B, Fmax, nfilt) float32     rows [4 - r[b], 4) of a slot: its last r[b] = min(4, meta[b][2]) log-mel rows
+ *   meta (B, ASR_FBANK_STREAM_META) int32: {m, a predecessor exists, log-mel frames so far, feature frames emitted since the reset,
+ *                                       ended: flushed and not fed since, 0, 0, 0}
+ * asr_fbank_stream_push, chunk (B rows of chunk_pitch >= Nc samples, int16 or float32), n (B) int32 or NULL (= Nc), clamped to [0, Nc]:
+ *   1. y[i] = x[i] - c x[i - 1] with the instructions of the one-shot kernels; the predecessor of the chunk's first sample is `last`;
+ *      y = x for the first sample after a reset.
+ *   2. window row b = [m pending | n new | zeros up to four past a multiple of 4], wlen[b] = m + n; the complete frames in it:
+ *      k[b] = 0 if wlen < L, else 1 + (wlen - L) / S; the new pending part is window[k S : wlen], always shorter than L.
+ *   3. (the caller) asr_specgram_bands(window, sig_is_f32 = 1, lengths = wlen, sig_pitch = win_pitch, preemph = 0.0, nframes = k,
+ *      Fmax, logmel_out = logmel + 4 * nfilt): with a zero coefficient the samples pass unchanged, so every frame goes through the
+ *      one-shot transform, mel and logarithm code on the same float32 inputs; the k new rows land behind the slot's 4 carried rows.
+ *      win_pitch % 4 == 0 and a 16-byte aligned window keep the nfft = 512 kernel selected whenever the one-shot call selects it.
+ *   A slot with n[b] == 0 keeps every byte of its state (wlen[b] = m, k[b] = 0).
+ *   flush (B) int32, non-NULL = end of utterance for the slots with flush[b] != 0 (chunk NULL, Nc 0): wlen[b] = m and k[b] = 1 iff the
+ *   slot has no log-mel frame yet or m > L - S -- the one zero-padded frame framesig adds: F - (complete frames), F = 1 + ceil((N - L) / S)
+ *   or 1 for N <= L -- and the slot's samples are dropped; other slots: k[b] = 0, state kept.
+ * asr_fbank_stream_deltas, after step 3, with c the log-mel frames before the call and c' = c + k[b]:
+ *   4. out (B, 3, nfilt, Tc) float32, left-aligned: columns 0 .. lengths[b] - 1 are feature frames max(0, c - 2) .. max(0, c' - 2) - 1
+ *      from [carried rows | new rows]: at(q) = lm[max(q, 0)], dl(q) = (at(max(q, 0) + 1) - at(max(q, 0) - 1)) * 0.5,
+ *      v0 = at(t), v1 = dl(t), v2 = (dl(t + 1) - dl(t - 1)) * 0.5, then (v - mean) / std if mean and stdv (3 * nfilt each) are given;
+ *      columns at or beyond lengths[b] hold the one-shot's padding: 0, or (0 - mean) / std.  The last min(4, c') rows are carried and
+ *      the counters advance.  With flush non-NULL the flushed slots emit their last 0 or 1 frame -- max(F - 2, 0) in all, the one-shot's
+ *      x_length -- and start over; their feature-frame count stands (ended = 1) until asr_fbank_stream_push feeds the slot again.
+ * asr_fbank_stream_reset empties every slot, or those with mask[b] != 0.
+ * Limits, checked before any launch: nfilt <= ASR_FBANK_STREAM_MAX_FILT; at most ASR_FBANK_STREAM_MAX_FRAMES new frames per call
+ * (1 + (Nc - 1) / S and Tc; (4 + 128) rows of 65 floats = 34 KB of LDS); S <= L <= 1024 as in asr_specgram: else ASR_ERR_UNSUPPORTED.
+ * pend_pitch < L, win_pitch < (L - 1 + Nc rounded up to 4) + 4, win_pitch % 4 != 0 or a window off 16 bytes: ASR_ERR_WORKSPACE.  NULL
+ * or non-positive arguments: ASR_ERR_BAD_ARG.  One workgroup per slot: no launch reads what another workgroup of it writes.  Nothing is
+ * allocated, copied to the host or synchronised. */
+#define ASR_FBANK_STREAM_MAX_FRAMES 128
+#define ASR_FBANK_STREAM_MAX_FILT 64
+#define ASR_FBANK_STREAM_META 8
+int asr_fbank_stream_push(void* stream, const void* chunk, int chunk_is_f32, long long chunk_pitch, int Nc, const int32_t* n,
+                          const int32_t* flush, float* pend, int pend_pitch, float* last, int32_t* meta, float* window,
+                          long long win_pitch, int32_t* wlen, int32_t* k, int B, int frame_len, int frame_step, double preemph);
+int asr_fbank_stream_deltas(void* stream, float* logmel, const int32_t* k, const int32_t* flush, int32_t* meta, int B, int Fmax,
+                            int nfilt, int Tc, const float* mean, const float* stdv, float* out, int32_t* lengths);
+int asr_fbank_stream_reset(void* stream, int32_t* meta, const int32_t* mask, int B);
+
 #ifdef __cplusplus
 }
 #endif
