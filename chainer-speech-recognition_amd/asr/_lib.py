@@ -241,6 +241,10 @@ SIGNATURES = {
     "asr_lookahead_bwd": (c_int, [c_void_p] * 8 + [c_size_t] + [c_int] * 4),
     "asr_stream_push": (c_int, [c_void_p] * 9 + [c_int] * 5),
     "asr_stream_push_reset": (c_int, [c_void_p] * 4 + [c_int] * 3),
+    "asr_time_stack_fwd": (c_int, [c_void_p] * 5 + [c_int] * 4),
+    "asr_time_stack_bwd": (c_int, [c_void_p] * 4 + [c_int] * 4),
+    "asr_time_stack_push": (c_int, [c_void_p] * 8 + [c_int] * 4),
+    "asr_time_stack_push_reset": (c_int, [c_void_p] * 4 + [c_int] * 3),
     "asr_fbank_stream_push": (c_int, [c_void_p, c_void_p, c_int, c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                       c_void_p, c_longlong, c_void_p, c_void_p, c_int, c_int, c_int, c_double]),
     "asr_fbank_stream_deltas": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p] * 4),

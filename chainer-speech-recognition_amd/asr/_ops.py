@@ -1601,6 +1601,65 @@ def stream_push_reset(state, m=None, mask=None):
           "asr_stream_push_reset")
 
 
+# ---------------------------------------------------------------------------------------------- time reduction by frame stacking
+TIME_STACK_MAX = 8              # ASR_TIME_STACK_MAX of include/asr_hip.h
+
+
+def _stack_args(x, what):
+    if x.element_size() != 2 or x.dim() != 3 or not x.is_contiguous():
+        raise ValueError("expected contiguous 16-bit %s, got %s %s" % (what, x.dtype, tuple(x.shape)))
+    return x.shape
+
+
+def time_stack_fwd(x, k, x_len=None, want_len=True):
+    """asr_time_stack_fwd: x (T, B, R) 16-bit, x_len (B) int32 or None -> (y (ceil(T / k), B, k * R), y_len (B) int32 or None):
+    y[g, b, j * R + r] = x[g * k + j, b, r] below x_len[b], zero elsewhere; y_len = ceil(x_len / k) (None if not `want_len`)"""
+    T, B, R = _stack_args(x, "(T, B, R) activations")
+    k = int(k)
+    y = torch.empty((-(-T // k) if k > 0 else 0, B, k * R), dtype=x.dtype, device=x.device)
+    y_len = torch.empty((B,), dtype=torch.int32, device=x.device) if want_len else None
+    check(_lib.lib().asr_time_stack_fwd(stream(), ptr(x), ptr(_len_i32(x_len, B, x.device)), ptr(y), ptr(y_len), T, B, R, k),
+          "asr_time_stack_fwd")
+    return y, y_len
+
+
+def time_stack_bwd(gy, k, T, x_len=None, out=None):
+    """asr_time_stack_bwd: gy (ceil(T / k), B, k * R) -> dx (T, B, R), every element written (zero at and beyond x_len[b])"""
+    G, B, KR = _stack_args(gy, "(G, B, k * R) gradients")
+    k, T = int(k), int(T)
+    if k < 1 or KR % k != 0 or G != -(-T // k):
+        raise ValueError("gy %s is not the stacked form of %d frames at k = %d" % (tuple(gy.shape), T, k))
+    dx = torch.empty((T, B, KR // k), dtype=gy.dtype, device=gy.device) if out is None else out
+    assert dx.dtype == gy.dtype and tuple(dx.shape) == (T, B, KR // k) and dx.is_contiguous()
+    check(_lib.lib().asr_time_stack_bwd(stream(), ptr(gy), ptr(_len_i32(x_len, B, gy.device)), ptr(dx), T, B, KR // k, k),
+          "asr_time_stack_bwd")
+    return dx
+
+
+def time_stack_push(state, m, chunk, n, y, k, flush=None):
+    """asr_time_stack_push: state (k - 1, B, R) 16-bit pending rows and m (B) int32 their counts (both updated), chunk (Tc, B, R) or
+    None (a flush), n (B) int32 or None, y (ceil((k - 1 + Tc) / k), B, k * R) (written: the groups of [pending | new], the trailing
+    partial one zero-completed) -> emit (B) int32, the whole groups in y"""
+    K, B, R = state.shape
+    k = int(k)
+    Tc = 0 if chunk is None else chunk.shape[0]
+    assert K == k - 1 and state.element_size() == 2 and y.dtype == state.dtype and tuple(y.shape) == (-(-(K + Tc) // k), B, k * R)
+    assert chunk is None or (chunk.dtype == state.dtype and tuple(chunk.shape[1:]) == (B, R))
+    assert m is None or (m.dtype == torch.int32 and m.numel() == B)
+    emit = torch.empty((B,), dtype=torch.int32, device=state.device)
+    check(_lib.lib().asr_time_stack_push(stream(), ptr(state) if K else None, ptr(m), ptr(chunk) if Tc else None,
+                                         ptr(_len_i32(n, B, state.device)), ptr(_len_i32(flush, B, state.device)),
+                                         ptr(y) if y.numel() else None, ptr(emit), Tc, B, R, k), "asr_time_stack_push")
+    return emit
+
+
+def time_stack_push_reset(state, m=None, mask=None):
+    """zero the pending rows (and m) of every slot, or of those with mask[b] != 0; state (k - 1, B, R)"""
+    K, B, R = state.shape
+    check(_lib.lib().asr_time_stack_push_reset(stream(), ptr(state) if K else None, ptr(m), ptr(_len_i32(mask, B, state.device)), B, R, K + 1),
+          "asr_time_stack_push_reset")
+
+
 # ---------------------------------------------------------------------------------------------- streaming log-mel front end
 FBANK_STREAM_MAX_FRAMES = 128   # ASR_FBANK_STREAM_MAX_FRAMES, ASR_FBANK_STREAM_MAX_FILT and ASR_FBANK_STREAM_META of include/asr_hip.h
 FBANK_STREAM_MAX_FILT = 64

@@ -71,10 +71,15 @@ class Processor(fft.Processor):
         sentences = [sentences[i] for i in keep]        # (the reference also forces katakana here: jaconv.hira2kata, :106)
         return DeviceFeatures(x, lengths), sentences, max(lengths), max(len(s) for _, s in batch)
 
-    def features_to_minibatch(self, features, sentences, max_feature_length, max_sentence_length, token_ids, id_blank):
+    def features_to_minibatch(self, features, sentences, max_feature_length, max_sentence_length, token_ids, id_blank,
+                              time_reduction=1):
         """-> x (B, 3, nmel, Tmax) f32 on the GPU, x_length list, t (B, Lmax) int32, t_length list, bigram (B, Lmax) int32
-        (host arrays, as the reference returns them before Loader.features_to_minibatch moves them)."""
+        (host arrays, as the reference returns them before Loader.features_to_minibatch moves them).  time_reduction = k of the
+        model (ds2.Model.time_reduction): the labels are cut against ceil(x_length / k), the frames the loss will see; x_length
+        stays the input-rate count."""
         assert isinstance(token_ids, dict) and isinstance(id_blank, int)
+        if isinstance(time_reduction, bool) or not isinstance(time_reduction, int) or time_reduction < 1:
+            raise ValueError("time_reduction must be a positive integer, got %r" % (time_reduction,))
         B = len(features)
         if isinstance(features, DeviceFeatures):
             x_batch, x_lengths = features.x[..., :max_feature_length], list(features.lengths)
@@ -95,7 +100,7 @@ class Processor(fft.Processor):
             unigrams = convert_sentence_to_unigram_tokens(sentence)
             unigram_ids = [token_ids[tok] for tok in unigrams]
             bigram_ids = [-1] + [token_ids.get(a + b, -1) for a, b in zip(unigrams[:-1], unigrams[1:])]     # :131-147
-            unigram_ids, bigram_ids = truncate_labels_for_ctc(unigram_ids, bigram_ids, x_lengths[i])
+            unigram_ids, bigram_ids = truncate_labels_for_ctc(unigram_ids, bigram_ids, -(-x_lengths[i] // time_reduction))
             n = len(unigram_ids)
             t_batch[i, :n] = unigram_ids
             bigram_batch[i, :n] = bigram_ids

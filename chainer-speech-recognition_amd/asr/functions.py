@@ -1321,6 +1321,48 @@ def lookahead_convolution(x, W, x_length=None):
     return logical3(_Lookahead.apply(p, W, x_length))
 
 
+# ---------------------------------------------------------------------------------------------- time reduction by frame stacking
+class _TimeStack(torch.autograd.Function):
+    """p (T, B, R) bf16 -> (ceil(T / k), B, k * R) bf16: csrc/time_stack.hip.  The backward pass is the inverse copy."""
+
+    @staticmethod
+    def forward(ctx, p, k, x_len):
+        ctx.meta = (k, p.shape[0], x_len)
+        y, y_len = _ops.time_stack_fwd(p, k, x_len, want_len=True)
+        ctx.mark_non_differentiable(y_len)
+        return y, y_len
+
+    @staticmethod
+    def backward(ctx, gy, _):
+        k, T, x_len = ctx.meta
+        gy = gy.contiguous() if gy.dtype == BF16 else _ops.cast_bf16(gy.contiguous().reshape(-1, gy.shape[-1])).reshape(gy.shape)
+        return _ops.time_stack_bwd(gy, k, T, x_len), None, None
+
+
+def reduced_length(x_length, k):
+    """ceil(x_length / k) of an int, a list or a tensor (None stays None): the frames left of x_length after ``time_stack``"""
+    if x_length is None:
+        return None
+    if isinstance(x_length, torch.Tensor):
+        return torch.div(x_length + (k - 1), k, rounding_mode="floor").to(x_length.dtype)
+    if isinstance(x_length, (list, tuple)):
+        return [-(-int(v) // k) for v in x_length]
+    if hasattr(x_length, "dtype") and hasattr(x_length, "shape"):           # a numpy array
+        return (x_length + (k - 1)) // k
+    return -(-int(x_length) // k)
+
+
+def time_stack(x, k, x_length=None):
+    """Time reduction by frame stacking: x logical (B, D, T) -> (y logical (B, k * D, ceil(T / k)), y_length):
+    y[b, j * D + d, g] = x[b, d, g * k + j], zero where g * k + j >= x_length[b] ((B) int32 on the device; None = T): a partly
+    filled last group is completed with zeros.  y_length = ceil(x_length / k), None when x_length is None."""
+    k = int(k)
+    if not 1 <= k <= _ops.TIME_STACK_MAX:
+        raise ValueError("time_stack: k must be in 1..%d, got %r" % (_ops.TIME_STACK_MAX, k))
+    y, y_length = _TimeStack.apply(phys3(x), k, x_length)
+    return logical3(y), (None if x_length is None else y_length)
+
+
 # ---------------------------------------------------------------------------------------------- array manipulation (views)
 def reshape(x, shape):
     """chainer.functions.reshape.  Merging (C, H) of a physical image -- run/ctc/sru/model.py:114

@@ -8,15 +8,18 @@ forward (the template drops it, run/ctc/sru/model.py:120-124).  SURVEY.md sectio
   num_rnn_layers x BiGRU(ndim_rnn) (directions summed);  Conv1D(->2*dense)+Maxout, Conv1D(dense->2*dense)+Maxout,
   Conv1D(dense->V), LayerNormalization.  ``lookahead`` > 0 (with bidirectional=False: the deployable streaming recipe,
   asr/model/stream.py) puts nn.LookaheadConvolution(ndim_rnn, lookahead) between the recurrent stack and the dense layers.
+  ``time_reduction`` = k > 1 puts nn.TimeStack(k) between the reshape and the first recurrent layer, as Deep Speech 2 reduces its
+  frame rate in front of the recurrences: k frames of C*H features become one of k*C*H, the recurrent, lookahead and dense layers
+  run over ceil(T / k) frames and the model emits that many (``output_length``).
 """
-from .. import functions, nn
+from .. import _ops, functions, nn
 from .base import NeedsVocabulary
 from ._acoustic import load_if_exists, save_atomic, split_output
 
 
 class Configuration(NeedsVocabulary):
     FIELDS = dict(ndim_audio_features=3, ndim_conv=64, ndim_rnn=512, ndim_dense=320, num_conv_layers=2, num_rnn_layers=4,
-                  bidirectional=True, kernel_size=(3, 5), dropout=0, lookahead=0)
+                  bidirectional=True, kernel_size=(3, 5), dropout=0, lookahead=0, time_reduction=1)
 
 
 def configure():
@@ -30,6 +33,10 @@ class Model(nn.Module):
         pad = kernel_size[1] - 1
         dropout = config.dropout
         self.num_rnn_layers = config.num_rnn_layers
+        k = getattr(config, "time_reduction", 1)
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= _ops.TIME_STACK_MAX:
+            raise ValueError("time_reduction must be an integer in 1..%d, got %r" % (_ops.TIME_STACK_MAX, k))
+        self.time_reduction = k
 
         conv_blocks = nn.Module()
         pools = [3] + [2] * (config.num_conv_layers - 1)
@@ -50,6 +57,11 @@ class Model(nn.Module):
             height -= kernel_size[0] - 1
             height = 1 if height <= pool else -(-(height - pool) // pool) + 1
         self._merged = (config.ndim_conv, height)
+
+        # time reduction by frame stacking in front of the recurrences.  It has no parameters and is an attribute of its own, so no
+        # checkpoint name moves; at k = 1 the model holds no such layer at all.
+        if k > 1:
+            self.time_stack = nn.TimeStack(k)
 
         rnn_blocks = nn.Module()
         rnn_cls = nn.BiGRU if config.bidirectional else nn.GRU
@@ -75,11 +87,15 @@ class Model(nn.Module):
     def __call__(self, x, split_into_variables=True, x_length=None):
         """x_length (B) int32 on the device (the Loader's x_length_batch, asr/data/loaders/base.py:30): the recurrent layers then
         run every utterance over its own frames (the reverse direction starts at the utterance's last frame, not in the padding);
-        None = the padded block as it is."""
+        None = the padded block as it is.  With ``time_reduction`` = k the output has ceil(T / k) frames, of which
+        ``output_length(x_length)`` are an utterance's own."""
         batchsize = x.shape[0]
         seq_length = x.shape[3]
         out_data = self.conv_blocks(x)
         out_data = functions.reshape(out_data, (batchsize, -1, seq_length))
+        if self.time_reduction > 1:
+            out_data, x_length = self.time_stack(out_data, x_length)
+            seq_length = out_data.shape[2]
         if x_length is None:
             out_data = self.rnn_blocks(out_data)
         else:
@@ -91,11 +107,18 @@ class Model(nn.Module):
         assert out_data.shape[2] == seq_length
         return split_output(out_data, batchsize, seq_length, split_into_variables)
 
+    def output_length(self, x_length):
+        """the logit frames of an utterance of `x_length` input frames: ceil(x_length / time_reduction), for an int, a list or a
+        tensor (of the same kind).  It is what the CTC and Gram-CTC losses, the decoders and the aligners take as the length."""
+        return functions.reduced_length(x_length, self.time_reduction)
+
     def column_permutations(self):
         """parameters whose last axis indexes the merged (channel, height) features of the conv stack: {name: (C, H)}.
         The reference's ``reshape(out, (B, -1, T))`` (run/ctc/sru/model.py:114) orders them (c, h), the physical layout here
-        (h, c) -- asr/serializers.py stores the reference's order."""
-        return {"rnn_blocks._sequential_0.w_ih": (self._merged[0], self._merged[1])}
+        (h, c) -- asr/serializers.py stores the reference's order.  With time_reduction = k the stacked columns are (j, h, c),
+        j the frame of the group; they are declared as (C, k * H), so the file holds them as (c, j, h): channel-major like the
+        reference's, a fixed permutation that load inverts exactly (no reference checkpoint has stacked features to agree with)."""
+        return {"rnn_blocks._sequential_0.w_ih": (self._merged[0], self._merged[1] * self.time_reduction)}
 
     def save(self, filename):
         save_atomic(self, filename)

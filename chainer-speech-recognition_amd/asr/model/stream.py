@@ -1,10 +1,11 @@
 """Streaming forward of a causal ``ds2.Model``: features in chunk by chunk, logits out chunk by chunk, all state on the device.
 
 A ``ds2.Model`` with ``bidirectional=False`` is causal end to end: causal convolutions, pooling over height only, forward GRUs,
-per-frame dense layers and LayerNormalization, no subsampling in time.  What has to be carried from one chunk to the next is
-therefore small and local (``stream_plan``): the last kw - 1 input rows of every convolution, the hidden state of every GRU
-layer, and the pending frames of the lookahead convolution, whose ``lookahead`` frames are the stream's delay.  The carry kernels
-are csrc/stream.hip; every other launch is the model's own.  ``(logits, lengths)`` go as they are into
+per-frame dense layers and LayerNormalization, and the only subsampling in time is frame stacking (``time_reduction`` = k: k
+frames in, one out), which is causal too.  What has to be carried from one chunk to the next is therefore small and local
+(``stream_plan``): the last kw - 1 input rows of every convolution, the up to k - 1 frames of a group not yet complete, the
+hidden state of every GRU layer, and the pending frames of the lookahead convolution, whose ``lookahead`` frames are the stream's
+delay.  The carry kernels are csrc/stream.hip and csrc/time_stack.hip; every other launch is the model's own.  ``(logits, lengths)`` go as they are into
 ``asr.error.BeamStream.advance``, ``asr.error.GramBeamStream.advance`` and ``asr.spot.KeywordStream.advance``.
 
 The features come chunk by chunk from ``asr.fft.FeatureStream``: its ``(x, lengths)`` go as they are into
@@ -25,9 +26,11 @@ def _pair(v):
 
 def stream_plan(model):
     """What a stream over `model` carries, layer by layer, from the model's structure alone (no device, no parameters read):
-    {"delay": frames the output lags the input, "layers": [...]} with one entry per carrying layer, in order:
+    {"delay": output frames the output lags the input, "layers": [...]} with one entry per carrying layer, in order:
       {"kind": "context", "K": kw - 1, "R": height * channels of the block's input, "height", "channels", "index": position in
        conv_blocks.layers}                                       a causal convolution's left context, K rows of R features
+      {"kind": "stack", "K": k - 1, "R": height * channels of the conv stack's output, "k": k}      the frames of a group of
+       k not yet complete (only with time_reduction = k > 1, and then the plan also has "time_reduction": k)
       {"kind": "state", "H": units, "index": position in rnn_blocks.layers}      a GRU layer's hidden state
       {"kind": "lookahead", "K": lookahead, "R": features}                       the lookahead layer's pending frames
     ValueError: not a ds2.Model, or a bidirectional one (its reverse recurrences need the whole utterance)."""
@@ -51,6 +54,9 @@ def stream_plan(model):
             height = _ops.pooled_height(height, _pair(layer.ksize)[0])
         elif type(layer).__name__ != "Dropout":
             raise ValueError("no streaming form of %s" % type(layer).__name__)
+    k = getattr(model, "time_reduction", 1)
+    if k > 1:
+        layers.append({"kind": "stack", "K": k - 1, "R": height * channels, "k": k})
     for index, layer in enumerate(model.rnn_blocks.layers):
         if isinstance(layer, nn.BiGRU):
             raise ValueError("a bidirectional model cannot be streamed: its reverse recurrences start at the end of the utterance")
@@ -61,7 +67,10 @@ def stream_plan(model):
     if look is not None:
         delay = look.lookahead
         layers.append({"kind": "lookahead", "K": delay, "R": look.W.shape[0]})
-    return {"delay": delay, "layers": layers}
+    plan = {"delay": delay, "layers": layers}
+    if k > 1:
+        plan["time_reduction"] = k
+    return plan
 
 
 class AcousticStream:
@@ -69,12 +78,20 @@ class AcousticStream:
 
         s = AcousticStream(model, B, max_chunk=64)
         for x, n in chunks:                             # x (B, C, n_mel, Tc) features, n (B): valid frames per slot (0: untouched)
-            logits, lengths = s.advance(x, n)           # (Tc, B, V) f32 left-aligned per slot, (B) int32 on the device
+            logits, lengths = s.advance(x, n)           # (To, B, V) f32 left-aligned per slot, (B) int32 on the device
             beam.advance(logits, lengths)
         logits, lengths = s.flush(mask)                 # end of utterance of the masked slots: the `delay` frames held back
 
     ``delay`` is the model's lookahead: a slot's first `delay` frames come out with later chunks or with ``flush``, which feeds
-    the pending frames a zero future (as the one-shot forward does at an utterance's end) and then resets the slots.  ``frames``
+    the pending frames a zero future (as the one-shot forward does at an utterance's end) and then resets the slots.
+
+    With ``time_reduction`` = k > 1 every k input frames give one output frame: To = ceil((k - 1 + Tc) / k) rows, of which
+    ``lengths[b]`` = (pending + n[b]) // k are the slot's; the up to k - 1 frames of an incomplete group wait for the next chunk,
+    and ``flush`` completes them with zeros (the one-shot forward's last group) before it drains the lookahead, so it returns up
+    to ``delay + 1`` frames.  A slot fed x_len frames in any cuts and flushed has emitted ceil(x_len / k) frames.  ``delay``,
+    ``lengths`` and ``frames`` count output frames; in input frames the output lags by up to k * delay + k - 1.
+
+    ``frames``
     (B) int32 on the device counts the logit frames a slot has emitted since it was last reset (``flush`` leaves the finished
     utterance's count standing until the slot is fed again).  Rows of `logits` at or beyond ``lengths[b]`` are unspecified (the
     epsilon-free LayerNormalization turns a constant row into NaN).  Runs under ``torch.no_grad()``; dropout layers are skipped.
@@ -101,6 +118,12 @@ class AcousticStream:
             self._look = (torch.zeros((e["K"], self.B, e["R"]), dtype=_ops.BF16, device=dev),
                           torch.zeros((self.B,), dtype=torch.int32, device=dev),
                           torch.zeros((e["K"] + self.max_chunk, self.B, e["R"]), dtype=_ops.BF16, device=dev))
+        self.k, self._stack = self.plan.get("time_reduction", 1), None
+        if self.k > 1:
+            e = next(e for e in self.plan["layers"] if e["kind"] == "stack")
+            self._stack = (torch.zeros((e["K"], self.B, e["R"]), dtype=_ops.BF16, device=dev),
+                           torch.zeros((self.B,), dtype=torch.int32, device=dev),
+                           torch.zeros((-(-(e["K"] + self.max_chunk) // self.k), self.B, self.k * e["R"]), dtype=_ops.BF16, device=dev))
         self.frames = torch.zeros((self.B,), dtype=torch.int32, device=dev)
         self._ended = torch.zeros((self.B,), dtype=torch.bool, device=dev)       # flushed and not fed since: `frames` is the old count
         self._ones = torch.ones((self.B,), dtype=torch.int32, device=dev)
@@ -121,6 +144,8 @@ class AcousticStream:
         for _, state, _ in self._ctx:
             if state.shape[0] > 0:
                 _ops.stream_push_reset(state, None, mask)
+        if self._stack is not None:
+            _ops.time_stack_push_reset(self._stack[0], self._stack[1], mask)
         if self._look is not None:
             _ops.stream_push_reset(self._look[0], self._look[1], mask)
         if mask is None:
@@ -145,7 +170,8 @@ class AcousticStream:
     # ---------------------------------------------------------------------------------------------------------------- the chunk
     def advance(self, x, x_length=None):
         """x (B, C, n_mel, Tc) features, Tc <= max_chunk; x_length (B), host or device: the valid frames of this chunk per slot,
-        left-aligned (0: the slot is left exactly as it is), None: all Tc -> (logits (Tc, B, V) f32, lengths (B) int32)"""
+        left-aligned (0: the slot is left exactly as it is), None: all Tc -> (logits (To, B, V) f32, lengths (B) int32), To = Tc, or
+        ceil((k - 1 + Tc) / k) with time_reduction = k (an empty chunk, Tc = 0, touches nothing and returns no rows)"""
         first = self._ctx[0][0] if self._ctx else None
         if x.dim() != 4 or x.shape[0] != self.B or (first is not None and tuple(x.shape[1:3]) != (first["channels"], first["height"])):
             want = ("C", "n_mel") if first is None else (first["channels"], first["height"])
@@ -167,16 +193,20 @@ class AcousticStream:
         with torch.no_grad():
             out = self._conv_blocks(functions.phys4(x.to(self.device)), n, Tc)
             out = functions.reshape(out, (self.B, -1, Tc))
-            grus = [layer for layer in self.model.rnn_blocks.layers if isinstance(layer, nn.GRU)]
-            for layer, h in zip(grus, self._h):
-                out, hy = layer(out, n, hx=h)
-                h.copy_(hy)                 # (a slot beyond its length keeps its state bit for bit: csrc/gru.hip pins its update gate)
-            lengths = n
+            To, steps = Tc, n
+            if self._stack is not None:     # the whole groups of [pending | chunk]; the rest waits
+                state, m, groups = self._stack
+                To = (self.k - 1 + Tc + self.k - 1) // self.k
+                groups = groups[:To]
+                steps = _ops.time_stack_push(state, m, functions.phys3(out), n, groups, self.k)
+                out = functions.logical3(groups)
+            out = self._recurrences(out, steps)
+            lengths = steps
             if self._look is not None:
                 state, m, window = self._look
-                window = window[:self.delay + Tc]
-                wlen, lengths = _ops.stream_push(state, m, functions.phys3(out), n, window, _ops.STREAM_LOOKAHEAD)
-                out = functions.logical3(_ops.lookahead_fwd(window, self.model.lookahead.W.detach(), wlen)[:Tc])
+                window = window[:self.delay + To]
+                wlen, lengths = _ops.stream_push(state, m, functions.phys3(out), steps, window, _ops.STREAM_LOOKAHEAD)
+                out = functions.logical3(_ops.lookahead_fwd(window, self.model.lookahead.W.detach(), wlen)[:To])
             logits = self._logits(out)
             if lengths is None:
                 lengths = torch.full((self.B,), Tc, dtype=torch.int32, device=self.device)
@@ -184,6 +214,14 @@ class AcousticStream:
                 lengths = n.clone()         # (the caller's own tensor stays the caller's)
             self._emitted(lengths, None if n is None else n > 0)
         return logits, lengths
+
+    def _recurrences(self, out, steps):
+        """the GRU layers on (B, D, To) from their carried states, over steps[b] frames per slot (None: all)"""
+        grus = [layer for layer in self.model.rnn_blocks.layers if isinstance(layer, nn.GRU)]
+        for layer, h in zip(grus, self._h):
+            out, hy = layer(out, steps, hx=h)
+            h.copy_(hy)                     # (a slot beyond its length keeps its state bit for bit: csrc/gru.hip pins its update gate)
+        return out
 
     def _conv_blocks(self, p, n, Tc):
         """the conv stack on this chunk: p (Tc, B, H, C) physical features -> logical (B, C', H', Tc).  Every convolution runs
@@ -213,6 +251,23 @@ class AcousticStream:
             p = functions.phys4(out)
         return out
 
+    def _flush_stacked(self, mask):
+        """the masked slots' incomplete group, completed with zeros, goes through the recurrences as one more frame; behind it the
+        lookahead runs over [its pending frames | that frame] with nothing to come, which is the one-shot forward's utterance end"""
+        with torch.no_grad():
+            state, m, groups = self._stack
+            groups = groups[:1]
+            steps = _ops.time_stack_push(state, m, None, None, groups, self.k, flush=mask)      # (B) of 0 or 1
+            out = self._recurrences(functions.logical3(groups), steps)
+            lengths = steps
+            if self._look is not None:
+                state, m, window = self._look
+                window = window[:self.delay + 1]
+                wlen, _ = _ops.stream_push(state, m, functions.phys3(out), steps, window, _ops.STREAM_LOOKAHEAD)
+                out = functions.logical3(_ops.lookahead_fwd(window, self.model.lookahead.W.detach(), wlen))
+                lengths = torch.where(mask != 0, wlen, torch.zeros_like(wlen))
+            return self._logits(out), lengths
+
     def _logits(self, out):
         """dense blocks and the per-frame LayerNormalization on (B, D, To) -> (To, B, V) float32"""
         out = nn.nn._apply_layers(self._dense, out)
@@ -221,9 +276,11 @@ class AcousticStream:
     def flush(self, mask=None):
         """end of utterance for every slot, or those with mask[b] != 0: -> (logits (delay, B, V), lengths (B)) with the frames the
         lookahead held back, computed with a zero future; then these slots are reset (``frames`` keeps the finished count until
-        the slot is fed again)"""
+        the slot is fed again).  With time_reduction > 1: (delay + 1, B, V), the zero-completed last group first."""
         mask = self._ones if mask is None else self._slots(mask, "mask")
-        if self._look is None:
+        if self._stack is not None:
+            logits, lengths = self._flush_stacked(mask)
+        elif self._look is None:
             logits = torch.empty((0, self.B, self._vocab), dtype=torch.float32, device=self.device)
             lengths = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
         else:

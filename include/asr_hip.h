@@ -1076,6 +1076,35 @@ int asr_stream_push(void* stream, void* state, int* m, const void* chunk, const 
                     int* emit, int K, int Tc, int B, int R, int mode);
 int asr_stream_push_reset(void* stream, void* state, int* m, const int* mask, int K, int B, int R);
 
+/* ---------------------------------------------------------------------------------------- time reduction by frame stacking
+ * k consecutive frames of R 16-bit features become one frame of k * R features.  x (T, B, R), y (G, B, k * R), G = ceil(T / k);
+ * x_len (B) int32 or NULL (= T), clamped to [0, T]:
+ *   asr_time_stack_fwd   y[g, b, j * R + r] = x[g * k + j, b, r] where g * k + j < x_len[b], 0 elsewhere: a partly filled last group
+ *                        is completed with zeros (the zero future of the lookahead layer), whole groups at or beyond
+ *                        ceil(x_len[b] / k) are zero.  y_len (B) int32, if not NULL, receives ceil(x_len[b] / k).  T == 0 writes
+ *                        only y_len.
+ *   asr_time_stack_bwd   the inverse copy: dx[t, b, r] = gy[t / k, b, (t % k) * R + r] for t < x_len[b], 0 for x_len[b] <= t < T.
+ *                        Every element of dx is written; no atomics.
+ * asr_time_stack_push is the streaming form.  Per slot b, state (k - 1, B, R) holds m[b] < k pending rows.  The call takes n[b]
+ * rows of chunk (Tc, B, R) (n NULL = Tc; clamped to [0, Tc]) and writes y (ceil((k - 1 + Tc) / k), B, k * R): the forward above of
+ * the sequence [m[b] pending | n[b] new], left-aligned -- so the trailing partial group IS written, zero-completed, behind the
+ * emit[b] = (m[b] + n[b]) / k whole groups, and whole zero groups behind it; the consumer runs with length emit[b].  The last
+ * (m[b] + n[b]) % k rows become the new state (the rows behind them are zeroed) and the new m[b].  A slot with n[b] == 0 keeps its
+ * state bytes.  flush (B) int32 not NULL = end of utterances: no slot is fed (chunk may be NULL, Tc 0); where flush[b] != 0 and
+ * m[b] > 0 the pending rows are emitted as one zero-completed group (emit[b] = 1) and the slot is emptied (state rows zeroed,
+ * m[b] = 0); elsewhere emit[b] = 0, y is zero and the state stays.  Two launches: the first reads the state and writes y and emit,
+ * the second reads y and writes the state and m (one workgroup per slot), so a short chunk never reads what it has overwritten.
+ * asr_time_stack_push_reset zeroes the pending rows and m[b] (m may be NULL) of every slot, or of those with mask[b] != 0.
+ * k == 1: fwd and bwd are plain copies, the push state is empty (state and m may be NULL, emit[b] = n[b]).
+ * Bit-exact copies, independent of the activation type.  R % 8 != 0 or k outside [1, ASR_TIME_STACK_MAX]: ASR_ERR_UNSUPPORTED;
+ * a NULL tensor that would be accessed, a negative T or Tc, B < 1 or R < 1: ASR_ERR_BAD_ARG; nothing is written in either case. */
+#define ASR_TIME_STACK_MAX 8
+int asr_time_stack_fwd(void* stream, const void* x, const int* x_len, void* y, int* y_len, int T, int B, int R, int k);
+int asr_time_stack_bwd(void* stream, const void* gy, const int* x_len, void* dx, int T, int B, int R, int k);
+int asr_time_stack_push(void* stream, void* state, int* m, const void* chunk, const int* n, const int* flush, void* y, int* emit,
+                        int Tc, int B, int R, int k);
+int asr_time_stack_push_reset(void* stream, void* state, int* m, const int* mask, int B, int R, int k);
+
 /* ---------------------------------------------------------------------------------------- streaming log-mel front end
  * Samples in chunk by chunk, feature frames out, for B batch slots that start and end on their own: for every way of cutting a
  * signal the emitted frames are, bit for bit, those of asr_specgram_bands + asr_deltas on the whole signal (L = frame_len,
