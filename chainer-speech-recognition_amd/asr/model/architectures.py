@@ -46,6 +46,7 @@ def build_model(config):
         return nn.Convolution2D(ci, co, ksize=ksize, stride=1, pad=0, weightnorm=wn)
 
     model = AcousticModel()
+    model._input_height = config.num_mel_filters    # (asr/model/stream.py sizes the carried rows of the first convolution from it)
     maxout_family = arch in ("zhang", "zhang+fc_relu", "zhang+residual", "zhang+layernorm", "glu")
     explicit_init = arch not in ("zhang", "zhang+fc_relu")
     ln = arch in ("zhang+layernorm", "relu+layernorm", "relu+layernorm+residual")

@@ -1,27 +1,107 @@
-"""Streaming forward of a causal ``ds2.Model``: features in chunk by chunk, logits out chunk by chunk, all state on the device.
+"""Streaming forward of a causal acoustic model: features in chunk by chunk, logits out chunk by chunk, all state on the device.
 
-A ``ds2.Model`` with ``bidirectional=False`` is causal end to end: causal convolutions, pooling over height only, forward GRUs,
-per-frame dense layers and LayerNormalization, and the only subsampling in time is frame stacking (``time_reduction`` = k: k
-frames in, one out), which is causal too.  What has to be carried from one chunk to the next is therefore small and local
-(``stream_plan``): the last kw - 1 input rows of every convolution, the up to k - 1 frames of a group not yet complete, the
-hidden state of every GRU layer, and the pending frames of the lookahead convolution, whose ``lookahead`` frames are the stream's
-delay.  The carry kernels are csrc/stream.hip and csrc/time_stack.hip; every other launch is the model's own.  ``(logits, lengths)`` go as they are into
-``asr.error.BeamStream.advance``, ``asr.error.GramBeamStream.advance`` and ``asr.spot.KeywordStream.advance``.
+Two families of models are causal end to end and can be streamed (``stream_plan`` says what each of them carries):
+
+A ``ds2.Model`` with ``bidirectional=False``: causal convolutions, pooling over height only, forward GRUs, per-frame dense layers
+and LayerNormalization, and the only subsampling in time is frame stacking (``time_reduction`` = k: k frames in, one out), which is
+causal too.  What has to be carried from one chunk to the next is small and local: the last kw - 1 input rows of every convolution,
+the up to k - 1 frames of a group not yet complete, the hidden state of every GRU layer, and the pending frames of the lookahead
+convolution, whose ``lookahead`` frames are the stream's delay.
+
+The seven convolutional recipes of architectures.py (``cnn.AcousticModel``, what ``build_model`` returns): every
+time-padded convolution is pad_t = kw - 1 followed by the crop (``nn.GLU`` pads and crops itself), pooling runs over height only, the
+4-d LayerNormalization takes its statistics over (C, H) of one frame and the residual adds are per frame.  There is no recurrence and
+no lookahead: the carry is the last kw - 1 input rows of every convolution wider than one frame, and the delay is 0.
+
+The carry kernels are csrc/stream.hip and csrc/time_stack.hip; every other launch is the model's own.  ``(logits, lengths)`` go as they
+are into ``asr.error.BeamStream.advance``, ``asr.error.GramBeamStream.advance`` and ``asr.spot.KeywordStream.advance``.
 
 The features come chunk by chunk from ``asr.fft.FeatureStream``: its ``(x, lengths)`` go as they are into
 ``advance``, with ``max_chunk >= FeatureStream.max_frames``.
 
-Not covered: the CNN recipes of architectures.py and the SRU template (``stream_plan`` is where they would
-plug in), and a backward pass through a stream.
+Not covered: the SRU template (its reference model drops the recurrent output and ``asr_sru_fwd`` has no
+per-slot lengths; ``stream_plan`` is where it would plug in), and a backward pass through a stream.
 """
 import torch
 
 from .. import _ops, functions, nn
+from ..link import Link
 from . import ds2
+from ._acoustic import AcousticCall, mark_logit_layers
 
 
 def _pair(v):
     return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
+def _name(layer):
+    return getattr(layer, "__name__", None) or type(layer).__name__
+
+
+def _convolution_of(layer):
+    """(the convolution link of a layer, whether a GLU wraps it), or (None, False)"""
+    if isinstance(layer, nn.GLU):
+        return layer.W, True
+    if isinstance(layer, (nn.PlainConvolution2D, nn.WeightnormConvolution2D)):
+        return layer, False
+    return None, False
+
+
+def _cnn_walk(model):
+    """the "context" entries of a cnn.AcousticModel and the (height, channels) of its output, from the layer list alone"""
+    first = None
+    for layer in model.layers:
+        for sub in (layer.layers if isinstance(layer, nn.Residual) else (layer,)):
+            if first is None:
+                first = _convolution_of(sub)[0]
+    master = None if first is None else (first.V if isinstance(first, nn.WeightnormConvolution2D) else first.W)
+    if master is None or master.dim() != 4:
+        raise ValueError("no streaming form of %s: it has no sized convolution that says how many channels the features have"
+                         % type(model).__name__)
+    # (build_model records the configuration's num_mel_filters; a container filled by hand gets the front end's default of 40 rows)
+    shape = [getattr(model, "_input_height", 40), master.shape[1]]
+    entries = []
+
+    def step(layer, path):
+        height, channels = shape
+        conv, gated = _convolution_of(layer)
+        if conv is not None:
+            (kh, kw), (pad_h, pad_t) = conv.ksize, conv.pad
+            where = "layer %s (%s)" % ("_".join(str(i) for i in path), _name(layer))
+            if kw > 1:
+                if pad_t != kw - 1 or not (gated or conv.causal):
+                    raise ValueError("%s is not causal: a stream needs pad_t = kw - 1 and the crop behind it" % where)
+                entries.append({"kind": "context", "K": kw - 1, "R": height * channels, "height": height, "channels": channels,
+                                "index": path[0], "path": path, "pad_h": pad_h})
+            elif pad_t != 0:
+                raise ValueError("%s pads the time axis of a one-frame kernel" % where)
+            shape[:] = [height + 2 * pad_h - kh + 1, conv.out_channels // 2 if gated else conv.out_channels]
+            if shape[0] < 1:
+                raise ValueError("%s is higher than its input" % where)
+        elif _name(layer) == "Maxout":
+            if not isinstance(layer.pool_size, int) or channels % layer.pool_size:
+                raise ValueError("no streaming form of Maxout(%r) over %d channels" % (layer.pool_size, channels))
+            shape[1] = channels // layer.pool_size
+        elif _name(layer) == "MaxPooling2D":
+            ks = _pair(layer.ksize)
+            if len(ks) != 2 or ks[1] != 1 or layer.stride is not None or layer.pad not in (0, (0, 0)):
+                raise ValueError("no streaming form of MaxPooling2D(%r): a stream pools over height only" % (layer.ksize,))
+            shape[0] = _ops.pooled_height(height, ks[0])
+        elif isinstance(layer, nn.Residual):
+            if len(path) > 1:
+                raise ValueError("no streaming form of a Residual inside a Residual")
+            for inner, sub in enumerate(layer.layers):
+                step(sub, path + (inner,))
+            if shape != [height, channels]:
+                raise ValueError("no streaming form of the Residual at layer %d: it turns (height, channels) = %s into %s"
+                                 % (path[0], (height, channels), tuple(shape)))
+        elif not (getattr(layer, "_asr_identity", False) or layer is functions.relu or _name(layer) == "Dropout"
+                  or isinstance(layer, nn.LayerNormalization)):
+            raise ValueError("no streaming form of %s (layer %s)" % (_name(layer), "_".join(str(i) for i in path)))
+
+    for index, layer in enumerate(model.layers):
+        step(layer, (index,))
+    return entries, shape[0], shape[1]
 
 
 def stream_plan(model):
@@ -33,9 +113,15 @@ def stream_plan(model):
        k not yet complete (only with time_reduction = k > 1, and then the plan also has "time_reduction": k)
       {"kind": "state", "H": units, "index": position in rnn_blocks.layers}      a GRU layer's hidden state
       {"kind": "lookahead", "K": lookahead, "R": features}                       the lookahead layer's pending frames
-    ValueError: not a ds2.Model, or a bidirectional one (its reverse recurrences need the whole utterance)."""
+    A ``cnn.AcousticModel`` (architectures.build_model) carries only convolution contexts, and its delay is 0: one "context" entry
+    per convolution wider than one frame, as above with "index": position in model.layers, plus "path": (index,), or (index, inner)
+    for a layer inside a Residual, and "pad_h".  The convolution of a GLU is model.layers[index].W.
+    ValueError: neither of the two, a bidirectional ds2.Model (its reverse recurrences need the whole utterance), a convolution that
+    looks ahead in time, or a layer without a per-frame form (BatchNormalization, a recurrent layer, a Residual that changes shape)."""
+    if isinstance(model, AcousticCall) and isinstance(model, nn.Stream):
+        return {"delay": 0, "layers": _cnn_walk(model)[0]}
     if not isinstance(model, ds2.Model):
-        raise ValueError("a stream runs a ds2.Model, got %s" % type(model).__name__)
+        raise ValueError("a stream runs a ds2.Model or a cnn.AcousticModel, got %s" % type(model).__name__)
     layers = []
     height, channels = model._input_height, None
     for index, layer in enumerate(model.conv_blocks.layers):
@@ -73,8 +159,62 @@ def stream_plan(model):
     return plan
 
 
+class _StreamedConvolution:
+    """Stands in an ``AcousticStream``'s layer list for one convolution (or GLU) of a cnn.AcousticModel.  With a plan entry it pushes
+    its input rows and runs the layer's own convolution un-padded in time over [the K carried rows | the chunk], which is the causal
+    convolution of the whole sequence; without one (a one-frame kernel) it is the layer itself.  Either way the W of a
+    weight-normalised layer, and through `link` the 16-bit matrices made from it, are the ones ``refresh`` formed."""
+
+    def __init__(self, stream, conv, gated, slot):
+        self.stream, self.conv, self.gated, self.slot = stream, conv, gated, slot
+        self.derived = isinstance(conv, nn.WeightnormConvolution2D)
+        self.refresh()
+
+    def refresh(self):
+        if self.derived:        # (a new link: its cache is keyed by the weight's address, which a freed W may hand to the next one)
+            self.W, self.link = self.conv.W, Link()
+
+    def _weight(self):
+        return (self.W, self.link) if self.derived else (self.conv.W, self.conv)
+
+    def _window(self, x):
+        """the view of [carried rows | chunk] this layer reads, before it is filled"""
+        entry, _, window = self.stream._ctx[self.slot]
+        return functions.logical4(window[:entry["K"] + x.shape[3]].view(-1, self.stream.B, entry["height"], entry["channels"]))
+
+    def _push(self, x):
+        entry, state, window = self.stream._ctx[self.slot]
+        Tc = x.shape[3]
+        _ops.stream_push(state, None, functions.phys4(x).reshape(Tc, self.stream.B, entry["R"]), self.stream._n, window[:entry["K"] + Tc],
+                         _ops.STREAM_CONTEXT)
+
+    def __call__(self, x):
+        conv = self.conv
+        W, link = self._weight()
+        pad, causal = conv.pad, conv.causal
+        if self.slot is not None:
+            xw = self._window(x)
+            self._push(x)
+            x, pad, causal = xw, (conv.pad[0], 0), False
+        y = functions.convolution_2d(x, W, conv.b, link, pad, causal, conv.output_float32)
+        return functions.glu(y) if self.gated else y
+
+    def fused_maxout_pool(self, x, k):
+        """the model's first block as one pass, where the one-shot forward runs it as one (nn.nn._apply_layers); None: three layers"""
+        conv = self.conv
+        if self.slot is None or self.gated or conv.output_float32:
+            return None
+        W, link = self._weight()
+        xw, pad = self._window(x), (conv.pad[0], 0)
+        if not functions.convolution_maxout_pool_ok(xw, tuple(W.shape), pad, False, k):
+            return None
+        self._push(x)
+        return functions.convolution_maxout_pool(xw, W, conv.b, link, pad, False, k)
+
+
 class AcousticStream:
-    """``model(x)`` of a causal ``ds2.Model`` fed chunk by chunk, for `B` batch slots that start and end on their own:
+    """``model(x)`` of a causal ``ds2.Model``, or of a ``cnn.AcousticModel`` (the recipes of architectures.py), fed chunk by chunk,
+    for `B` batch slots that start and end on their own:
 
         s = AcousticStream(model, B, max_chunk=64)
         for x, n in chunks:                             # x (B, C, n_mel, Tc) features, n (B): valid frames per slot (0: untouched)
@@ -95,13 +235,21 @@ class AcousticStream:
     (B) int32 on the device counts the logit frames a slot has emitted since it was last reset (``flush`` leaves the finished
     utterance's count standing until the slot is fed again).  Rows of `logits` at or beyond ``lengths[b]`` are unspecified (the
     epsilon-free LayerNormalization turns a constant row into NaN).  Runs under ``torch.no_grad()``; dropout layers are skipped.
-    Nothing here synchronises with the host."""
+    Nothing here synchronises with the host.
+
+    A ``cnn.AcousticModel`` must have been called or loaded once, so that every lazily sized parameter has its size.  Its delay is 0:
+    ``advance`` returns ``lengths == n`` and ``flush`` no rows.  The W = g V / (||V|| + 1e-9) of its weight-normalised layers, and the
+    16-bit matrices made from it, are formed once, here: the stream sees a later change of such a layer's V or g only after
+    ``refresh()`` (every other parameter is read as it is when the chunk runs)."""
 
     def __init__(self, model, B, max_chunk=64, device=None):
         self.plan = stream_plan(model)
         self.model, self.B, self.max_chunk, self.delay = model, int(B), int(max_chunk), self.plan["delay"]
         if self.B < 1 or self.max_chunk < 1:
             raise ValueError("B and max_chunk must be positive")
+        self._cnn = not isinstance(model, ds2.Model)
+        if self._cnn and any(p.numel() == 0 for p in model.parameters()):
+            raise ValueError("the model has parameters without a size yet: run it once or load it before it is streamed")
         if device is None:
             device = next(model.parameters()).device
         self.device = dev = torch.device(device)
@@ -127,8 +275,46 @@ class AcousticStream:
         self.frames = torch.zeros((self.B,), dtype=torch.int32, device=dev)
         self._ended = torch.zeros((self.B,), dtype=torch.bool, device=dev)       # flushed and not fed since: `frames` is the old count
         self._ones = torch.ones((self.B,), dtype=torch.int32, device=dev)
+        if self._cnn:
+            self._n = None                  # the chunk's frames per slot while ``advance`` runs
+            self._layers, self._streamed = self._cnn_layers()
+            return
         self._dense = [layer for layer in model.dense_blocks.layers if type(layer).__name__ != "Dropout"]
         self._vocab = model.dense_blocks.layers[-2].out_channels
+
+    def _cnn_layers(self):
+        """the layer list ``advance`` runs for a cnn.AcousticModel: the model's own layers without the dropouts, a
+        _StreamedConvolution for every convolution that carries rows or whose weight is derived -> (layers, those stand-ins)"""
+        _, height, self._vocab = _cnn_walk(self.model)
+        if height != 1:
+            raise ValueError("the model leaves %d rows per frame: logits need one" % height)
+        slots = {e["path"]: i for i, (e, _, _) in enumerate(self._ctx)}
+        streamed = []
+
+        def stand_in(layer, path):
+            conv, gated = _convolution_of(layer)
+            if conv is None or (path not in slots and not isinstance(conv, nn.WeightnormConvolution2D)):
+                return layer
+            streamed.append(_StreamedConvolution(self, conv, gated, slots.get(path)))
+            return streamed[-1]
+
+        layers = []
+        for index, layer in enumerate(self.model.layers):
+            if isinstance(layer, nn.Residual):
+                layer = nn.Residual(*[stand_in(sub, (index, inner)) for inner, sub in enumerate(layer.layers)
+                                      if type(sub).__name__ != "Dropout"])
+            elif type(layer).__name__ == "Dropout":
+                continue
+            layers.append(stand_in(layer, (index,)))
+        return layers, streamed
+
+    def refresh(self):
+        """read the weight-normalised layers' parameters again: W = g V / (||V|| + 1e-9) and its 16-bit matrices, one pass per layer
+        (a ds2.Model has none: nothing to do)"""
+        if self._cnn:
+            with torch.no_grad():
+                for layer in self._streamed:
+                    layer.refresh()
 
     # ---------------------------------------------------------------------------------------------------------------- arguments
     def _slots(self, values, what):
@@ -190,6 +376,8 @@ class AcousticStream:
         if Tc == 0:
             return (torch.empty((0, self.B, self._vocab), dtype=torch.float32, device=self.device),
                     torch.zeros((self.B,), dtype=torch.int32, device=self.device))
+        if self._cnn:
+            return self._advance_cnn(x, n, Tc)
         with torch.no_grad():
             out = self._conv_blocks(functions.phys4(x.to(self.device)), n, Tc)
             out = functions.reshape(out, (self.B, -1, Tc))
@@ -213,6 +401,21 @@ class AcousticStream:
             elif lengths is n:
                 lengths = n.clone()         # (the caller's own tensor stays the caller's)
             self._emitted(lengths, None if n is None else n > 0)
+        return logits, lengths
+
+    def _advance_cnn(self, x, n, Tc):
+        """the chunk through a cnn.AcousticModel: the one-shot forward's own sequence (nn.nn._apply_layers, so the same fused passes),
+        with every convolution wider than one frame reading [its carried rows | the chunk]"""
+        mark_logit_layers(self.model.layers)        # the last projection and normalisation write float32, as in the one-shot call
+        self._n = n
+        try:
+            with torch.no_grad():
+                out = nn.nn._apply_layers(self._layers, x.to(self.device))         # (B, V, 1, Tc) over a (Tc, B, 1, V) buffer
+                logits = out.permute(3, 0, 2, 1).squeeze(2).to(torch.float32).contiguous()
+                lengths = torch.full((self.B,), Tc, dtype=torch.int32, device=self.device) if n is None else n.clone()
+                self._emitted(lengths, None if n is None else n > 0)
+        finally:
+            self._n = None
         return logits, lengths
 
     def _recurrences(self, out, steps):
