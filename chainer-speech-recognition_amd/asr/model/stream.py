@@ -13,6 +13,10 @@ time-padded convolution is pad_t = kw - 1 followed by the crop (``nn.GLU`` pads 
 4-d LayerNormalization takes its statistics over (C, H) of one frame and the residual adds are per frame.  There is no recurrence and
 no lookahead: the carry is the last kw - 1 input rows of every convolution wider than one frame, and the delay is 0.
 
+Both families go through the same code: ``_walk_layers`` plans the convolutional front of either, a
+``_StreamedConvolution`` stands in for each of its carrying convolutions in the layer list that ``nn.nn._apply_layers`` runs on every
+chunk, and what a ds2.Model has behind that front (frame stacking, recurrences, lookahead, dense layers) a recipe simply has not.
+
 The carry kernels are csrc/stream.hip and csrc/time_stack.hip; every other launch is the model's own.  ``(logits, lengths)`` go as they
 are into ``asr.error.BeamStream.advance``, ``asr.error.GramBeamStream.advance`` and ``asr.spot.KeywordStream.advance``.
 
@@ -47,27 +51,18 @@ def _convolution_of(layer):
     return None, False
 
 
-def _cnn_walk(model):
-    """the "context" entries of a cnn.AcousticModel and the (height, channels) of its output, from the layer list alone"""
-    first = None
-    for layer in model.layers:
-        for sub in (layer.layers if isinstance(layer, nn.Residual) else (layer,)):
-            if first is None:
-                first = _convolution_of(sub)[0]
-    master = None if first is None else (first.V if isinstance(first, nn.WeightnormConvolution2D) else first.W)
-    if master is None or master.dim() != 4:
-        raise ValueError("no streaming form of %s: it has no sized convolution that says how many channels the features have"
-                         % type(model).__name__)
-    # (build_model records the configuration's num_mel_filters; a container filled by hand gets the front end's default of 40 rows)
-    shape = [getattr(model, "_input_height", 40), master.shape[1]]
+def _walk_layers(layers, height, channels, outer=()):
+    """The one structural walk, for the layers of a cnn.AcousticModel and for the conv stack of a ds2.Model: from the (height,
+    channels) that enter `layers` -> (the "context" entries, height, channels behind the last layer).  ValueError for whatever
+    has no per-frame form.  `outer`: the path of the Residual whose layers these are."""
     entries = []
-
-    def step(layer, path):
-        height, channels = shape
+    for index, layer in enumerate(layers):
+        path = outer + (index,)
+        at = "_".join(str(i) for i in path)
+        where = "layer %s (%s)" % (at, _name(layer))
         conv, gated = _convolution_of(layer)
         if conv is not None:
             (kh, kw), (pad_h, pad_t) = conv.ksize, conv.pad
-            where = "layer %s (%s)" % ("_".join(str(i) for i in path), _name(layer))
             if kw > 1:
                 if pad_t != kw - 1 or not (gated or conv.causal):
                     raise ValueError("%s is not causal: a stream needs pad_t = kw - 1 and the crop behind it" % where)
@@ -75,71 +70,72 @@ def _cnn_walk(model):
                                 "index": path[0], "path": path, "pad_h": pad_h})
             elif pad_t != 0:
                 raise ValueError("%s pads the time axis of a one-frame kernel" % where)
-            shape[:] = [height + 2 * pad_h - kh + 1, conv.out_channels // 2 if gated else conv.out_channels]
-            if shape[0] < 1:
+            height, channels = height + 2 * pad_h - kh + 1, conv.out_channels // 2 if gated else conv.out_channels
+            if height < 1:
                 raise ValueError("%s is higher than its input" % where)
         elif _name(layer) == "Maxout":
             if not isinstance(layer.pool_size, int) or channels % layer.pool_size:
                 raise ValueError("no streaming form of Maxout(%r) over %d channels" % (layer.pool_size, channels))
-            shape[1] = channels // layer.pool_size
+            channels //= layer.pool_size
         elif _name(layer) == "MaxPooling2D":
             ks = _pair(layer.ksize)
             if len(ks) != 2 or ks[1] != 1 or layer.stride is not None or layer.pad not in (0, (0, 0)):
                 raise ValueError("no streaming form of MaxPooling2D(%r): a stream pools over height only" % (layer.ksize,))
-            shape[0] = _ops.pooled_height(height, ks[0])
+            height = _ops.pooled_height(height, ks[0])
         elif isinstance(layer, nn.Residual):
-            if len(path) > 1:
+            if outer:
                 raise ValueError("no streaming form of a Residual inside a Residual")
-            for inner, sub in enumerate(layer.layers):
-                step(sub, path + (inner,))
-            if shape != [height, channels]:
+            inner, h, c = _walk_layers(layer.layers, height, channels, path)
+            if (h, c) != (height, channels):
                 raise ValueError("no streaming form of the Residual at layer %d: it turns (height, channels) = %s into %s"
-                                 % (path[0], (height, channels), tuple(shape)))
+                                 % (index, (height, channels), (h, c)))
+            entries += inner
         elif not (getattr(layer, "_asr_identity", False) or layer is functions.relu or _name(layer) == "Dropout"
                   or isinstance(layer, nn.LayerNormalization)):
-            raise ValueError("no streaming form of %s (layer %s)" % (_name(layer), "_".join(str(i) for i in path)))
+            raise ValueError("no streaming form of %s (layer %s)" % (_name(layer), at))
+    return entries, height, channels
 
-    for index, layer in enumerate(model.layers):
-        step(layer, (index,))
-    return entries, shape[0], shape[1]
+
+def _front(model):
+    """the layers in front of whatever else a stream runs: all of a cnn.AcousticModel, the conv stack of a ds2.Model"""
+    if isinstance(model, ds2.Model):
+        return model.conv_blocks
+    if isinstance(model, AcousticCall) and isinstance(model, nn.Stream):
+        return model
+    raise ValueError("a stream runs a ds2.Model or a cnn.AcousticModel, got %s" % type(model).__name__)
+
+
+def _walk(model):
+    """_walk_layers over the front of `model`, from the features' (height, channels)"""
+    layers = _front(model).layers
+    convs = (_convolution_of(sub)[0] for layer in layers for sub in (layer.layers if isinstance(layer, nn.Residual) else (layer,)))
+    first = next((conv for conv in convs if conv is not None), None)
+    master = None if first is None else (first.V if isinstance(first, nn.WeightnormConvolution2D) else first.W)
+    if master is None or master.dim() != 4:
+        raise ValueError("no streaming form of %s: it has no sized convolution that says how many channels the features have"
+                         % type(model).__name__)
+    # (both model builders record the configuration's num_mel_filters; a container filled by hand gets the front end's default of 40 rows)
+    return _walk_layers(layers, getattr(model, "_input_height", 40), master.shape[1])
 
 
 def stream_plan(model):
     """What a stream over `model` carries, layer by layer, from the model's structure alone (no device, no parameters read):
     {"delay": output frames the output lags the input, "layers": [...]} with one entry per carrying layer, in order:
       {"kind": "context", "K": kw - 1, "R": height * channels of the block's input, "height", "channels", "index": position in
-       conv_blocks.layers}                                       a causal convolution's left context, K rows of R features
+       conv_blocks.layers, "path": (index,), "pad_h"}            a causal convolution's left context, K rows of R features
       {"kind": "stack", "K": k - 1, "R": height * channels of the conv stack's output, "k": k}      the frames of a group of
        k not yet complete (only with time_reduction = k > 1, and then the plan also has "time_reduction": k)
       {"kind": "state", "H": units, "index": position in rnn_blocks.layers}      a GRU layer's hidden state
       {"kind": "lookahead", "K": lookahead, "R": features}                       the lookahead layer's pending frames
     A ``cnn.AcousticModel`` (architectures.build_model) carries only convolution contexts, and its delay is 0: one "context" entry
-    per convolution wider than one frame, as above with "index": position in model.layers, plus "path": (index,), or (index, inner)
-    for a layer inside a Residual, and "pad_h".  The convolution of a GLU is model.layers[index].W.
-    ValueError: neither of the two, a bidirectional ds2.Model (its reverse recurrences need the whole utterance), a convolution that
-    looks ahead in time, or a layer without a per-frame form (BatchNormalization, a recurrent layer, a Residual that changes shape)."""
-    if isinstance(model, AcousticCall) and isinstance(model, nn.Stream):
-        return {"delay": 0, "layers": _cnn_walk(model)[0]}
+    per convolution wider than one frame, as above with "index": position in model.layers and "path": (index,), or (index, inner)
+    for a layer inside a Residual.  The convolution of a GLU is model.layers[index].W.
+    ValueError: neither of the two, a bidirectional ds2.Model (its reverse recurrences need the whole utterance), or, in the layers
+    of a cnn.AcousticModel as in the conv stack of a ds2.Model (_walk_layers walks both), a convolution that looks ahead in time or a
+    layer without a per-frame form (pooling over time, BatchNormalization, a recurrent layer, a Residual that changes shape)."""
+    layers, height, channels = _walk(model)
     if not isinstance(model, ds2.Model):
-        raise ValueError("a stream runs a ds2.Model or a cnn.AcousticModel, got %s" % type(model).__name__)
-    layers = []
-    height, channels = model._input_height, None
-    for index, layer in enumerate(model.conv_blocks.layers):
-        if isinstance(layer, nn.PlainConvolution2D):
-            kh, kw = layer.ksize
-            if not layer.causal or layer.pad[1] != kw - 1:
-                raise ValueError("convolution %d is not causal" % index)
-            if channels is None:
-                channels = layer.W.shape[1]
-            layers.append({"kind": "context", "K": kw - 1, "R": height * channels, "height": height, "channels": channels,
-                           "index": index})
-            height, channels = height + 2 * layer.pad[0] - kh + 1, layer.out_channels
-        elif type(layer).__name__ == "Maxout":
-            channels //= layer.pool_size
-        elif type(layer).__name__ == "MaxPooling2D":
-            height = _ops.pooled_height(height, _pair(layer.ksize)[0])
-        elif type(layer).__name__ != "Dropout":
-            raise ValueError("no streaming form of %s" % type(layer).__name__)
+        return {"delay": 0, "layers": layers}
     k = getattr(model, "time_reduction", 1)
     if k > 1:
         layers.append({"kind": "stack", "K": k - 1, "R": height * channels, "k": k})
@@ -159,14 +155,21 @@ def stream_plan(model):
     return plan
 
 
-class _StreamedConvolution:
-    """Stands in an ``AcousticStream``'s layer list for one convolution (or GLU) of a cnn.AcousticModel.  With a plan entry it pushes
-    its input rows and runs the layer's own convolution un-padded in time over [the K carried rows | the chunk], which is the causal
-    convolution of the whole sequence; without one (a one-frame kernel) it is the layer itself.  Either way the W of a
-    weight-normalised layer, and through `link` the 16-bit matrices made from it, are the ones ``refresh`` formed."""
+class _ChunkLengths:
+    """The valid frames per slot of the chunk that is running, (B) int32 on the device or None for all of them: ``advance`` fills
+    it before the layer list runs, and the stand-ins of that list read it when they push."""
+    n = None
 
-    def __init__(self, stream, conv, gated, slot):
-        self.stream, self.conv, self.gated, self.slot = stream, conv, gated, slot
+
+class _StreamedConvolution:
+    """Stands in an ``AcousticStream``'s layer list for one convolution (or GLU) of the model.  With `carry`, its own (plan entry,
+    carried rows, window), it pushes its input rows and runs the layer's own convolution un-padded in time over [the K carried rows |
+    the chunk], which is the causal convolution of the whole sequence; without one (a one-frame kernel) it is the layer itself.
+    Either way the W of a weight-normalised layer, and through `link` the 16-bit matrices made from it, are the ones ``refresh``
+    formed."""
+
+    def __init__(self, conv, gated, carry, lengths):
+        self.conv, self.gated, self.carry, self.lengths = conv, gated, carry, lengths
         self.derived = isinstance(conv, nn.WeightnormConvolution2D)
         self.refresh()
 
@@ -179,20 +182,20 @@ class _StreamedConvolution:
 
     def _window(self, x):
         """the view of [carried rows | chunk] this layer reads, before it is filled"""
-        entry, _, window = self.stream._ctx[self.slot]
-        return functions.logical4(window[:entry["K"] + x.shape[3]].view(-1, self.stream.B, entry["height"], entry["channels"]))
+        entry, _, window = self.carry
+        return functions.logical4(window[:entry["K"] + x.shape[3]].view(-1, window.shape[1], entry["height"], entry["channels"]))
 
     def _push(self, x):
-        entry, state, window = self.stream._ctx[self.slot]
+        entry, state, window = self.carry
         Tc = x.shape[3]
-        _ops.stream_push(state, None, functions.phys4(x).reshape(Tc, self.stream.B, entry["R"]), self.stream._n, window[:entry["K"] + Tc],
-                         _ops.STREAM_CONTEXT)
+        _ops.stream_push(state, None, functions.phys4(x).reshape(Tc, window.shape[1], entry["R"]), self.lengths.n,
+                         window[:entry["K"] + Tc], _ops.STREAM_CONTEXT)
 
     def __call__(self, x):
         conv = self.conv
         W, link = self._weight()
         pad, causal = conv.pad, conv.causal
-        if self.slot is not None:
+        if self.carry is not None:
             xw = self._window(x)
             self._push(x)
             x, pad, causal = xw, (conv.pad[0], 0), False
@@ -202,7 +205,7 @@ class _StreamedConvolution:
     def fused_maxout_pool(self, x, k):
         """the model's first block as one pass, where the one-shot forward runs it as one (nn.nn._apply_layers); None: three layers"""
         conv = self.conv
-        if self.slot is None or self.gated or conv.output_float32:
+        if self.carry is None or self.gated or conv.output_float32:
             return None
         W, link = self._weight()
         xw, pad = self._window(x), (conv.pad[0], 0)
@@ -247,8 +250,8 @@ class AcousticStream:
         self.model, self.B, self.max_chunk, self.delay = model, int(B), int(max_chunk), self.plan["delay"]
         if self.B < 1 or self.max_chunk < 1:
             raise ValueError("B and max_chunk must be positive")
-        self._cnn = not isinstance(model, ds2.Model)
-        if self._cnn and any(p.numel() == 0 for p in model.parameters()):
+        front = _front(model)
+        if any(p.numel() == 0 for p in front.parameters()):
             raise ValueError("the model has parameters without a size yet: run it once or load it before it is streamed")
         if device is None:
             device = next(model.parameters()).device
@@ -256,65 +259,64 @@ class AcousticStream:
         for entry in self.plan["layers"]:
             if entry["kind"] != "state" and entry["R"] % 8 != 0:
                 raise ValueError("carried rows must be a multiple of 8 features wide, got %d" % entry["R"])
-        self._ctx = [(e, torch.zeros((e["K"], self.B, e["R"]), dtype=_ops.BF16, device=dev),
-                      torch.zeros((e["K"] + self.max_chunk, self.B, e["R"]), dtype=_ops.BF16, device=dev))
+
+        def rows(count, width):
+            return torch.zeros((count, self.B, width), dtype=_ops.BF16, device=dev)
+
+        def per_slot(dtype=torch.int32):
+            return torch.zeros((self.B,), dtype=dtype, device=dev)
+
+        # per carrying layer (carried rows[, their count per slot], the window a chunk is laid into)
+        kinds = {e["kind"]: e for e in self.plan["layers"]}
+        self._ctx = [(e, rows(e["K"], e["R"]), rows(e["K"] + self.max_chunk, e["R"]))
                      for e in self.plan["layers"] if e["kind"] == "context"]
         self._h = [torch.zeros((1, self.B, e["H"]), dtype=torch.float32, device=dev) for e in self.plan["layers"] if e["kind"] == "state"]
-        self._look = None
-        if self.delay > 0:
-            e = self.plan["layers"][-1]
-            self._look = (torch.zeros((e["K"], self.B, e["R"]), dtype=_ops.BF16, device=dev),
-                          torch.zeros((self.B,), dtype=torch.int32, device=dev),
-                          torch.zeros((e["K"] + self.max_chunk, self.B, e["R"]), dtype=_ops.BF16, device=dev))
-        self.k, self._stack = self.plan.get("time_reduction", 1), None
-        if self.k > 1:
-            e = next(e for e in self.plan["layers"] if e["kind"] == "stack")
-            self._stack = (torch.zeros((e["K"], self.B, e["R"]), dtype=_ops.BF16, device=dev),
-                           torch.zeros((self.B,), dtype=torch.int32, device=dev),
-                           torch.zeros((-(-(e["K"] + self.max_chunk) // self.k), self.B, self.k * e["R"]), dtype=_ops.BF16, device=dev))
-        self.frames = torch.zeros((self.B,), dtype=torch.int32, device=dev)
-        self._ended = torch.zeros((self.B,), dtype=torch.bool, device=dev)       # flushed and not fed since: `frames` is the old count
+        e = kinds.get("lookahead")
+        self._look = e and (rows(e["K"], e["R"]), per_slot(), rows(e["K"] + self.max_chunk, e["R"]))
+        self.k, e = self.plan.get("time_reduction", 1), kinds.get("stack")
+        self._stack = e and (rows(e["K"], e["R"]), per_slot(), rows(-(-(e["K"] + self.max_chunk) // self.k), self.k * e["R"]))
+        self.frames = per_slot()
+        self._ended = per_slot(torch.bool)          # flushed and not fed since: `frames` is the old count
         self._ones = torch.ones((self.B,), dtype=torch.int32, device=dev)
-        if self._cnn:
-            self._n = None                  # the chunk's frames per slot while ``advance`` runs
-            self._layers, self._streamed = self._cnn_layers()
-            return
-        self._dense = [layer for layer in model.dense_blocks.layers if type(layer).__name__ != "Dropout"]
-        self._vocab = model.dense_blocks.layers[-2].out_channels
+        # the layer list every chunk runs in front: the model's own layers without the dropouts, a _StreamedConvolution for every
+        # convolution that carries rows or whose weight is derived
+        self._lengths, self._streamed = _ChunkLengths(), []
+        carries = {c[0]["path"]: c for c in self._ctx}
 
-    def _cnn_layers(self):
-        """the layer list ``advance`` runs for a cnn.AcousticModel: the model's own layers without the dropouts, a
-        _StreamedConvolution for every convolution that carries rows or whose weight is derived -> (layers, those stand-ins)"""
-        _, height, self._vocab = _cnn_walk(self.model)
-        if height != 1:
-            raise ValueError("the model leaves %d rows per frame: logits need one" % height)
-        slots = {e["path"]: i for i, (e, _, _) in enumerate(self._ctx)}
-        streamed = []
+        def stand_ins(layers, outer=()):
+            out = []
+            for index, layer in enumerate(layers):
+                path = outer + (index,)
+                conv, gated = _convolution_of(layer)
+                if _name(layer) == "Dropout":
+                    continue
+                if isinstance(layer, nn.Residual):
+                    layer = nn.Residual(*stand_ins(layer.layers, path))
+                elif conv is not None and (path in carries or isinstance(conv, nn.WeightnormConvolution2D)):
+                    layer = _StreamedConvolution(conv, gated, carries.get(path), self._lengths)
+                    self._streamed.append(layer)
+                out.append(layer)
+            return out
 
-        def stand_in(layer, path):
-            conv, gated = _convolution_of(layer)
-            if conv is None or (path not in slots and not isinstance(conv, nn.WeightnormConvolution2D)):
-                return layer
-            streamed.append(_StreamedConvolution(self, conv, gated, slots.get(path)))
-            return streamed[-1]
-
-        layers = []
-        for index, layer in enumerate(self.model.layers):
-            if isinstance(layer, nn.Residual):
-                layer = nn.Residual(*[stand_in(sub, (index, inner)) for inner, sub in enumerate(layer.layers)
-                                      if type(sub).__name__ != "Dropout"])
-            elif type(layer).__name__ == "Dropout":
-                continue
-            layers.append(stand_in(layer, (index,)))
-        return layers, streamed
+        self._layers = stand_ins(front.layers)
+        # and what runs behind it: nothing for a recipe, whose last layer gives the logits
+        self._grus, self._dense = [], []
+        if front is model:
+            _, height, self._vocab = _walk(model)
+            if height != 1:
+                raise ValueError("the model leaves %d rows per frame: logits need one" % height)
+            mark_logit_layers(model.layers)     # the last projection and normalisation write float32, as in the one-shot call
+        else:
+            self._grus = [layer for layer in model.rnn_blocks.layers if isinstance(layer, nn.GRU)]
+            self._dense = [layer for layer in model.dense_blocks.layers if _name(layer) != "Dropout"]
+            self._vocab = model.dense_blocks.layers[-2].out_channels
 
     def refresh(self):
         """read the weight-normalised layers' parameters again: W = g V / (||V|| + 1e-9) and its 16-bit matrices, one pass per layer
         (a ds2.Model has none: nothing to do)"""
-        if self._cnn:
-            with torch.no_grad():
-                for layer in self._streamed:
-                    layer.refresh()
+        with torch.no_grad():
+            for layer in self._streamed:
+                layer.refresh()
 
     # ---------------------------------------------------------------------------------------------------------------- arguments
     def _slots(self, values, what):
@@ -376,11 +378,11 @@ class AcousticStream:
         if Tc == 0:
             return (torch.empty((0, self.B, self._vocab), dtype=torch.float32, device=self.device),
                     torch.zeros((self.B,), dtype=torch.int32, device=self.device))
-        if self._cnn:
-            return self._advance_cnn(x, n, Tc)
         with torch.no_grad():
-            out = self._conv_blocks(functions.phys4(x.to(self.device)), n, Tc)
-            out = functions.reshape(out, (self.B, -1, Tc))
+            # the front on this chunk -> logical (B, C', H', Tc): the one-shot forward's own sequencer, so the same fused passes, with
+            # every carrying convolution un-padded in time over [its K carried rows | the chunk]
+            self._lengths.n = n
+            out = functions.reshape(nn.nn._apply_layers(self._layers, x.to(self.device)), (self.B, -1, Tc))
             To, steps = Tc, n
             if self._stack is not None:     # the whole groups of [pending | chunk]; the rest waits
                 state, m, groups = self._stack
@@ -388,14 +390,7 @@ class AcousticStream:
                 groups = groups[:To]
                 steps = _ops.time_stack_push(state, m, functions.phys3(out), n, groups, self.k)
                 out = functions.logical3(groups)
-            out = self._recurrences(out, steps)
-            lengths = steps
-            if self._look is not None:
-                state, m, window = self._look
-                window = window[:self.delay + To]
-                wlen, lengths = _ops.stream_push(state, m, functions.phys3(out), steps, window, _ops.STREAM_LOOKAHEAD)
-                out = functions.logical3(_ops.lookahead_fwd(window, self.model.lookahead.W.detach(), wlen)[:To])
-            logits = self._logits(out)
+            logits, lengths = self._tail(self._recurrences(out, steps), steps, self.delay + To, To)
             if lengths is None:
                 lengths = torch.full((self.B,), Tc, dtype=torch.int32, device=self.device)
             elif lengths is n:
@@ -403,96 +398,53 @@ class AcousticStream:
             self._emitted(lengths, None if n is None else n > 0)
         return logits, lengths
 
-    def _advance_cnn(self, x, n, Tc):
-        """the chunk through a cnn.AcousticModel: the one-shot forward's own sequence (nn.nn._apply_layers, so the same fused passes),
-        with every convolution wider than one frame reading [its carried rows | the chunk]"""
-        mark_logit_layers(self.model.layers)        # the last projection and normalisation write float32, as in the one-shot call
-        self._n = n
-        try:
-            with torch.no_grad():
-                out = nn.nn._apply_layers(self._layers, x.to(self.device))         # (B, V, 1, Tc) over a (Tc, B, 1, V) buffer
-                logits = out.permute(3, 0, 2, 1).squeeze(2).to(torch.float32).contiguous()
-                lengths = torch.full((self.B,), Tc, dtype=torch.int32, device=self.device) if n is None else n.clone()
-                self._emitted(lengths, None if n is None else n > 0)
-        finally:
-            self._n = None
-        return logits, lengths
-
     def _recurrences(self, out, steps):
         """the GRU layers on (B, D, To) from their carried states, over steps[b] frames per slot (None: all)"""
-        grus = [layer for layer in self.model.rnn_blocks.layers if isinstance(layer, nn.GRU)]
-        for layer, h in zip(grus, self._h):
+        for layer, h in zip(self._grus, self._h):
             out, hy = layer(out, steps, hx=h)
             h.copy_(hy)                     # (a slot beyond its length keeps its state bit for bit: csrc/gru.hip pins its update gate)
         return out
 
-    def _conv_blocks(self, p, n, Tc):
-        """the conv stack on this chunk: p (Tc, B, H, C) physical features -> logical (B, C', H', Tc).  Every convolution runs
-        un-padded in time over [its K carried rows | the chunk], which is the causal convolution of the whole sequence."""
-        layers = self.model.conv_blocks.layers
-        out = None
-        for i, (entry, state, window) in enumerate(self._ctx):
-            K, conv = entry["K"], layers[entry["index"]]
-            window = window[:K + Tc]
-            _ops.stream_push(state, None, p.reshape(Tc, self.B, entry["R"]), n, window, _ops.STREAM_CONTEXT)
-            x = functions.logical4(window.view(K + Tc, self.B, entry["height"], entry["channels"]))
-            stop = self._ctx[i + 1][0]["index"] if i + 1 < len(self._ctx) else len(layers)
-            tail = [layer for layer in layers[entry["index"] + 1:stop] if type(layer).__name__ != "Dropout"]
-            pad = (conv.pad[0], 0)
-            if conv.W.numel() == 0:
-                conv._initialize_params(entry["channels"])
-            y = None
-            j = nn.nn._fusable_pool(tail, 0) if tail else -1
-            if j > 0 and not conv.output_float32:
-                ks = _pair(tail[j].ksize)[0]
-                y = functions.convolution_maxout_pool(x, conv.W, conv.b, conv, pad, False, ks)
-                if y is not None:
-                    tail = tail[j + 1:]
-            if y is None:
-                y = functions.convolution_2d(x, conv.W, conv.b, conv, pad, False, conv.output_float32)
-            out = nn.nn._apply_layers(tail, y)
-            p = functions.phys4(out)
-        return out
+    def _tail(self, out, steps, rows, keep=None, flush=None, ended=None):
+        """What follows the recurrences: the lookahead, if the model has one, and the dense layers.  `out` (B, D, To) with steps[b]
+        frames per slot (None: nothing new, the slots in `flush` end) goes behind the lookahead's pending frames into the first
+        `rows` rows of its window, the layer runs over them with nothing to come, and the first `keep` rows of that (None: all)
+        go through the dense layers and the per-frame LayerNormalization -> (logits (rows kept, B, V) float32, lengths (B): the
+        frames the push says a slot emits, or with `ended` every valid window row of the slots in it and none of the others);
+        without a lookahead `out` goes straight on and lengths are `steps`."""
+        lengths = steps
+        if self._look is not None:
+            state, m, window = self._look
+            window = window[:rows]
+            wlen, lengths = _ops.stream_push(state, m, None if out is None else functions.phys3(out), steps, window,
+                                             _ops.STREAM_LOOKAHEAD, flush=flush)
+            out = functions.logical3(_ops.lookahead_fwd(window, self.model.lookahead.W.detach(), wlen)[:keep])
+            if ended is not None:
+                lengths = torch.where(ended != 0, wlen, torch.zeros_like(wlen))
+        out = nn.nn._apply_layers(self._dense, out)
+        return out.permute(2, 0, 1).to(torch.float32).contiguous(), lengths
 
     def _flush_stacked(self, mask):
         """the masked slots' incomplete group, completed with zeros, goes through the recurrences as one more frame; behind it the
         lookahead runs over [its pending frames | that frame] with nothing to come, which is the one-shot forward's utterance end"""
-        with torch.no_grad():
-            state, m, groups = self._stack
-            groups = groups[:1]
-            steps = _ops.time_stack_push(state, m, None, None, groups, self.k, flush=mask)      # (B) of 0 or 1
-            out = self._recurrences(functions.logical3(groups), steps)
-            lengths = steps
-            if self._look is not None:
-                state, m, window = self._look
-                window = window[:self.delay + 1]
-                wlen, _ = _ops.stream_push(state, m, functions.phys3(out), steps, window, _ops.STREAM_LOOKAHEAD)
-                out = functions.logical3(_ops.lookahead_fwd(window, self.model.lookahead.W.detach(), wlen))
-                lengths = torch.where(mask != 0, wlen, torch.zeros_like(wlen))
-            return self._logits(out), lengths
-
-    def _logits(self, out):
-        """dense blocks and the per-frame LayerNormalization on (B, D, To) -> (To, B, V) float32"""
-        out = nn.nn._apply_layers(self._dense, out)
-        return out.permute(2, 0, 1).to(torch.float32).contiguous()
+        state, m, groups = self._stack
+        groups = groups[:1]
+        steps = _ops.time_stack_push(state, m, None, None, groups, self.k, flush=mask)      # (B) of 0 or 1
+        return self._tail(self._recurrences(functions.logical3(groups), steps), steps, self.delay + 1, ended=mask)
 
     def flush(self, mask=None):
         """end of utterance for every slot, or those with mask[b] != 0: -> (logits (delay, B, V), lengths (B)) with the frames the
         lookahead held back, computed with a zero future; then these slots are reset (``frames`` keeps the finished count until
         the slot is fed again).  With time_reduction > 1: (delay + 1, B, V), the zero-completed last group first."""
         mask = self._ones if mask is None else self._slots(mask, "mask")
-        if self._stack is not None:
-            logits, lengths = self._flush_stacked(mask)
-        elif self._look is None:
-            logits = torch.empty((0, self.B, self._vocab), dtype=torch.float32, device=self.device)
-            lengths = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
-        else:
-            with torch.no_grad():
-                state, m, window = self._look
-                window = window[:self.delay]
-                wlen, lengths = _ops.stream_push(state, m, None, None, window, _ops.STREAM_LOOKAHEAD, flush=mask)
-                out = functions.logical3(_ops.lookahead_fwd(window, self.model.lookahead.W.detach(), wlen))
-                logits = self._logits(out)
+        with torch.no_grad():
+            if self._stack is not None:
+                logits, lengths = self._flush_stacked(mask)
+            elif self._look is not None:
+                logits, lengths = self._tail(None, None, self.delay, flush=mask)
+            else:
+                logits = torch.empty((0, self.B, self._vocab), dtype=torch.float32, device=self.device)
+                lengths = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
         count = self.frames + lengths
         self.reset(mask)
         on = mask != 0

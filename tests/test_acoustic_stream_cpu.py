@@ -43,6 +43,47 @@ def test_plan_follows_the_configuration():
     assert model._merged == (8, 1)
 
 
+def test_the_conv_stack_is_planned_by_the_shared_walker():
+    """the conv stack of a ds2.Model goes through the walker that plans the layers of a cnn.AcousticModel: the plan's context
+    entries are its result on conv_blocks.layers, and they carry its keys ("path", "pad_h")"""
+    from asr.model.stream import _walk_layers, stream_plan
+    for fields in (dict(lookahead=5), dict(kernel_size=(5, 3), num_conv_layers=3, num_mel_filters=48, time_reduction=2)):
+        cfg, model = _ds2_small(bidirectional=False, **fields)
+        plan = stream_plan(model)
+        contexts = [e for e in plan["layers"] if e["kind"] not in ("stack", "state", "lookahead")]
+        assert len(contexts) == cfg.num_conv_layers
+        assert all(e["kind"] == "context" and e["path"] == (e["index"],) and e["pad_h"] == 0 for e in contexts)
+        entries, height, channels = _walk_layers(model.conv_blocks.layers, cfg.num_mel_filters, cfg.ndim_audio_features)
+        assert contexts == entries and (channels, height) == model._merged
+
+
+def _swap_conv_layer(model, index, layer):
+    """put `layer` where conv_blocks.layers[index] is, in the list and under the registered name"""
+    layers = list(model.conv_blocks.layers)
+    layers[index] = layer
+    model.conv_blocks.layers = layers
+    setattr(model.conv_blocks, "_sequential_%d" % index, layer)
+
+
+def test_a_conv_stack_that_pools_over_time_is_refused():
+    from asr import nn
+    from asr.model.stream import stream_plan
+    cfg, model = _ds2_small(bidirectional=False)
+    assert type(model.conv_blocks.layers[3]).__name__ == "MaxPooling2D"
+    stream_plan(model)
+    _swap_conv_layer(model, 3, nn.MaxPooling2D((2, 2)))
+    with pytest.raises(ValueError, match="no streaming form of MaxPooling2D"):
+        stream_plan(model)
+
+
+def test_a_conv_stack_that_looks_ahead_is_refused():
+    from asr.model.stream import stream_plan
+    cfg, model = _ds2_small(bidirectional=False)
+    model.conv_blocks.layers[0].causal = False
+    with pytest.raises(ValueError, match="not causal"):
+        stream_plan(model)
+
+
 def test_a_bidirectional_model_is_refused():
     from asr.model.stream import AcousticStream, stream_plan
     cfg, model = _ds2_small()
