@@ -245,6 +245,9 @@ SIGNATURES = {
     "asr_time_stack_bwd": (c_int, [c_void_p] * 4 + [c_int] * 4),
     "asr_time_stack_push": (c_int, [c_void_p] * 8 + [c_int] * 4),
     "asr_time_stack_push_reset": (c_int, [c_void_p] * 4 + [c_int] * 3),
+    "asr_lc_gather": (c_int, [c_void_p] * 6 + [c_int] * 6),
+    "asr_lc_scatter": (c_int, [c_void_p] * 6 + [c_int] * 6),
+    "asr_lc_push": (c_int, [c_void_p] * 10 + [c_int] * 5),
     "asr_fbank_stream_push": (c_int, [c_void_p, c_void_p, c_int, c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                       c_void_p, c_longlong, c_void_p, c_void_p, c_int, c_int, c_int, c_double]),
     "asr_fbank_stream_deltas": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p] * 4),

@@ -1660,6 +1660,62 @@ def time_stack_push_reset(state, m=None, mask=None):
           "asr_time_stack_push_reset")
 
 
+# ---------------------------------------------------------------------------------------------- latency-controlled BiGRU: window copies
+LC_MAX_WINDOW = 4096            # ASR_LC_MAX_WINDOW, ASR_LC_WINDOW and ASR_LC_BLOCK of include/asr_hip.h
+LC_WINDOW, LC_BLOCK = 0, 1
+
+
+def lc_window_shape(T, B, Nc, Nr):
+    """(W, C * B): the rows of a window and the windows of a (T, B, .) sequence"""
+    return min(Nc + Nr, T), -(-T // Nc) * B
+
+
+def lc_gather(x, Nc, Nr, mode, x_len=None, n_win=None, want_len=True):
+    """asr_lc_gather: x (T, B, R) 16-bit -> (xw (W, C * B, R): window c * B + b holds block c of slot b with its right context,
+    time-reversed; w_len (C * B) int32, its live rows, or None).  mode LC_WINDOW: every live row; LC_BLOCK: only the block's own."""
+    T, B, R = _stack_args(x, "(T, B, R) activations")
+    Nc, Nr = int(Nc), int(Nr)
+    W, CB = lc_window_shape(T, B, max(Nc, 1), max(Nr, 0))
+    xw = torch.empty((W, CB, R), dtype=x.dtype, device=x.device)
+    w_len = torch.empty((CB,), dtype=torch.int32, device=x.device) if want_len else None
+    check(_lib.lib().asr_lc_gather(stream(), ptr(x), ptr(_len_i32(x_len, B, x.device)), ptr(_len_i32(n_win, B, x.device)), ptr(xw),
+                                   ptr(w_len), T, B, R, Nc, Nr, int(mode)), "asr_lc_gather")
+    return xw, w_len
+
+
+def lc_scatter(yw, T, B, Nc, Nr, mode, addend=None, x_len=None, n_win=None, out=None):
+    """asr_lc_scatter: yw (W, C * B, R) -> y (T, B, R) = addend + the windows' rows of every frame below x_len[b] (LC_BLOCK: the
+    frame's own block; LC_WINDOW: every window that holds it), float32 sums in a fixed order; zero at and beyond x_len[b]"""
+    W, CB, R = _stack_args(yw, "(W, C * B, R) windows")
+    T, B, Nc, Nr = int(T), int(B), int(Nc), int(Nr)
+    if (W, CB) != lc_window_shape(T, B, max(Nc, 1), max(Nr, 0)):
+        raise ValueError("yw %s is not the window batch of (%d, %d, .) at Nc = %d, Nr = %d" % (tuple(yw.shape), T, B, Nc, Nr))
+    y = torch.empty((T, B, R), dtype=yw.dtype, device=yw.device) if out is None else out
+    assert y.dtype == yw.dtype and tuple(y.shape) == (T, B, R) and y.is_contiguous()
+    assert addend is None or (addend.dtype == yw.dtype and tuple(addend.shape) == (T, B, R) and addend.is_contiguous())
+    check(_lib.lib().asr_lc_scatter(stream(), ptr(yw), ptr(addend), ptr(_len_i32(x_len, B, yw.device)), ptr(_len_i32(n_win, B, yw.device)),
+                                    ptr(y), T, B, R, Nc, Nr, int(mode)), "asr_lc_scatter")
+    return y
+
+
+def lc_push(state, m, chunk, n, window, Nc, Nr, flush=None):
+    """asr_lc_push: state (Nc + Nr - 1, B, R) 16-bit pending rows and m (B) int32 their counts (both updated), chunk (Tc, B, R) or None,
+    n (B) int32 or None, flush (B) int32 or None (these slots end), window (K + Tc, B, R) (written: [pending | new | zeros]) ->
+    (a, w, emit), (B) int32 each: the rows in the window, its whole blocks, the frames the layer emits"""
+    K, B, R = state.shape
+    Nc, Nr = int(Nc), int(Nr)
+    Tc = 0 if chunk is None else chunk.shape[0]
+    assert K == Nc + Nr - 1 and state.element_size() == 2 and window.dtype == state.dtype and tuple(window.shape) == (K + Tc, B, R)
+    assert chunk is None or (chunk.dtype == state.dtype and tuple(chunk.shape[1:]) == (B, R) and chunk.is_contiguous())
+    assert m.dtype == torch.int32 and m.numel() == B and window.is_contiguous()
+    dev = state.device
+    a, w, emit = (torch.empty((B,), dtype=torch.int32, device=dev) for _ in range(3))
+    check(_lib.lib().asr_lc_push(stream(), ptr(state) if K else None, ptr(m), ptr(chunk) if Tc else None, ptr(_len_i32(n, B, dev)),
+                                 ptr(_len_i32(flush, B, dev)), ptr(window) if window.numel() else None, ptr(a), ptr(w), ptr(emit),
+                                 Tc, B, R, Nc, Nr), "asr_lc_push")
+    return a, w, emit
+
+
 # ---------------------------------------------------------------------------------------------- streaming log-mel front end
 FBANK_STREAM_MAX_FRAMES = 128   # ASR_FBANK_STREAM_MAX_FRAMES, ASR_FBANK_STREAM_MAX_FILT and ASR_FBANK_STREAM_META of include/asr_hip.h
 FBANK_STREAM_MAX_FILT = 64

@@ -1290,6 +1290,108 @@ def gru(x, w_ih, w_hh, b_ih, b_hh, link, ndir, x_length=None, hx=None):
     return logical3(y.reshape(T, B, H))
 
 
+# ---------------------------------------------------------------------------------------------- latency-controlled BiGRU
+def _as_act(g):
+    """an incoming gradient as contiguous 16-bit activations"""
+    return g.contiguous() if g.dtype == BF16 else _ops.cast_bf16(g.contiguous().reshape(-1, g.shape[-1])).reshape(g.shape)
+
+
+class _LCGather(torch.autograd.Function):
+    """p (T, B, R) bf16 -> (the windows (W, C * B, R), their lengths (C * B) int32): csrc/lc_window.hip.  The backward pass is the
+    scatter over every window that holds a frame: the overlap-add of the input gradient, in a fixed order."""
+
+    @staticmethod
+    def forward(ctx, p, Nc, Nr, x_len, n_win):
+        ctx.meta = (p.shape[0], p.shape[1], Nc, Nr, x_len, n_win)
+        xw, w_len = _ops.lc_gather(p, Nc, Nr, _ops.LC_WINDOW, x_len, n_win)
+        ctx.mark_non_differentiable(w_len)
+        return xw, w_len
+
+    @staticmethod
+    def backward(ctx, gxw, _):
+        T, B, Nc, Nr, x_len, n_win = ctx.meta
+        return _ops.lc_scatter(_as_act(gxw), T, B, Nc, Nr, _ops.LC_WINDOW, None, x_len, n_win), None, None, None, None
+
+
+class _LCScatter(torch.autograd.Function):
+    """yw (W, C * B, R), addend (T, B, R) bf16 -> (T, B, R): every frame's row of its own block's window, added to the addend.  The
+    backward pass is the gather of the blocks' own rows (the right-context outputs were cropped: no gradient); the addend's gradient is
+    the output's, which the recurrence behind it reads below x_len only."""
+
+    @staticmethod
+    def forward(ctx, yw, addend, T, B, Nc, Nr, x_len, n_win):
+        ctx.meta = (Nc, Nr, x_len, n_win)
+        return _ops.lc_scatter(yw, T, B, Nc, Nr, _ops.LC_BLOCK, addend, x_len, n_win)
+
+    @staticmethod
+    def backward(ctx, gy):
+        Nc, Nr, x_len, n_win = ctx.meta
+        gy = _as_act(gy)
+        gyw = _ops.lc_gather(gy, Nc, Nr, _ops.LC_BLOCK, x_len, n_win, want_len=False)[0] if ctx.needs_input_grad[0] else None
+        return gyw, (gy if ctx.needs_input_grad[1] else None), None, None, None, None, None, None
+
+
+class _LCAnnounce(torch.autograd.Function):
+    """Identity in front of the two recurrences.  Its backward runs once both of them have queued their weight gradients (each into
+    its slice of the stacked parameters' buffers) and says so for the whole parameters: asr/link.py, grads_queued.  The parameters are
+    inputs of the node, so its output asks for a gradient whenever they do: the recurrences behind it (whose own weight arguments are
+    detached views) run their backward passes, and this one, also where the layer's input asks for none."""
+
+    @staticmethod
+    def forward(ctx, p, *params):
+        ctx.params = params
+        return p.view_as(p)
+
+    @staticmethod
+    def backward(ctx, g):
+        grads_queued(*ctx.params)
+        return (g,) + (None,) * len(ctx.params)
+
+
+def _direction(param, d):
+    """direction d of a stacked parameter as a (1, ...) tensor on the parameter's memory that names its owner, so that the backward
+    pass of functions.gru with ndir = 1 accumulates the direction's gradient into that slice of the parameter's gradient buffer, where
+    the optimiser reads it (asr/link.py: grad_buffer, which looks the buffer up when the backward pass runs)"""
+    s = param.detach()[d:d + 1]
+    s._asr_grad_of = (param, slice(d, d + 1))
+    return s
+
+
+def lc_direction(params, d):
+    """(w_ih, w_hh, b_ih, b_hh) of direction d of a bidirectional layer's stacked parameters, each (1, ...): what ``gru`` takes with ndir = 1"""
+    return [_direction(w, d) for w in params]
+
+
+def lc_check(Nc, Nr):
+    """(Nc, Nr) as integers; ValueError unless Nc >= 1, Nr >= 0 and Nc + Nr <= ASR_LC_MAX_WINDOW"""
+    for v in (Nc, Nr):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError("latency control takes integers (block, right context), got %r" % ((Nc, Nr),))
+    if Nc < 1 or Nr < 0 or Nc + Nr > _ops.LC_MAX_WINDOW:
+        raise ValueError("latency control needs a block >= 1, a right context >= 0 and block + right <= %d, got %r"
+                         % (_ops.LC_MAX_WINDOW, (Nc, Nr)))
+    return Nc, Nr
+
+
+def lc_bigru(x, w_ih, w_hh, b_ih, b_hh, link, Nc, Nr, x_length=None):
+    """The latency-controlled bidirectional GRU (include/asr_hip.h): x logical (B, I, T), the parameters of a BiGRU (stacked over the
+    two directions) -> logical (B, H, T), the directions summed.  The forward direction is ``gru`` with the direction-0 slices over the
+    whole utterance; the reverse direction is restarted from zero for every block of `Nc` frames and sees `Nr` frames beyond it: the
+    blocks, with their right context and time-reversed, run as one batch of ceil(T / Nc) * B sequences through ``gru`` with the
+    direction-1 slices.  `link` holds one ``Link`` per direction in ``link.directions`` for the 16-bit weight copies.  With Nc >= T
+    this is ``gru(..., ndir=2)`` up to the rounding of the forward direction's output before the sum."""
+    Nc, Nr = lc_check(Nc, Nr)
+    p = phys3(x)
+    T, B, _ = p.shape
+    p = _LCAnnounce.apply(p, w_ih, w_hh, b_ih, b_hh)
+    x_in = logical3(p)
+    parts = [lc_direction((w_ih, w_hh, b_ih, b_hh), d) for d in range(2)]
+    fwd = phys3(gru(x_in, *parts[0], link.directions[0], 1, x_length))
+    xw, w_len = _LCGather.apply(p, Nc, Nr, x_length, None)
+    yw = phys3(gru(logical3(xw), *parts[1], link.directions[1], 1, w_len))
+    return logical3(_LCScatter.apply(yw, fwd, T, B, Nc, Nr, x_length, None))
+
+
 # ---------------------------------------------------------------------------------------------- lookahead convolution
 class _Lookahead(torch.autograd.Function):
     """p (T, B, D) bf16, W (D, tau + 1) f32 master -> (T, B, D) bf16: csrc/lookahead.hip.  dW goes straight into W.grad."""

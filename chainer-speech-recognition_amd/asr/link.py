@@ -188,7 +188,12 @@ def grads_queued(*params):
 
 
 def grad_buffer(param):
-    """The f32 buffer the backward kernels accumulate this parameter's gradient into (param.grad)."""
+    """The f32 buffer the backward kernels accumulate this parameter's gradient into (param.grad).  A view of a parameter made by
+    ``functions.lc_direction`` (one direction of a stacked recurrent parameter) names its owner: its buffer is the same view of the
+    owner's, looked up now -- an optimiser may have moved the owner's .grad since the forward pass."""
+    owner = getattr(param, "_asr_grad_of", None)
+    if owner is not None:
+        return grad_buffer(owner[0])[owner[1]]
     if param.grad is None:
         from . import _ops
         g = torch.empty_like(param, memory_format=torch.contiguous_format)

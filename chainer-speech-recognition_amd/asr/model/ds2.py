@@ -11,6 +11,8 @@ forward (the template drops it, run/ctc/sru/model.py:120-124).  SURVEY.md sectio
   ``time_reduction`` = k > 1 puts nn.TimeStack(k) between the reshape and the first recurrent layer, as Deep Speech 2 reduces its
   frame rate in front of the recurrences: k frames of C*H features become one of k*C*H, the recurrent, lookahead and dense layers
   run over ceil(T / k) frames and the model emits that many (``output_length``).
+  ``latency_control`` = (Nc, Nr) (with bidirectional=True) makes every recurrent layer an nn.LCBiGRU: the reverse directions restart
+  per block of Nc frames with Nr frames of right context, and the model streams with a delay of num_rnn_layers * (Nc + Nr - 1) frames.
 """
 from .. import _ops, functions, nn
 from .base import NeedsVocabulary
@@ -19,7 +21,7 @@ from ._acoustic import load_if_exists, save_atomic, split_output
 
 class Configuration(NeedsVocabulary):
     FIELDS = dict(ndim_audio_features=3, ndim_conv=64, ndim_rnn=512, ndim_dense=320, num_conv_layers=2, num_rnn_layers=4,
-                  bidirectional=True, kernel_size=(3, 5), dropout=0, lookahead=0, time_reduction=1)
+                  bidirectional=True, kernel_size=(3, 5), dropout=0, lookahead=0, time_reduction=1, latency_control=None)
 
 
 def configure():
@@ -63,10 +65,27 @@ class Model(nn.Module):
         if k > 1:
             self.time_stack = nn.TimeStack(k)
 
+        # latency control (Nc, Nr): every recurrent layer of a bidirectional model becomes an nn.LCBiGRU, whose reverse direction is
+        # restarted per block of Nc frames with Nr frames of right context -- a BiGRU's parameters under a BiGRU's names, so no
+        # checkpoint name moves.  Blocks count the frames the recurrences see: reduced ones with time_reduction > 1.
+        control = getattr(config, "latency_control", None)
+        if control is not None:
+            if not isinstance(control, (tuple, list)) or len(control) != 2:
+                raise ValueError("latency_control must be None or (block, right context), got %r" % (control,))
+            control = functions.lc_check(*control)
+            if not config.bidirectional:
+                raise ValueError("latency_control restarts the reverse direction of a bidirectional model: bidirectional=False has none")
+            if config.lookahead > 0:
+                raise ValueError("latency_control and lookahead > 0 do not combine: the right context is the model's lookahead")
+        self.latency_control = control
+
         rnn_blocks = nn.Module()
-        rnn_cls = nn.BiGRU if config.bidirectional else nn.GRU
         for _ in range(config.num_rnn_layers):
-            rnn_blocks.add(rnn_cls(None, config.ndim_rnn), nn.Dropout(dropout))
+            if control is not None:
+                rnn = nn.LCBiGRU(None, config.ndim_rnn, block=control[0], right=control[1])
+            else:
+                rnn = (nn.BiGRU if config.bidirectional else nn.GRU)(None, config.ndim_rnn)
+            rnn_blocks.add(rnn, nn.Dropout(dropout))
         self.rnn_blocks = rnn_blocks
 
         # Deep Speech 2's lookahead convolution between the recurrent stack and the dense layers: `lookahead` future frames for a
@@ -100,7 +119,7 @@ class Model(nn.Module):
             out_data = self.rnn_blocks(out_data)
         else:
             for layer in self.rnn_blocks.layers:
-                out_data = layer(out_data, x_length) if isinstance(layer, (nn.GRU, nn.BiGRU)) else layer(out_data)
+                out_data = layer(out_data, x_length) if isinstance(layer, (nn.GRU, nn.BiGRU, nn.LCBiGRU)) else layer(out_data)
         if getattr(self, "lookahead", None) is not None:
             out_data = self.lookahead(out_data, x_length)
         out_data = self.dense_blocks(out_data)

@@ -6,7 +6,9 @@ A ``ds2.Model`` with ``bidirectional=False``: causal convolutions, pooling over 
 and LayerNormalization, and the only subsampling in time is frame stacking (``time_reduction`` = k: k frames in, one out), which is
 causal too.  What has to be carried from one chunk to the next is small and local: the last kw - 1 input rows of every convolution,
 the up to k - 1 frames of a group not yet complete, the hidden state of every GRU layer, and the pending frames of the lookahead
-convolution, whose ``lookahead`` frames are the stream's delay.
+convolution, whose ``lookahead`` frames are the stream's delay.  A bidirectional model streams when it was built with
+``latency_control`` = (Nc, Nr): its reverse directions restart per block of Nc frames and see Nr frames beyond it, so a layer holds
+back at most Nc + Nr - 1 frames (``_blocks``; csrc/lc_window.hip).
 
 The seven convolutional recipes of architectures.py (``cnn.AcousticModel``, what ``build_model`` returns): every
 time-padded convolution is pad_t = kw - 1 followed by the crop (``nn.GLU`` pads and crops itself), pooling runs over height only, the
@@ -127,10 +129,13 @@ def stream_plan(model):
        k not yet complete (only with time_reduction = k > 1, and then the plan also has "time_reduction": k)
       {"kind": "state", "H": units, "index": position in rnn_blocks.layers}      a GRU layer's hidden state
       {"kind": "lookahead", "K": lookahead, "R": features}                       the lookahead layer's pending frames
+      {"kind": "lc", "H": units, "index": position in rnn_blocks.layers, "Nc": block, "Nr": right context, "K": Nc + Nr - 1,
+       "R": the layer's input width}      a latency-controlled BiGRU layer: the forward direction's state and up to K pending
+       input rows that wait for the right context of their block; "delay" is then the bound num_layers * K
     A ``cnn.AcousticModel`` (architectures.build_model) carries only convolution contexts, and its delay is 0: one "context" entry
     per convolution wider than one frame, as above with "index": position in model.layers and "path": (index,), or (index, inner)
     for a layer inside a Residual.  The convolution of a GLU is model.layers[index].W.
-    ValueError: neither of the two, a bidirectional ds2.Model (its reverse recurrences need the whole utterance), or, in the layers
+    ValueError: neither of the two, a ds2.Model with plain BiGRU layers (their reverse recurrences need the whole utterance), or, in the layers
     of a cnn.AcousticModel as in the conv stack of a ds2.Model (_walk_layers walks both), a convolution that looks ahead in time or a
     layer without a per-frame form (pooling over time, BatchNormalization, a recurrent layer, a Residual that changes shape)."""
     layers, height, channels = _walk(model)
@@ -139,13 +144,21 @@ def stream_plan(model):
     k = getattr(model, "time_reduction", 1)
     if k > 1:
         layers.append({"kind": "stack", "K": k - 1, "R": height * channels, "k": k})
+    delay, width = 0, k * height * channels
     for index, layer in enumerate(model.rnn_blocks.layers):
         if isinstance(layer, nn.BiGRU):
             raise ValueError("a bidirectional model cannot be streamed: its reverse recurrences start at the end of the utterance")
+        if isinstance(layer, nn.LCBiGRU):
+            K = layer.block + layer.right - 1
+            layers.append({"kind": "lc", "H": layer.out_size, "index": index, "Nc": layer.block, "Nr": layer.right, "K": K, "R": width})
+            delay += K
         if isinstance(layer, nn.GRU):
             layers.append({"kind": "state", "H": layer.out_size, "index": index})
-    delay = 0
+        width = getattr(layer, "out_size", width)
     look = getattr(model, "lookahead", None)
+    kinds = {e["kind"] for e in layers}
+    if "lc" in kinds and ("state" in kinds or look is not None):
+        raise ValueError("no streaming form of latency-controlled recurrences beside forward-only ones or a lookahead layer")
     if look is not None:
         delay = look.lookahead
         layers.append({"kind": "lookahead", "K": delay, "R": look.W.shape[0]})
@@ -234,6 +247,14 @@ class AcousticStream:
     to ``delay + 1`` frames.  A slot fed x_len frames in any cuts and flushed has emitted ceil(x_len / k) frames.  ``delay``,
     ``lengths`` and ``frames`` count output frames; in input frames the output lags by up to k * delay + k - 1.
 
+    A model with ``latency_control`` = (Nc, Nr) (bidirectional, every recurrent layer an ``nn.LCBiGRU``) streams
+    too: every layer carries its forward direction's state and the up to K = Nc + Nr - 1 input rows that wait for the right context
+    of their block, and emits whole blocks.  ``delay`` = num_layers * K is then a bound: ``advance`` returns ``delay`` + To rows, of
+    which ``lengths[b]`` (a multiple of Nc) are the slot's, and ``flush`` ends the masked slots layer by layer -- a layer's [pending
+    rows | what the layer in front of it emitted] are its utterance's end, every block in them is closed as the one-shot forward
+    closes a truncated one -- and returns up to ``delay`` (+ 1 with ``time_reduction``) rows.  The blocks are anchored at a slot's
+    frame 0, so what comes out does not depend on the cuts.
+
     ``frames``
     (B) int32 on the device counts the logit frames a slot has emitted since it was last reset (``flush`` leaves the finished
     utterance's count standing until the slot is fed again).  Rows of `logits` at or beyond ``lengths[b]`` are unspecified (the
@@ -275,6 +296,14 @@ class AcousticStream:
         self._look = e and (rows(e["K"], e["R"]), per_slot(), rows(e["K"] + self.max_chunk, e["R"]))
         self.k, e = self.plan.get("time_reduction", 1), kinds.get("stack")
         self._stack = e and (rows(e["K"], e["R"]), per_slot(), rows(-(-(e["K"] + self.max_chunk) // self.k), self.k * e["R"]))
+        # per latency-controlled layer (plan entry, the layer, the forward direction's state, pending rows, their count per slot, the
+        # window [pending | incoming]): layer l takes up to l * K + To rows from the one in front of it and holds up to K of its own
+        self._lc, incoming = [], -(-(self.k - 1 + self.max_chunk) // self.k)
+        for e in self.plan["layers"]:
+            if e["kind"] == "lc":
+                self._lc.append((e, model.rnn_blocks.layers[e["index"]], torch.zeros((1, self.B, e["H"]), dtype=torch.float32, device=dev),
+                                 rows(e["K"], e["R"]), per_slot(), rows(e["K"] + incoming, e["R"])))
+                incoming += e["K"]
         self.frames = per_slot()
         self._ended = per_slot(torch.bool)          # flushed and not fed since: `frames` is the old count
         self._ones = torch.ones((self.B,), dtype=torch.int32, device=dev)
@@ -336,14 +365,17 @@ class AcousticStream:
             _ops.time_stack_push_reset(self._stack[0], self._stack[1], mask)
         if self._look is not None:
             _ops.stream_push_reset(self._look[0], self._look[1], mask)
+        for _, _, _, state, m, _ in self._lc:
+            _ops.stream_push_reset(state, m, mask)
+        states = self._h + [carry[2] for carry in self._lc]
         if mask is None:
-            for h in self._h:
+            for h in states:
                 h.zero_()
             self.frames.zero_()
             self._ended.zero_()
         else:
             on = mask != 0
-            for h in self._h:
+            for h in states:
                 h.masked_fill_(on.view(1, self.B, 1), 0)
             self.frames.masked_fill_(on, 0)
             self._ended.masked_fill_(on, False)
@@ -390,7 +422,10 @@ class AcousticStream:
                 groups = groups[:To]
                 steps = _ops.time_stack_push(state, m, functions.phys3(out), n, groups, self.k)
                 out = functions.logical3(groups)
-            logits, lengths = self._tail(self._recurrences(out, steps), steps, self.delay + To, To)
+            if self._lc:
+                logits, lengths = self._tail(*self._blocks(out, steps), None)
+            else:
+                logits, lengths = self._tail(self._recurrences(out, steps), steps, self.delay + To, To)
             if lengths is None:
                 lengths = torch.full((self.B,), Tc, dtype=torch.int32, device=self.device)
             elif lengths is n:
@@ -404,6 +439,33 @@ class AcousticStream:
             out, hy = layer(out, steps, hx=h)
             h.copy_(hy)                     # (a slot beyond its length keeps its state bit for bit: csrc/gru.hip pins its update gate)
         return out
+
+    def _blocks(self, out, steps, flush=None):
+        """The latency-controlled layers on `out` (B, D, To) with steps[b] new frames per slot (None: all; `out` None: nothing new).
+        Every layer lays [its pending rows | the incoming ones] into its window, runs the forward direction from the carried state
+        over the emit[b] frames of the whole blocks whose right context is there, the reverse direction over those w[b] blocks as
+        windows (the one-shot layer's own kernels and order of sums), and hands the emit[b] frames on as the next layer's chunk.
+        The slots in `flush` end: their rows are the utterance's end, every block of them is whole (the one-shot rule for a
+        truncated window) and all of them are emitted.  -> (the last layer's output (B, H, rows of its window), emitted frames (B));
+        a layer that holds nothing back (Nc = 1, Nr = 0: K = 0) and is handed nothing has no rows: (None, zeros) if it is the last."""
+        chunk = None if out is None else functions.phys3(out)
+        for entry, layer, h, state, m, window in self._lc:
+            Nc, Nr = entry["Nc"], entry["Nr"]
+            rows = entry["K"] + (0 if chunk is None else chunk.shape[0])
+            if rows == 0:
+                chunk, steps = None, torch.zeros((self.B,), dtype=torch.int32, device=self.device)
+                continue
+            window = window[:rows]
+            a, w, steps = _ops.lc_push(state, m, chunk, steps, window, Nc, Nr, flush)
+            if layer.w_ih.numel() == 0:     # (a model that never ran: the layer sizes its input weights at its first call)
+                layer._initialize_params(entry["R"])
+            params = (layer.w_ih, layer.w_hh, layer.b_ih, layer.b_hh)
+            fwd, hy = functions.gru(functions.logical3(window), *functions.lc_direction(params, 0), layer.directions[0], 1, steps, hx=h)
+            h.copy_(hy)                     # (a slot beyond its length keeps its state bit for bit, as in _recurrences)
+            xw, w_len = _ops.lc_gather(window, Nc, Nr, _ops.LC_WINDOW, a, w)
+            yw = functions.gru(functions.logical3(xw), *functions.lc_direction(params, 1), layer.directions[1], 1, w_len)
+            chunk = _ops.lc_scatter(functions.phys3(yw), rows, self.B, Nc, Nr, _ops.LC_BLOCK, functions.phys3(fwd), a, w)
+        return (None if chunk is None else functions.logical3(chunk)), steps
 
     def _tail(self, out, steps, rows, keep=None, flush=None, ended=None):
         """What follows the recurrences: the lookahead, if the model has one, and the dense layers.  `out` (B, D, To) with steps[b]
@@ -438,13 +500,26 @@ class AcousticStream:
         the slot is fed again).  With time_reduction > 1: (delay + 1, B, V), the zero-completed last group first."""
         mask = self._ones if mask is None else self._slots(mask, "mask")
         with torch.no_grad():
-            if self._stack is not None:
+            logits = None
+            if self._lc:
+                # layer by layer: the incomplete group, if there is one, is the first layer's last frame; every layer then emits all
+                # of [its pending rows | what the layer in front of it emitted], up to `delay` (+ 1) frames behind the last one
+                out = steps = None
+                if self._stack is not None:
+                    state, m, groups = self._stack
+                    steps = _ops.time_stack_push(state, m, None, None, groups[:1], self.k, flush=mask)
+                    out = functions.logical3(groups[:1])
+                out, lengths = self._blocks(out, steps, flush=mask)
+                if out is not None:
+                    logits, lengths = self._tail(out, lengths, None)
+            elif self._stack is not None:
                 logits, lengths = self._flush_stacked(mask)
             elif self._look is not None:
                 logits, lengths = self._tail(None, None, self.delay, flush=mask)
             else:
-                logits = torch.empty((0, self.B, self._vocab), dtype=torch.float32, device=self.device)
                 lengths = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
+            if logits is None:              # (nothing is held back anywhere)
+                logits = torch.empty((0, self.B, self._vocab), dtype=torch.float32, device=self.device)
         count = self.frames + lengths
         self.reset(mask)
         on = mask != 0

@@ -51,6 +51,31 @@ class BiGRU(_GRUBase):
         super().__init__(in_size, out_size, 2)
 
 
+class LCBiGRU(_GRUBase):
+    """The latency-controlled bidirectional GRU (LC-BLSTM in the literature; include/asr_hip.h states the semantics): the forward
+    direction runs over the whole utterance, the reverse direction is restarted from a zero state for every block of `block` frames
+    and sees `right` frames of right context beyond it.  Exactly a ``BiGRU``'s parameters, names and shapes, so a checkpoint of one
+    loads into the other; it is trained in this form and streams with a bounded delay (asr/model/stream.py).  With block >= T it is
+    ``BiGRU``."""
+
+    def __init__(self, in_size, out_size=None, block=32, right=16):
+        if out_size is None:
+            in_size, out_size = None, in_size
+        block, right = functions.lc_check(block, right)
+        super().__init__(in_size, out_size, 2)
+        self.block, self.right = block, right
+        # the 16-bit weight copies are cached by the weight's address: one holder per direction, or the two slices evict each other
+        self.directions = torch.nn.ModuleList([Link(), Link()])
+
+    def __call__(self, x, x_length=None, hx=None):
+        """x (B, D, T) -> (B, H, T), the directions summed; x_length (B) int32 on the device: every utterance over its own length"""
+        if hx is not None:
+            raise ValueError("LCBiGRU takes no initial state: asr.model.stream.AcousticStream carries it chunk by chunk")
+        if self.w_ih.numel() == 0:
+            self._initialize_params(x.shape[1])
+        return functions.lc_bigru(x, self.w_ih, self.w_hh, self.b_ih, self.b_hh, self, self.block, self.right, x_length)
+
+
 class _NStep(Link):
     """chainer.links.NStepGRU / NStepBiGRU call semantics: ``hy, ys = rnn(hx, xs)`` with ``xs`` a list of (T_i, I) sequences
     (any lengths), ``hx`` None (zero initial state) or (n_layers * ndir, B, H) (a given one runs the layer on the per-step kernels),

@@ -14,7 +14,7 @@ from ..link import Chain, Link, Parameter, get_initializer, initializers  # noqa
 from .convolution_1d import Convolution1D
 from .convolution_2d import Convolution2D as WeightnormConvolution2D
 from .convolution_2d import PlainConvolution2D
-from .gru import GRU, NStepBiGRU, NStepGRU, BiGRU  # noqa: F401
+from .gru import GRU, NStepBiGRU, NStepGRU, BiGRU, LCBiGRU  # noqa: F401
 from .layernorm import normalize_layer  # noqa: F401
 from .lookahead import LookaheadConvolution  # noqa: F401
 from .sru import SRU  # noqa: F401

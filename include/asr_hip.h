@@ -1105,6 +1105,47 @@ int asr_time_stack_push(void* stream, void* state, int* m, const void* chunk, co
                         int Tc, int B, int R, int k);
 int asr_time_stack_push_reset(void* stream, void* state, int* m, const int* mask, int B, int R, int k);
 
+/* ---------------------------------------------------------------------------------------- latency-controlled bidirectional GRU
+ * The layer (asr.nn.LCBiGRU, asr.functions.lc_bigru) on x logical (B, D, T), len[b] = x_length[b] clamped to 0..T (T without
+ * lengths), a block of Nc >= 1 frames, Nr >= 0 frames of right context, W = min(Nc + Nr, T):
+ *   forward direction   as nn.GRU with the direction-0 parameters over t = 0 .. len[b] - 1 from a zero state.
+ *   reverse direction   for every block c = 0 .. ceil(len[b] / Nc) - 1, with e = min((c + 1) Nc + Nr, len[b]): the state is zero at e,
+ *                       the direction-1 recurrence runs t = e - 1 down to c Nc, and its outputs are kept for
+ *                       c Nc <= t < min((c + 1) Nc, len[b]); the Nr right-context steps only warm the state up.
+ *   output              y[t] = h_fwd[t] + h_rev[t] (summed, as BiGRU does), zero at t >= len[b]; no gradient enters or leaves the
+ *                       padding.  With Nc >= T the layer is mathematically nn.BiGRU.
+ * The reverse direction runs as a batch of C * B windows, C = ceil(T / Nc), window (c, b) at index c * B + b, each time-reversed so
+ * that the ndir = 1 recurrence serves it with per-window lengths.  Window (c, b) has L = clamp(len[b] - c Nc, 0, W) live rows; with
+ * n_win (B) int32 not NULL, L = 0 for c >= n_win[b].  x, y, addend (T, B, R) and xw, yw (W, C * B, R) are 16-bit activations.
+ *   asr_lc_gather   xw[j, c B + b] = x[c Nc + L - 1 - j, b] for j < L and L - 1 - j < keep, zero elsewhere; w_len[c B + b] = L
+ *                   (w_len may be NULL).  mode ASR_LC_WINDOW: keep = W (the inputs).  mode ASR_LC_BLOCK: keep = Nc (the output
+ *                   gradient: the adjoint of the crop, right-context outputs receive none).
+ *   asr_lc_scatter  for t < len[b]: y[t, b] = addend[t, b] (0 if addend is NULL) + the sum over c, ascending, of
+ *                   yw[L_c - 1 - (t - c Nc), c B + b] over the windows with c Nc <= t < c Nc + L_c.  mode ASR_LC_BLOCK: only the
+ *                   frame's own block c = t / Nc (the forward pass: the two directions summed).  mode ASR_LC_WINDOW: every such
+ *                   window (the overlap-add of the input gradient, up to 1 + ceil(Nr / Nc) terms).  float32 accumulation in that
+ *                   order, one rounding to the activation type.  y is zero at t >= len[b]; every element of y is written.
+ * The two are adjoint in pairs: gather(ASR_LC_BLOCK) of scatter(ASR_LC_BLOCK), gather(ASR_LC_WINDOW) of scatter(ASR_LC_WINDOW).
+ * asr_lc_push is the streaming carry.  Per slot b, state (K, B, R), K = Nc + Nr - 1, holds m[b] <= K pending rows.  The call takes
+ * n[b] rows of chunk (Tc, B, R) (n NULL = Tc; clamped to [0, Tc]) and writes window (K + Tc, B, R) = [m[b] pending | n[b] new | zeros],
+ * a[b] = m[b] + n[b], w[b] = max(0, a[b] - Nr) / Nc (the whole blocks whose right context is present) and emit[b] = w[b] Nc; for a
+ * slot with flush[b] != 0 (flush (B) int32 or NULL), whose [pending | new] rows are its utterance's end: w[b] = ceil(a[b] / Nc) and
+ * emit[b] = a[b].  Rows emit[b] .. a[b] - 1 become the new state (the rows behind them are zeroed) and their count the new m[b].  A
+ * slot with n[b] == 0 and no flush keeps its state bytes.  Two launches: the first reads the state and writes the window, a, w and
+ * emit; the second reads those and writes the state and m.  Reset: asr_stream_push_reset(state, m, mask, K, B, R).
+ * ASR_ERR_BAD_ARG, and nothing launched or written: Nc < 1, Nr < 0, R < 8 or R % 8 != 0, B < 1, a negative T or Tc, T above 2^30,
+ * a mode other than the two, W (or, for the push, Nc + Nr) above ASR_LC_MAX_WINDOW, C * B or a tensor's count of 16-byte lanes that
+ * does not fit 31 bits, a NULL tensor that would be accessed.  T == 0 (gather, scatter) is ASR_OK and writes nothing. */
+#define ASR_LC_MAX_WINDOW 4096
+#define ASR_LC_WINDOW 0
+#define ASR_LC_BLOCK 1
+int asr_lc_gather(void* stream, const void* x, const int* x_len, const int* n_win, void* xw, int* w_len, int T, int B, int R, int Nc,
+                  int Nr, int mode);
+int asr_lc_scatter(void* stream, const void* yw, const void* addend, const int* x_len, const int* n_win, void* y, int T, int B, int R,
+                   int Nc, int Nr, int mode);
+int asr_lc_push(void* stream, void* state, int* m, const void* chunk, const int* n, const int* flush, void* window, int* a, int* w,
+                int* emit, int Tc, int B, int R, int Nc, int Nr);
+
 /* ---------------------------------------------------------------------------------------- streaming log-mel front end
  * Samples in chunk by chunk, feature frames out, for B batch slots that start and end on their own: for every way of cutting a
  * signal the emitted frames are, bit for bit, those of asr_specgram_bands + asr_deltas on the whole signal (L = frame_len,
