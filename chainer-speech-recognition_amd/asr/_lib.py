@@ -211,6 +211,9 @@ SIGNATURES = {
     "asr_sru_fwd": (c_int, [c_void_p] * 9 + [c_int] * 4 + [c_void_p, c_size_t]),
     "asr_sru_bwd": (c_int, [c_void_p] * 13 + [c_int] * 4 + [c_void_p, c_size_t]),
     "asr_sru_combine": (c_int, [c_void_p] * 5 + [c_longlong, c_int]),
+    "asr_sru_seq_ws_bytes": (c_size_t, [c_int] * 4),
+    "asr_sru_seq_fwd": (c_int, [c_void_p] * 9 + [c_int] * 6 + [c_void_p, c_size_t]),
+    "asr_sru_seq_bwd": (c_int, [c_void_p] * 13 + [c_int] * 6 + [c_void_p, c_size_t]),
     "asr_fill_f32": (c_int, [c_void_p, c_void_p, c_longlong, c_float]),
     "asr_sqnorm_acc": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p]),
     "asr_clip_decay_sgd": (c_int, [c_void_p] * 4 + [c_longlong, c_int] + [c_float] * 5 + [c_void_p]),

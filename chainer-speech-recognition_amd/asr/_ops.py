@@ -681,6 +681,40 @@ def sru_combine(a, b, mask):
     return out
 
 
+def _sru_seq_ws(T, B, D, ndir, dev):
+    n = int(_lib.lib().asr_sru_seq_ws_bytes(T, B, D, ndir))
+    return (torch.empty(n, dtype=torch.uint8, device=dev), n) if n else (None, 0)
+
+
+def sru_seq_fwd(x, U, bias, cx, x_len, T, B, D, k, ndir, use_tanh):
+    """x (T, B, D) bf16 (k = 3; None for k = 4), U (T*B, ndir k D) f32, bias (ndir, 2D), cx (ndir, B, D) f32 or None, x_len (B) int32
+    or None -> y (T, B, D) bf16 (directions summed), C (ndir, T, B, D) f32, cy (ndir, B, D) f32   (include/asr_hip.h)"""
+    dev = U.device
+    x_len = _len_i32(x_len, B, dev)
+    y = torch.empty((T, B, D), dtype=BF16, device=dev)
+    C = torch.empty((ndir, T, B, D), dtype=F32, device=dev)
+    cy = torch.empty((ndir, B, D), dtype=F32, device=dev)
+    ws, n = _sru_seq_ws(T, B, D, ndir, dev)
+    rc = _lib.lib().asr_sru_seq_fwd(stream(), ptr(x), ptr(U), ptr(bias), ptr(cx), ptr(x_len), ptr(y), ptr(C), ptr(cy), T, B, D, int(k),
+                                    int(ndir), int(bool(use_tanh)), ptr(ws), n)
+    check(rc, "asr_sru_seq_fwd")
+    return y, C, cy
+
+
+def sru_seq_bwd(x, U, bias, C, cx, x_len, gy, dcy, gbias, T, B, D, k, ndir, use_tanh, need_dcx=True):
+    """-> gU (T*B, ndir k D) bf16, gxh (T, B, D) bf16 (k = 3) or None, dcx (ndir, B, D) f32 or None; gbias (ndir, 2D) f32 is added to"""
+    dev = U.device
+    x_len = _len_i32(x_len, B, dev)
+    gU = torch.empty((T * B, ndir * k * D), dtype=BF16, device=dev)
+    gxh = torch.empty((T, B, D), dtype=BF16, device=dev) if k == 3 else None
+    dcx = torch.empty((ndir, B, D), dtype=F32, device=dev) if need_dcx else None
+    ws, n = _sru_seq_ws(T, B, D, ndir, dev)
+    rc = _lib.lib().asr_sru_seq_bwd(stream(), ptr(x), ptr(U), ptr(bias), ptr(C), ptr(cx), ptr(x_len), ptr(gy), ptr(dcy), ptr(gU), ptr(gxh),
+                                    ptr(gbias), ptr(dcx), T, B, D, int(k), int(ndir), int(bool(use_tanh)), ptr(ws), n)
+    check(rc, "asr_sru_seq_bwd")
+    return gU, gxh, dcx
+
+
 def clip_decay_sgd(p, g, v, kind, lr, momentum, weight_decay, clip, grad_scale, sqnorm):
     rc = _lib.lib().asr_clip_decay_sgd(stream(), ptr(p), ptr(g), ptr(v), p.numel(), int(kind), lr, momentum, weight_decay,
                                        clip, grad_scale, ptr(sqnorm))

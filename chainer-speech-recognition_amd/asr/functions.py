@@ -1290,6 +1290,72 @@ def gru(x, w_ih, w_hh, b_ih, b_hh, link, ndir, x_length=None, hx=None):
     return logical3(y.reshape(T, B, H))
 
 
+# ---------------------------------------------------------------------------------------------- SRU as a sequence layer
+class _SRUSeq(torch.autograd.Function):
+    """x rows (T*B, I) bf16, cx (ndir, B, D) float32 or None -> y rows (T*B, D) bf16 (directions summed) and cy (ndir, B, D) float32.
+    include/asr_hip.h states the semantics; the two GEMMs are the ones nn.sru.SRUFunction runs, over the stacked (ndir k D, I) weight."""
+
+    @staticmethod
+    def forward(ctx, x2, W, Bias, cx, copies, T, B, D, k, ndir, x_len, use_tanh):
+        ctx.set_materialize_grads(False)
+        w16, w16t = copies
+        U = _ops.gemm_nt(x2, w16, None, F32)
+        cx = None if cx is None else cx.detach().to(F32).contiguous()
+        y, C, cy = _ops.sru_seq_fwd(x2 if k == 3 else None, U, Bias.detach(), cx, x_len, T, B, D, k, ndir, use_tanh)
+        ctx.save_for_backward(x2, U, C, w16t, cx)
+        ctx.params = (W, Bias)
+        ctx.meta = (T, B, D, k, ndir, x_len, use_tanh, ctx.needs_input_grad[0], ctx.needs_input_grad[3])
+        return y.reshape(T * B, D), cy
+
+    @staticmethod
+    def backward(ctx, gy, gcy):
+        x2, U, C, w16t, cx = ctx.saved_tensors
+        W, Bias = ctx.params
+        T, B, D, k, ndir, x_len, use_tanh, need_dx, need_dcx = ctx.meta
+        if gy is None:      # (only cy received a gradient)
+            gy = torch.zeros((T * B, D), dtype=BF16, device=U.device)
+        dcy = None if gcy is None else gcy.to(F32).contiguous()
+        gU, gxh, dcx = _ops.sru_seq_bwd(x2 if k == 3 else None, U, Bias.detach(), C, cx, x_len, _as_act(gy), dcy, grad_buffer(Bias),
+                                        T, B, D, k, ndir, use_tanh, need_dcx)
+        _ops.gemm_tn_acc(gU, x2, grad_buffer(W).reshape(ndir * k * D, -1))
+        grads_queued(W, Bias)
+        gx = None
+        if need_dx:
+            gx = _ops.gemm_nt(gU, w16t, None, BF16)
+            if k == 3:          # + the highway's share
+                gx = _ops.sru_combine(gx.reshape(T, B, D), gxh, None).reshape(T * B, D)
+        return gx, None, None, dcx, None, None, None, None, None, None, None, None
+
+
+def sru_seq(x, W, B, link, ndir, x_length=None, cx=None, use_tanh=True):
+    """The SRU as a recurrent layer (include/asr_hip.h: "SRU as a sequence layer").  x logical (B, I, T); W (ndir, k D, I) with rows
+    [z; f; r] (k = 3, exactly when I == D: the highway carries x) or [z; f; r; p] (k = 4: it carries the projection p); B (ndir, 2D) =
+    [b_f; b_r] -> logical (B, D, T), the directions summed.
+    x_length (B) int32 device tensor or None: every utterance over its own frames as ``gru`` runs them -- direction 1 starts at
+    x_length[b] - 1, the output is zero beyond the length and the padding receives / passes no gradient.
+    cx (ndir, B, D) float32 or None: the initial cell states; given one, the result is (y, cy), cy (ndir, B, D) the states after every
+    utterance's last own frame in scan order (x_length[b] = 0: cy = cx on bits)."""
+    p = phys3(x)
+    T, Bn, I = p.shape
+    if W.dim() != 3 or W.shape[0] != ndir or W.shape[2] != I or tuple(B.shape) != (ndir, B.shape[-1]) or B.shape[-1] % 2:
+        raise ValueError("W must be (ndir, k D, I) and B (ndir, 2 D), got %s and %s for ndir = %d, I = %d"
+                         % (tuple(W.shape), tuple(B.shape), ndir, I))
+    D = B.shape[-1] // 2
+    k = 3 if I == D else 4
+    if W.shape[1] != k * D:
+        raise ValueError("W has %d rows per direction: an input of width %d into %d units takes k = %d blocks, %d rows"
+                         % (W.shape[1], I, D, k, k * D))
+    copies = (
+        link.compute_copy("w16", W, lambda w: _ops.cast_bf16(w.reshape(-1, w.shape[-1])), "plain"),
+        link.compute_copy("w16t", W, lambda w: _ops.cast_bf16(w.reshape(-1, w.shape[-1]), transpose=True), "t_last"),
+    )
+    if cx is not None and tuple(cx.shape) != (ndir, Bn, D):
+        raise ValueError("cx must have shape (ndir, B, D) = %s, got %s" % ((ndir, Bn, D), tuple(cx.shape)))
+    y, cy = _SRUSeq.apply(p.reshape(T * Bn, I), W, B, cx, copies, T, Bn, D, k, ndir, x_length, bool(use_tanh))
+    y = logical3(y.reshape(T, Bn, D))
+    return y if cx is None else (y, cy)
+
+
 # ---------------------------------------------------------------------------------------------- latency-controlled BiGRU
 def _as_act(g):
     """an incoming gradient as contiguous 16-bit activations"""

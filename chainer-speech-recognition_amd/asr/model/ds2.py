@@ -13,15 +13,22 @@ forward (the template drops it, run/ctc/sru/model.py:120-124).  SURVEY.md sectio
   run over ceil(T / k) frames and the model emits that many (``output_length``).
   ``latency_control`` = (Nc, Nr) (with bidirectional=True) makes every recurrent layer an nn.LCBiGRU: the reverse directions restart
   per block of Nc frames with Nr frames of right context, and the model streams with a delay of num_rnn_layers * (Nc + Nr - 1) frames.
+  ``rnn`` = "sru" makes every recurrent layer an nn.BiSeqSRU (or nn.SeqSRU with bidirectional=False) in place of the GRU links: the
+  cell recurrence is linear in its state, so a layer is two scans that run time in parallel chunks and not T dependent steps
+  (csrc/sru_seq.hip); it takes x_length, lookahead, time_reduction and dropout as the GRU stack does and, forward-only, streams.
 """
 from .. import _ops, functions, nn
 from .base import NeedsVocabulary
 from ._acoustic import load_if_exists, save_atomic, split_output
 
 
+_RECURRENT = (nn.GRU, nn.BiGRU, nn.LCBiGRU, nn.SeqSRU, nn.BiSeqSRU)
+
+
 class Configuration(NeedsVocabulary):
     FIELDS = dict(ndim_audio_features=3, ndim_conv=64, ndim_rnn=512, ndim_dense=320, num_conv_layers=2, num_rnn_layers=4,
-                  bidirectional=True, kernel_size=(3, 5), dropout=0, lookahead=0, time_reduction=1, latency_control=None)
+                  bidirectional=True, kernel_size=(3, 5), dropout=0, lookahead=0, time_reduction=1, latency_control=None,
+                  rnn="gru")
 
 
 def configure():
@@ -79,9 +86,19 @@ class Model(nn.Module):
                 raise ValueError("latency_control and lookahead > 0 do not combine: the right context is the model's lookahead")
         self.latency_control = control
 
+        # the recurrent cell.  A configuration from before the field reads as "gru"; with "gru" the model is what it was, attribute
+        # for attribute and parameter name for parameter name.
+        cell = getattr(config, "rnn", "gru")
+        if cell not in ("gru", "sru"):
+            raise ValueError("rnn must be \"gru\" or \"sru\", got %r" % (cell,))
+        if cell == "sru" and control is not None:
+            raise ValueError("latency_control with rnn=\"sru\" is not built: the windowed reverse direction exists for the GRU only")
+
         rnn_blocks = nn.Module()
         for _ in range(config.num_rnn_layers):
-            if control is not None:
+            if cell == "sru":
+                rnn = (nn.BiSeqSRU if config.bidirectional else nn.SeqSRU)(None, config.ndim_rnn)
+            elif control is not None:
                 rnn = nn.LCBiGRU(None, config.ndim_rnn, block=control[0], right=control[1])
             else:
                 rnn = (nn.BiGRU if config.bidirectional else nn.GRU)(None, config.ndim_rnn)
@@ -119,7 +136,7 @@ class Model(nn.Module):
             out_data = self.rnn_blocks(out_data)
         else:
             for layer in self.rnn_blocks.layers:
-                out_data = layer(out_data, x_length) if isinstance(layer, (nn.GRU, nn.BiGRU, nn.LCBiGRU)) else layer(out_data)
+                out_data = layer(out_data, x_length) if isinstance(layer, _RECURRENT) else layer(out_data)
         if getattr(self, "lookahead", None) is not None:
             out_data = self.lookahead(out_data, x_length)
         out_data = self.dense_blocks(out_data)
@@ -137,7 +154,8 @@ class Model(nn.Module):
         (h, c) -- asr/serializers.py stores the reference's order.  With time_reduction = k the stacked columns are (j, h, c),
         j the frame of the group; they are declared as (C, k * H), so the file holds them as (c, j, h): channel-major like the
         reference's, a fixed permutation that load inverts exactly (no reference checkpoint has stacked features to agree with)."""
-        return {"rnn_blocks._sequential_0.w_ih": (self._merged[0], self._merged[1] * self.time_reduction)}
+        first = "W" if isinstance(self.rnn_blocks.layers[0], (nn.SeqSRU, nn.BiSeqSRU)) else "w_ih"
+        return {"rnn_blocks._sequential_0.%s" % first: (self._merged[0], self._merged[1] * self.time_reduction)}
 
     def save(self, filename):
         save_atomic(self, filename)

@@ -25,8 +25,11 @@ are into ``asr.error.BeamStream.advance``, ``asr.error.GramBeamStream.advance`` 
 The features come chunk by chunk from ``asr.fft.FeatureStream``: its ``(x, lengths)`` go as they are into
 ``advance``, with ``max_chunk >= FeatureStream.max_frames``.
 
-Not covered: the SRU template (its reference model drops the recurrent output and ``asr_sru_fwd`` has no
-per-slot lengths; ``stream_plan`` is where it would plug in), and a backward pass through a stream.
+A ``ds2.Model`` with ``rnn="sru"`` and ``bidirectional=False`` streams the same way: an ``nn.SeqSRU`` layer
+carries its cell state, (1, B, D) float32 per layer, and a chunk is one projection and one scan per layer whatever its frame count.
+
+Not covered: ``nn.SRU`` itself (the reference's link has no per-slot lengths and its reference model drops the recurrent output), a
+bidirectional SRU stack, and a backward pass through a stream.
 """
 import torch
 
@@ -128,6 +131,7 @@ def stream_plan(model):
       {"kind": "stack", "K": k - 1, "R": height * channels of the conv stack's output, "k": k}      the frames of a group of
        k not yet complete (only with time_reduction = k > 1, and then the plan also has "time_reduction": k)
       {"kind": "state", "H": units, "index": position in rnn_blocks.layers}      a GRU layer's hidden state
+      {"kind": "state", "H": units, "index": position in rnn_blocks.layers, "cell": "sru"}      an nn.SeqSRU layer's cell state
       {"kind": "lookahead", "K": lookahead, "R": features}                       the lookahead layer's pending frames
       {"kind": "lc", "H": units, "index": position in rnn_blocks.layers, "Nc": block, "Nr": right context, "K": Nc + Nr - 1,
        "R": the layer's input width}      a latency-controlled BiGRU layer: the forward direction's state and up to K pending
@@ -135,7 +139,7 @@ def stream_plan(model):
     A ``cnn.AcousticModel`` (architectures.build_model) carries only convolution contexts, and its delay is 0: one "context" entry
     per convolution wider than one frame, as above with "index": position in model.layers and "path": (index,), or (index, inner)
     for a layer inside a Residual.  The convolution of a GLU is model.layers[index].W.
-    ValueError: neither of the two, a ds2.Model with plain BiGRU layers (their reverse recurrences need the whole utterance), or, in the layers
+    ValueError: neither of the two, a ds2.Model with plain BiGRU or BiSeqSRU layers (their reverse recurrences need the whole utterance), or, in the layers
     of a cnn.AcousticModel as in the conv stack of a ds2.Model (_walk_layers walks both), a convolution that looks ahead in time or a
     layer without a per-frame form (pooling over time, BatchNormalization, a recurrent layer, a Residual that changes shape)."""
     layers, height, channels = _walk(model)
@@ -146,7 +150,7 @@ def stream_plan(model):
         layers.append({"kind": "stack", "K": k - 1, "R": height * channels, "k": k})
     delay, width = 0, k * height * channels
     for index, layer in enumerate(model.rnn_blocks.layers):
-        if isinstance(layer, nn.BiGRU):
+        if isinstance(layer, (nn.BiGRU, nn.BiSeqSRU)):
             raise ValueError("a bidirectional model cannot be streamed: its reverse recurrences start at the end of the utterance")
         if isinstance(layer, nn.LCBiGRU):
             K = layer.block + layer.right - 1
@@ -154,6 +158,8 @@ def stream_plan(model):
             delay += K
         if isinstance(layer, nn.GRU):
             layers.append({"kind": "state", "H": layer.out_size, "index": index})
+        if isinstance(layer, nn.SeqSRU):
+            layers.append({"kind": "state", "H": layer.out_size, "index": index, "cell": "sru"})
         width = getattr(layer, "out_size", width)
     look = getattr(model, "lookahead", None)
     kinds = {e["kind"] for e in layers}
@@ -336,7 +342,7 @@ class AcousticStream:
                 raise ValueError("the model leaves %d rows per frame: logits need one" % height)
             mark_logit_layers(model.layers)     # the last projection and normalisation write float32, as in the one-shot call
         else:
-            self._grus = [layer for layer in model.rnn_blocks.layers if isinstance(layer, nn.GRU)]
+            self._grus = [layer for layer in model.rnn_blocks.layers if isinstance(layer, (nn.GRU, nn.SeqSRU))]
             self._dense = [layer for layer in model.dense_blocks.layers if _name(layer) != "Dropout"]
             self._vocab = model.dense_blocks.layers[-2].out_channels
 
@@ -434,10 +440,11 @@ class AcousticStream:
         return logits, lengths
 
     def _recurrences(self, out, steps):
-        """the GRU layers on (B, D, To) from their carried states, over steps[b] frames per slot (None: all)"""
+        """the GRU or SeqSRU layers on (B, D, To) from their carried states, over steps[b] frames per slot (None: all)"""
         for layer, h in zip(self._grus, self._h):
             out, hy = layer(out, steps, hx=h)
-            h.copy_(hy)                     # (a slot beyond its length keeps its state bit for bit: csrc/gru.hip pins its update gate)
+            # (a slot beyond its length keeps its state bit for bit: csrc/gru.hip pins its update gate, csrc/sru_seq.hip hands cx on)
+            h.copy_(hy)
         return out
 
     def _blocks(self, out, steps, flush=None):

@@ -18,6 +18,7 @@ from .gru import GRU, NStepBiGRU, NStepGRU, BiGRU, LCBiGRU  # noqa: F401
 from .layernorm import normalize_layer  # noqa: F401
 from .lookahead import LookaheadConvolution  # noqa: F401
 from .sru import SRU  # noqa: F401
+from .sru_seq import SeqSRU, BiSeqSRU  # noqa: F401
 from .time_stack import TimeStack  # noqa: F401
 
 

@@ -966,6 +966,42 @@ int asr_sru_bwd(void* stream, const void* x_bf16, const float* U, const float* b
 int asr_sru_combine(void* stream, const void* a_bf16, const void* b_bf16, const float* mask, void* out_bf16, long long n,
                     int BD);
 
+/* ---------------------------------------------------------------------------------------- SRU as a sequence layer
+ * The SRU above as a recurrent layer of the DS2 family (asr.functions.sru_seq, nn.SeqSRU / nn.BiSeqSRU; csrc/sru_seq.hip): per-utterance
+ * lengths, ndir in {1, 2} directions, input width I != D, a carried cell state per direction.  The entries above are untouched.
+ *
+ * One layer has input width I, width D and ndir directions, each direction dir with parameters of its own, on (T, B, .) activations:
+ *   U_t = W_dir x_t,  W_dir (k D, I) with rows [z; f; r] (k = 3) or [z; f; r; p] (k = 4).  k = 3 exactly when I == D (the reference's
+ *   form, nn.SRU's parameter layout) and the highway input is xh_t = x_t; otherwise k = 4 and xh_t = U_p, the projection.
+ *   f = sigmoid(U_f + b_f)   r = sigmoid(U_r + b_r)   c_t = f c_prev + (1 - f) z   h_t = r g(c_t) + (1 - r) xh_t,  g = tanh or identity.
+ *   Direction 0 scans t = 0 .. x_len[b] - 1, direction 1 scans t = x_len[b] - 1 .. 0; both start from cx[dir, b] (NULL = zeros).
+ *   x_len (B) int32 on the device, NULL = T for every utterance; an entry outside 0 .. T is CLAMPED to that range.
+ *   Frames t >= x_len[b]: y is zero, the state is frozen, and the frame receives and passes no gradient (gU and gxh are zero there,
+ *   gy is not read there) -- what functions.gru leaves in its padding.  C is not written there.
+ *   cy[dir, b] = the state after the utterance's last own frame in scan order; x_len[b] = 0 gives cy = cx bit for bit (and dcx = dcy).
+ *   y = sum over dir of h^dir.
+ * Rounding points of y: every h^dir is formed in float32 registers from the float32 U, the float32 state and -- k = 3 -- the 16-bit x;
+ * the sum over directions is taken in float32 in the same thread and y is rounded ONCE, to the 16-bit activation format, when it is
+ * stored.  There is no 16-bit h per direction.  C and cy are float32 and never rounded.  Likewise backward: gxh = gy sum_dir (1 - r^dir)
+ * is summed in float32 and rounded once; every block of gU is rounded once.
+ * Operands: x (T, B, D) bf16, read only when k = 3 (may be NULL for k = 4); U (T*B, ndir k D) f32, direction-major column blocks
+ * [dir][z | f | r (| p)] -- ONE product of the shared x with the stacked (ndir k D, I) weight; bias (ndir, 2D) [b_f | b_r];
+ * cx, cy, dcy, dcx (ndir, B, D) f32 (cx, dcy, dcx may be NULL); C (ndir, T, B, D) f32 saved for the backward pass; y, gy (T, B, D) bf16;
+ * gU (T*B, ndir k D) bf16, all k blocks (the p block: gy (1 - r)); gxh (T, B, D) bf16, the highway's gradient of x, written when k = 3
+ * (may be NULL for k = 4); gbias (ndir, 2D) f32 is ACCUMULATED into.  The caller forms U and the weight / input gradients with
+ * asr_gemm_nt / asr_gemm_tn_acc.
+ * ws: asr_sru_seq_ws_bytes(T, B, D, ndir) bytes (0: none needed), required where that is not 0 (ASR_ERR_WORKSPACE).  Chunked scans as
+ * above; odd D or operands off an 8-byte (float) / 4-byte (16-bit) boundary run one feature per lane instead of two, and T < 32 runs as
+ * one chunk: the same kernels.  ASR_ERR_BAD_ARG: T, B or D <= 0, k not in {3, 4}, ndir not in {1, 2}, a NULL required pointer.
+ * The IEEE-half build refuses (ASR_ERR_UNSUPPORTED).
+ */
+size_t asr_sru_seq_ws_bytes(int T, int B, int D, int ndir);
+int asr_sru_seq_fwd(void* stream, const void* x_bf16, const float* U, const float* bias, const float* cx, const int* x_len,
+                    void* y_bf16, float* C, float* cy, int T, int B, int D, int k, int ndir, int use_tanh, void* ws, size_t ws_bytes);
+int asr_sru_seq_bwd(void* stream, const void* x_bf16, const float* U, const float* bias, const float* C, const float* cx,
+                    const int* x_len, const void* gy_bf16, const float* dcy, void* gU_bf16, void* gxh_bf16, float* gbias, float* dcx,
+                    int T, int B, int D, int k, int ndir, int use_tanh, void* ws, size_t ws_bytes);
+
 /* ---------------------------------------------------------------------------------------- optimiser step
  * GradientClipping -> WeightDecay -> Adam over one flat buffer (run/ctc/cnn/train.py:142-147,200).
  * grad_scale multiplies every gradient first (1/world_size after a sum all-reduce).
